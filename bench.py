@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """BQSR (observe + apply) throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--dump-outputs DIR] [--full]
 
 One step = one whole BQSR job over the GPU's read shard, inputs resident in
 HBM: zero the covariate table, observe (+ the exact expectedMismatch fold),
@@ -10,9 +10,12 @@ expectedMismatch folded in rank order], finalize, apply.  `bases` = sum of the
 sequence lengths of ALL reads (filtered ones included).  The ranks' shards
 are consecutive read ranges of one synthetic dataset (cfg2 / cfg4: the
 config's reads per GPU, weak scaling; cfg3: the 60M-read set split over the
-ranks), the job's partitions in rank order.  After the timed jobs every rank
-checks the last job's table, expectedMismatch and recalibrated chars against
-the oracle (oracle/, outside the timed region); rank 0 prints one JSON line.
+ranks), the job's partitions in rank order.  A plain run sets up, warms up,
+times the K jobs, writes the last job's results with --dump-outputs, and rank 0
+prints one JSON line.  With --full it goes on, outside the timed region: stage
+times by HIP events and the roofline, layout times, the CPU baseline, and every
+rank checks the last job's table, expectedMismatch and recalibrated chars
+against the oracle (oracle/); the line then carries them too.
 See DESIGN.md "Measurement".
 """
 from __future__ import annotations
@@ -53,11 +56,19 @@ def parse(argv=None):
     ap.add_argument("--reads", type=int, default=None, help="reads per GPU (default: the config's)")
     ap.add_argument("--sorted", action="store_true",
                     help="coordinate-sorted reads (as after transform -sort_reads; the known-site A/B of cfg3)")
-    ap.add_argument("--cpu-reads", type=int, default=10_000_000, help="oracle baseline sample (reads)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the timed job's results")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: per-stage HIP-event "
+                         "times and the roofline, the layout times, the CPU baseline and the oracle parity check "
+                         "(each with its own switch below); without it only the timed steps run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64; big arrays "
+                         "as a fixed seeded sample of reads, see dump_outputs)")
+    ap.add_argument("--cpu-reads", type=int, default=10_000_000, help="--full: oracle baseline sample (reads)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="--full without the oracle check of the timed job's results")
     ap.add_argument("--event-steps", type=int, default=3,
-                    help="untimed jobs after the timed region whose stages are timed with HIP events")
+                    help="--full: untimed jobs after the timed region whose stages are timed with HIP events")
     ap.add_argument("--tune", action="append", default=[], metavar="KNOB=V",
                     help="bqsr_context_tune layout knob for an A/B run (order, fronts, key_major)")
     ap.add_argument("--traffic", default=None,
@@ -68,7 +79,13 @@ def parse(argv=None):
                          "apply writing into pinned host memory")
     ap.add_argument("--d2h", default="kernel", choices=("kernel", "dma"),
                     help="cfg5: results copied back by a kernel (beside the DMA uploads) or by DMA copies")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the timed steps and the result line only
+        args.no_cpu_baseline = args.no_parity = True
+        args.event_steps = 0
+    return args
 
 
 def _free_port() -> int:
@@ -212,16 +229,18 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    # per-stage times: HIP events on the launch stream over extra jobs after
-    # the timed region (an event record costs the stream ~30 us, so the timed
-    # jobs carry none; the stage times include their launch gaps)
+    if args.dump_outputs and rank == 0:
+        dump_resident(args.dump_outputs, job, batch, max(cfg["lens"]))
+    # per-stage times (--full): HIP events on the launch stream over extra jobs
+    # after the timed region (an event record costs the stream ~30 us, so the
+    # timed jobs carry none; the stage times include their launch gaps)
     for _ in range(max(0, args.event_steps)):
         job.step(True)
     torch.cuda.synchronize()
-    # what a bucketed batch pays once at creation, outside the repeated job:
-    # the piece-key sort and the key-major copy (bqsr_batch_relayout)
-    layout_ms = job.layout_ms()
-    layout_created = job.layout_times()
+    # what a bucketed batch pays once at creation, outside the repeated job
+    # (--full): the piece-key sort and the key-major copy (bqsr_batch_relayout)
+    layout_ms = job.layout_ms() if args.full else None
+    layout_created = job.layout_times() if args.full else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         D.allreduce(t, dist.ReduceOp.MAX)
@@ -231,11 +250,10 @@ def main():
         total_bases = int(nb.item())
     else:
         total_bases = n_bases
-    kt = job.kt
 
-    # parity of the last job's results against the oracle (every rank checks
-    # its own shard; N > 1 with the all-reduced oracle table), outside the
-    # timed region; the CPU baseline on rank 0 at N = 1
+    # --full: parity of the last job's results against the oracle (every rank
+    # checks its own shard; N > 1 with the all-reduced oracle table), outside
+    # the timed region; the CPU baseline on rank 0 at N = 1
     cpu_line, parity = None, None
     if world == 1:
         ref = None
@@ -250,34 +268,7 @@ def main():
         parity = parity_multi(job, cfg, batch, sites, world, rank, dev)
 
     if rank == 0:
-        ms = {k: float(np.mean(v)) for k, v in kt.items() if v}
         R = batch.n_reads
-        # algorithmic bytes: observe 1.75 B/base + 16 B/read, apply 2.5 B/base + 16 B/read
-        alg = {"observe": 1.75 * n_bases + 16 * R, "apply": 2.5 * n_bases + 16 * R}
-        tpath = args.traffic or os.path.join(ROOT, "profiles", "pmc_traffic_%s.json" % args.config)
-        tr = _profile_json(tpath, args.config, R)  # PMC bytes per launch (tools/make_traffic.py)
-        kpath = os.path.join(ROOT, "profiles", "kernel_stats_%s.json" % args.config)
-        ks = _profile_json(kpath, args.config, R)  # rocprofv3 kernel averages (tools/make_kstats.py)
-        # the dominant kernel: the longer one by rocprof's kernel-only averages of
-        # this tree's committed profile; by the live HIP events without one
-        rp = {k: ks["kernels"][k]["avg_ms"] for k in alg if ks and k in ks["kernels"]}
-        src = rp if len(rp) == 2 else ms
-        dom = "observe" if src.get("observe", 0) >= src.get("apply", 0) else "apply"
-        kernels = {}
-        for k in alg:
-            e = {"alg_bytes_per_launch": alg[k], "events_ms": ms.get(k),
-                 "events_frac": alg[k] / (ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if ms.get(k) else None}
-            if k in rp:
-                e.update(kernel=ks["kernels"][k]["kernel"], rocprof_ms=rp[k],
-                         rocprof_frac=alg[k] / (rp[k] * 1e-3) / 1e9 / HBM_PEAK_GBS)
-            if tr and k in tr["kernels"]:
-                e.update(traffic=tr["kernels"][k]["hbm_bytes_per_launch"],
-                         traffic_x_alg=tr["kernels"][k]["hbm_bytes_per_launch"] / alg[k])
-            kernels[k] = e
-        kernels["dominant"] = dom
-        achieved = alg[dom] / (ms[dom] * 1e-3) / 1e9 if dom in ms else None
-        traffic = kernels[dom].get("traffic")
-        kname = kernels[dom].get("kernel", "bqsr_%s" % dom)
         value = args.steps * total_bases / elapsed
         line = {
             "metric": METRIC,
@@ -302,38 +293,25 @@ def main():
                 "known_sites": int(sum(len(v) for v in sites.values())) if sites else 0,
                 "parallelism": "dp%d: read shards per GPU, RCCL int64 table all-reduce" % world,
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": kname,
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS if achieved else None,
-                "traffic": traffic,
-                "traffic_source": tpath if traffic is not None else None,
-                "alg_bytes_per_launch": alg[dom],
-                "kernel_ms": ms,
-                "kernel_ms_method": "HIP events on the launch stream around each stage over %d untimed jobs after "
-                                    "the timed region (apply: the kernel alone, its char tables before the "
-                                    "bracket)" % args.event_steps,
-                "kernels": kernels,
-                "kernels_source": {"rocprof": kpath if rp else None, "commit": ks.get("commit") if ks else None},
-            },
             "hbm_roofline_frac_step": (total_bases / world) * (4.25 + 32.0 / max(cfg["lens"])) /
                                       (elapsed / args.steps) / (HBM_PEAK_GBS * 1e9),
-            "layout_ms": layout_ms,
-            "layout_alloc_ms": layout_created[0] if layout_created else None,
-            "layout_build_ms": layout_created[1] if layout_created else None,
-            "job_with_layout_ms": ((elapsed / args.steps * 1e3 + layout_created[0] + layout_created[1])
-                                   if layout_created else None),
-            "layout_note": ("bucketed batch: the piece-key sort (and, with key_major=1, the key-major copy of "
-                            "quals / codes) runs once when the batch is created (outside the timed jobs); "
-                            "layout_alloc_ms / layout_build_ms are its allocation and kernel wall times at creation, "
-                            "layout_ms the kernels redone on the batch, job_with_layout_ms a single job that pays "
-                            "both -- the single-pass cost of a partition")
-                           if layout_created else None,
             "gen_s": t_gen,
         }
+        if args.full:
+            line["roofline"] = roofline_resident(args, job.kt, n_bases, R)
+            line.update({
+                "layout_ms": layout_ms,
+                "layout_alloc_ms": layout_created[0] if layout_created else None,
+                "layout_build_ms": layout_created[1] if layout_created else None,
+                "job_with_layout_ms": ((elapsed / args.steps * 1e3 + layout_created[0] + layout_created[1])
+                                       if layout_created else None),
+                "layout_note": ("bucketed batch: the piece-key sort (and, with key_major=1, the key-major copy of "
+                                "quals / codes) runs once when the batch is created (outside the timed jobs); "
+                                "layout_alloc_ms / layout_build_ms are its allocation and kernel wall times at "
+                                "creation, layout_ms the kernels redone on the batch, job_with_layout_ms a single "
+                                "job that pays both -- the single-pass cost of a partition")
+                               if layout_created else None,
+            })
         if cpu_line is not None:
             line["cpu_baseline"] = cpu_line
         if parity is not None:
@@ -342,6 +320,56 @@ def main():
     job.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def roofline_resident(args, kt, n_bases, R):
+    """--full: the `roofline` entry of a resident config's line, from the stage
+    times of the event steps and this tree's committed profile summaries."""
+    import numpy as np
+    ms = {k: float(np.mean(v)) for k, v in kt.items() if v}
+    # algorithmic bytes (SURVEY.md 8d): observe 1.75 B/base + 16 B/read, apply 2.5 B/base + 16 B/read
+    alg = {"observe": 1.75 * n_bases + 16 * R, "apply": 2.5 * n_bases + 16 * R}
+    tpath = args.traffic or os.path.join(ROOT, "profiles", "pmc_traffic_%s.json" % args.config)
+    tr = _profile_json(tpath, args.config, R)  # PMC bytes per launch (tools/make_traffic.py)
+    kpath = os.path.join(ROOT, "profiles", "kernel_stats_%s.json" % args.config)
+    ks = _profile_json(kpath, args.config, R)  # rocprofv3 kernel averages (tools/make_kstats.py)
+    # the dominant kernel: the longer one by rocprof's kernel-only averages of
+    # this tree's committed profile; by the live HIP events without one
+    rp = {k: ks["kernels"][k]["avg_ms"] for k in alg if ks and k in ks["kernels"]}
+    src = rp if len(rp) == 2 else ms
+    dom = "observe" if src.get("observe", 0) >= src.get("apply", 0) else "apply"
+    kernels = {}
+    for k in alg:
+        e = {"alg_bytes_per_launch": alg[k], "events_ms": ms.get(k),
+             "events_frac": alg[k] / (ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if ms.get(k) else None}
+        if k in rp:
+            e.update(kernel=ks["kernels"][k]["kernel"], rocprof_ms=rp[k],
+                     rocprof_frac=alg[k] / (rp[k] * 1e-3) / 1e9 / HBM_PEAK_GBS)
+        if tr and k in tr["kernels"]:
+            e.update(traffic=tr["kernels"][k]["hbm_bytes_per_launch"],
+                     traffic_x_alg=tr["kernels"][k]["hbm_bytes_per_launch"] / alg[k])
+        kernels[k] = e
+    kernels["dominant"] = dom
+    achieved = alg[dom] / (ms[dom] * 1e-3) / 1e9 if dom in ms else None
+    traffic = kernels[dom].get("traffic")
+    kname = kernels[dom].get("kernel", "bqsr_%s" % dom)
+    return {
+        "bound": "hbm",
+        "kernel": kname,
+        "achieved": achieved,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS if achieved else None,
+        "traffic": traffic,
+        "traffic_source": tpath if traffic is not None else None,
+        "alg_bytes_per_launch": alg[dom],
+        "kernel_ms": ms,
+        "kernel_ms_method": "HIP events on the launch stream around each stage over %d untimed jobs after "
+                            "the timed region (apply: the kernel alone, its char tables before the "
+                            "bracket)" % args.event_steps,
+        "kernels": kernels,
+        "kernels_source": {"rocprof": kpath if rp else None, "commit": ks.get("commit") if ks else None},
+    }
 
 
 def _profile_json(path, config, reads):
@@ -355,6 +383,90 @@ def _profile_json(path, config, reads):
     if d.get("config") != config or d.get("reads_per_gpu") != reads or "kernels" not in d:
         return None
     return d
+
+
+DUMP_READS = 32768  # reads whose chars --dump-outputs writes (32768 x 250 f32 = 32 MB at most)
+DUMP_WORDS = 1 << 21  # table words it writes (f64: 16 MB at most)
+
+
+def _dump_pick(n, k):
+    """Every index below n when n <= k, else a fixed sample of k (seeded, sorted)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(20240229).choice(n, k, replace=False)).astype(np.int64)
+
+
+def slot_bases(batch):
+    """Packed slot of every read's first char in the padded device layout (the
+    running sum of max(qual, sequence) lengths, each rounded up to 16)."""
+    import numpy as np
+    from adam_amd.records import F_HAS_QUAL, F_HAS_SEQ
+    f = np.asarray(batch.flags)
+    lq = np.where(f & F_HAS_QUAL, np.diff(np.asarray(batch.qual_offset).astype(np.int64)), 0)
+    ls = np.where(f & F_HAS_SEQ, np.diff(np.asarray(batch.seq_offset).astype(np.int64)), 0)
+    sl = (np.maximum(lq, ls) + 15) // 16 * 16
+    out = np.zeros(len(sl) + 1, np.int64)
+    np.cumsum(sl, out=out[1:])
+    return out[:-1]
+
+
+def dump_outputs(path, words, em, first, lens, chars, exc, max_len):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    job, as float arrays two builds can be compared by:
+      table.npy              f64  the covariate table's int64 words (exact below 2^53; over DUMP_WORDS words a
+                                  fixed seeded sample)
+      expected_mismatch.npy  f64  [1], the job's expectedMismatch
+      out_len.npy            f32  recalibrated length of each sampled read (every read, or a fixed seeded
+                                  sample of DUMP_READS in read order)
+      out_chars.npy          f32  [len(reads), max_len]: their recalibrated chars as Java char codes, chars above
+                                  0xFF taken from the exception list, -1 behind the read's end
+    `first`: position of each sampled read's first char in `chars` (u8), `exc`
+    the (position << 16 | char) exception words."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    words = np.asarray(words)
+    np.save(os.path.join(path, "table.npy"), words[_dump_pick(len(words), DUMP_WORDS)].astype(np.float64))
+    np.save(os.path.join(path, "expected_mismatch.npy"), np.asarray([em], dtype=np.float64))
+    lens = np.asarray(lens).astype(np.int64)
+    np.save(os.path.join(path, "out_len.npy"), lens.astype(np.float32))
+    k = np.arange(max_len, dtype=np.int64)[None, :]
+    pos = np.asarray(first).astype(np.int64)[:, None] + k
+    live = k < lens[:, None]
+    out = np.full(pos.shape, -1.0, dtype=np.float32)
+    if len(chars):
+        out[live] = chars[np.minimum(pos[live], len(chars) - 1)]
+    if len(exc):
+        e = np.sort(np.asarray(exc).astype(np.int64))  # by position
+        ep, ec = e >> 16, e & 0xFFFF
+        at = np.minimum(np.searchsorted(ep, pos), len(ep) - 1)
+        hit = live & (ep[at] == pos)
+        out[hit] = ec[at[hit]]
+    np.save(os.path.join(path, "out_chars.npy"), out)
+
+
+def dump_resident(path, job, batch, max_len):
+    """--dump-outputs of a resident job (this rank's shard)."""
+    words, em, q, st, ln, exc = job.results()
+    reads = _dump_pick(batch.n_reads, DUMP_READS)
+    first = slot_bases(batch)[reads] + st[reads]
+    dump_outputs(path, words, em, first, ln[reads], q, exc, max_len)
+
+
+def dump_stream(path, sh, table_t, part0, max_len):
+    """--dump-outputs of a streamed job: the table, expectedMismatch and the
+    chars of this rank's first partition."""
+    import numpy as np
+    res = sh.outputs(0)
+    reads = _dump_pick(part0.n_reads, DUMP_READS)
+    if res[0] == "compact":
+        _, q, off, exc = res
+        off = off.astype(np.int64)
+        first, lens = off[reads], off[reads + 1] - off[reads]
+    else:
+        _, q, st, ln, exc = res
+        first, lens = slot_bases(part0)[reads] + st[reads], ln[reads]
+    dump_outputs(path, table_t.cpu().numpy(), float(sh._em_keep.cpu()[0]), first, lens, q, exc, max_len)
 
 
 def oracle_shard(cfg, batch, sites):
@@ -505,8 +617,11 @@ def main_stream(args, cfg, world, rank, dev, ctx):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_stream(args.dump_outputs, sh, table_t, first, dims.max_len)
     apply_ms = [sh.apply_ms()]
-    probe_ms = sh.apply_probe_ms(0)  # the kernel alone (no copies in flight), for the roofline
+    # --full: the kernel alone (no copies in flight), for the roofline
+    probe_ms = sh.apply_probe_ms(0) if args.full else None
     n_bases = sh.n_bases
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -558,7 +673,12 @@ def main_stream(args, cfg, world, rank, dev, ctx):
                 "outputs": "compacted chars + u16 lengths" if sh.compact else "padded slots + start/len",
                 "parallelism": "dp%d: read shards per GPU, RCCL int64 table all-reduce" % world,
             },
-            "roofline": {
+            "pcie": {"h2d_bytes_per_step": h2d, "d2h_bytes_per_step": d2h,
+                     "achieved_GBps": (h2d + d2h) / (ms_step * 1e-3) / 1e9},
+            "gen_s": t_gen,
+        }
+        if args.full:
+            line["roofline"] = {
                 "bound": "hbm",
                 "kernel": "bqsr_apply_kernel (partition 0: %d reads)" % int(R0),
                 "achieved": achieved,
@@ -572,11 +692,7 @@ def main_stream(args, cfg, world, rank, dev, ctx):
                                     "jobs, no copies in flight (mean of 3); in_pipeline: the recorded timed job's "
                                     "brackets, sharing the GPU with the copies of the other partitions",
                 "bound_note": "cfg5 is PCIe-bound: see `pcie` (the link, not HBM, sets the job time)",
-            },
-            "pcie": {"h2d_bytes_per_step": h2d, "d2h_bytes_per_step": d2h,
-                     "achieved_GBps": (h2d + d2h) / (ms_step * 1e-3) / 1e9},
-            "gen_s": t_gen,
-        }
+            }
         if world == 1 and not args.no_cpu_baseline:
             args.cpu_reads = min(args.cpu_reads, 2_000_000)
             line["cpu_baseline"] = cpu_baseline(args, cfg, first, None)[0]

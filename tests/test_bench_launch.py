@@ -63,7 +63,7 @@ def test_bench_multi_rank_without_gpu_fails_loudly():
 
 def _run_gpu_bench(extra):
     p = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--steps", "2", "--warmup", "1", "--event-steps", "1", "--no-cpu-baseline"] + extra,
+                        "--steps", "2", "--warmup", "1", "--full", "--event-steps", "1", "--no-cpu-baseline"] + extra,
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

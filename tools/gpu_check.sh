@@ -19,8 +19,8 @@ if [ "$MODE" = tests ]; then
   tail -2 "$O/pytest.log"
 fi
 for c in $CFGS; do
-  extra="--no-parity --no-cpu-baseline"
-  [ "$c" = cfg2 ] && extra=""  # the parity check reuses the CPU leg's oracle run
+  extra="--full --no-parity --no-cpu-baseline"
+  [ "$c" = cfg2 ] && extra="--full"  # the parity check reuses the CPU leg's oracle run
   timeout -k 10 500 python -u bench.py --config "$c" --steps 10 $extra > "$O/bench_$c.json" 2> "$O/bench_$c.err"
   python -c "import json,sys;d=json.load(open(sys.argv[1]));print(sys.argv[2],round(d['ms_per_step'],3),{k:round(v,3) for k,v in d['roofline']['kernel_ms'].items()},d.get('parity',{}).get('ok'))" "$O/bench_$c.json" "$c"
 done

@@ -39,7 +39,7 @@ for c in $CONFIGS; do
   python3 tools/make_kstats.py "$KS" "$O/$c/kernel_stats.json" $c $READS "gpurun_out/$TAG/$c" $COMMIT
   cp "$O/$c/pmc_traffic.json" profiles/pmc_traffic_$c.json
   cp "$O/$c/kernel_stats.json" profiles/kernel_stats_$c.json
-  timeout -k 10 600 python -u bench.py --config $c > "$O/bench_$c.json" 2> "$O/bench_$c.err"
+  timeout -k 10 600 python -u bench.py --config $c --full > "$O/bench_$c.json" 2> "$O/bench_$c.err"
   cat "$O/bench_$c.json"
 done
 echo done
