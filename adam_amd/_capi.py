@@ -35,6 +35,7 @@ EXPORTS = [
     "bqsr_finalize_device", "bqsr_observe_stage", "bqsr_apply_stage", "bqsr_job_reset_async", "bqsr_job_result", "bqsr_copy_async",
     "bqsr_job_errors_export_async", "bqsr_job_errors_import_async", "bqsr_job_status_async", "bqsr_job_status_get",
     "bqsr_copy_dyn_async", "bqsr_compact_outputs_async", "bqsr_batch_exception_count_ptr",
+    "bqsr_sort_order", "bqsr_sam_sort",  # include/adam_sam.h
 ]
 
 

@@ -282,6 +282,7 @@ bqsr_status mark_duplicates_host(bqsr_sam* s, int64_t* n_duplicates) {
   }
   if (n) HIP_TRY(hipMemcpy(s->flags, flags.data(), n * 4, hipMemcpyHostToDevice));
   s->dup_marked = true;
+  s->flag_text_current = false;
   if (n_duplicates) *n_duplicates = nd;
   return ok();
 }

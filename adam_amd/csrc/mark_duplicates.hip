@@ -299,6 +299,7 @@ bqsr_status bqsr_sam_mark_duplicates(bqsr_sam* s, int64_t* n_duplicates) {
   HIP_TRY(hipSetDevice(s->ctx->device));
   if (s->n_reads == 0) {
     s->dup_marked = true;
+    s->flag_text_current = false;
     if (n_duplicates) *n_duplicates = 0;
     return ok();
   }
@@ -404,6 +405,7 @@ bqsr_status mark_duplicates_device(bqsr_sam* s, int64_t* n_duplicates, std::vect
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
   s->dup_marked = true;
+  s->flag_text_current = false;
   if (n_duplicates) *n_duplicates = (int64_t)hn;
   return ok();
 }
@@ -838,6 +840,7 @@ bqsr_status bqsr_dup_set_apply(bqsr_dup_set* d, int64_t part, bqsr_sam* s, int64
     HIP_TRY(hipStreamSynchronize(st));
   }
   s->dup_marked = true;
+  s->flag_text_current = false;
   if (n_duplicates) *n_duplicates = (int64_t)hn;
   return ok();
 }

@@ -890,6 +890,7 @@ struct bqsr_sam {
   uint64_t* line_span = nullptr;
   uint64_t* qual_span = nullptr;
   bool dup_marked = false;  // bqsr_sam_mark_duplicates ran: FLAG 0x400 rewritten on output
+  bool flag_text_current = false;  // the text's FLAG fields carry MarkDuplicates' bits (rewritten since it ran)
   bool from_bam = false;    // bqsr_bam_parse: d_text holds the records converted to SAM text on the device
   samk::NameTable sq_tab{}, rg_tab{};  // @SQ / @RG name tables on the device (ADAM columns)
   std::string header_text;  // the header lines (host copy)
@@ -1378,6 +1379,7 @@ bqsr_status bqsr_sam_rewrite_quals(bqsr_context* ctx, bqsr_sam* sm, const bqsr_b
   (void)hipFree(sm->d_text);
   sm->d_text = nt;
   sm->n_text = total;
+  sm->flag_text_current = sm->dup_marked;
   return ok();
 }
 

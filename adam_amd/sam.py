@@ -67,6 +67,8 @@ def _lib():
             "bqsr_dup_set_finish": (ctypes.c_int, [vp, ctypes.POINTER(i64)]),
             "bqsr_dup_set_apply": (ctypes.c_int, [vp, i64, vp, ctypes.POINTER(i64)]),
             "bqsr_dup_set_destroy": (None, [vp]),
+            "bqsr_sort_order": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, vp]),
+            "bqsr_sam_sort": (ctypes.c_int, [vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -159,6 +161,15 @@ class SamText:
         check(self.L.bqsr_sam_rewrite_quals(self.ctx.handle, self.h, job.bh, p(job.out_qual), p(job.out_start),
                                             p(job.out_len), p(job.exc), job.n_exc, job.sp))
 
+    def sort(self, stream=None) -> None:
+        """`transform -sort_reads` (bqsr_sam_sort,
+        core/rdd/AdamRDDFunctions.scala:63-93): the records in the
+        reference's order -- mapped reads by (referenceId, start), then the
+        unmapped ones, ties in input order.  Afterwards this is the parse of
+        the sorted text (``text()``, ``batch()``, the ADAM columns);
+        MarkDuplicates' result travels with the records."""
+        check(self.L.bqsr_sam_sort(self.ctx.handle, self.h, stream))
+
     def text(self) -> bytes:
         n = self.counts().text_bytes
         buf = ctypes.create_string_buffer(max(1, n))
@@ -214,6 +225,25 @@ class DupSet:
             self.close()
         except Exception:
             pass
+
+
+def sort_order(flags, reference_id, start, ctx: Optional[bqsr.Context] = None) -> np.ndarray:
+    """bqsr_sort_order over host columns (uploaded; the order comes back to
+    the host): order[i] = the input index of the read at sorted position i.
+    flags: the records' flag words (BQSR_F_MAPPED = readMapped;
+    BQSR_F_HAS_START unset = a null start); reference_id: -1 = null."""
+    import torch
+    L = _lib()
+    ctx = ctx or bqsr.Context.get(0)
+    n = len(flags)
+    dev = torch.device("cuda", ctx.device)
+    f = torch.from_numpy(np.ascontiguousarray(flags, np.uint32).view(np.int32)).to(dev)
+    r = torch.from_numpy(np.ascontiguousarray(reference_id, np.int32)).to(dev)
+    s = torch.from_numpy(np.ascontiguousarray(start, np.int64)).to(dev)
+    order = torch.empty(max(1, n), dtype=torch.int32, device=dev)
+    sp = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    check(L.bqsr_sort_order(ctx.handle, n, f.data_ptr(), r.data_ptr(), s.data_ptr(), order.data_ptr(), sp))
+    return order[:n].cpu().numpy().view(np.uint32).astype(np.int64)
 
 
 def mark_duplicates(read_name: Sequence[Optional[str]], library: Sequence[Optional[str]], flags, mate_mapped,

@@ -20,8 +20,20 @@ BQSR (`adamBQSR(loadSnpTable)`: an empty SnpTable without -dbsnp_sites,
 reference's adamSave writes them (core/rdd/AdamRDDFunctions.scala:37-56;
 OUTPUT.adam / .parquet / a directory), or SAM text -- the input records with
 their QUAL fields replaced by the recalibrated strings (and FLAG 0x400 by
-MarkDuplicates' result).  -sort_reads, -coalesce and
--realignIndels are outside this build and are refused.
+MarkDuplicates' result).  -coalesce and -realignIndels are outside this
+build and are refused.
+
+-sort_reads (adamSortReadsByReferencePosition,
+core/rdd/AdamRDDFunctions.scala:63-93; the last step before the save,
+cli/Transform.scala:89-93) sorts the records on the device (sam.SamText.sort:
+mapped reads by (referenceId, start), then the unmapped ones in the
+reference's counter order, ties in input order): the recalibrated text is
+written on the device, its records are sorted there and the sinks read the
+sorted parse.  ADAM Parquet input is sorted by `table.take` of the order the
+device computes from the readMapped / referenceId / start columns
+(sam.sort_order).  The input must be one partition: a global sort across
+streamed partitions is not built, and an input cut into several raises a
+ValueError before anything is read.
 
 Partitions: an input whose records exceed ``partition_bytes`` is cut at line
 boundaries into partitions (the Hadoop splits the reference's RDD is read
@@ -241,7 +253,8 @@ def _check_out(path: str, overwrite: bool, adam: bool) -> None:
 
 
 def transform_parquet(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bool = False,
-                      dbsnp: Optional[str] = None, device: int = 0, overwrite: bool = False) -> Dict[str, float]:
+                      dbsnp: Optional[str] = None, device: int = 0, overwrite: bool = False,
+                      sort_reads: bool = False) -> Dict[str, float]:
     """`transform` with ADAMRecord Parquet output (adamSave,
     core/rdd/AdamRDDFunctions.scala:37-56): the input -- Parquet (adamLoad,
     AdamContext.scala:318-331, every column kept and written back) or SAM
@@ -270,13 +283,38 @@ def transform_parquet(inp: str, out: str, mark_duplicates: bool = False, recalib
         cols = [c for c in table.column_names if c in P.BQSR_PROJECTION or c in P.MARKDUP_PROJECTION]
         A = P.ArrowReads(table.select(cols), bqsr.Context.get(device), markdup=mark_duplicates)
     try:
-        return _transform_table(A, table, batch, inp, out, mark_duplicates, recalibrate, dbsnp, device, stats, t0)
+        return _transform_table(A, table, batch, inp, out, mark_duplicates, recalibrate, dbsnp, device, stats, t0,
+                                sort_reads)
     finally:
         if A is not None:
             A.close()
 
 
-def _transform_table(A, table, batch, inp, out, mark_duplicates, recalibrate, dbsnp, device, stats, t0):
+def table_sort_order(table, ctx=None) -> np.ndarray:
+    """-sort_reads over an ADAMRecord table: the order sam.sort_order gives
+    its readMapped (null: false), referenceId and start columns"""
+    from .records import F_HAS_START, F_MAPPED
+    from .sam import sort_order
+    n = table.num_rows
+
+    def col(name, dtype, null):
+        if name not in table.column_names:
+            return np.full(n, null, dtype), np.zeros(n, bool)
+        c = table.column(name).combine_chunks()
+        valid = np.asarray(c.is_valid())
+        return np.asarray(c.fill_null(null)).astype(dtype), valid
+    mapped, _ = col("readMapped", bool, False)
+    ref, ref_ok = col("referenceId", np.int64, 0)
+    start, start_ok = col("start", np.int64, 0)
+    if np.any(mapped & ref_ok & ((ref < 0) | (ref > 0x7FFFFFFF))):
+        raise _capi.BQSRError(_capi.UNSUPPORTED, "sort_reads: a referenceId outside [0, Int.MaxValue]")
+    flags = np.where(mapped, np.uint32(F_MAPPED), np.uint32(0)) | np.where(start_ok, np.uint32(F_HAS_START),
+                                                                            np.uint32(0))
+    return sort_order(flags.astype(np.uint32), np.where(ref_ok, ref, -1).astype(np.int32), start, ctx)
+
+
+def _transform_table(A, table, batch, inp, out, mark_duplicates, recalibrate, dbsnp, device, stats, t0,
+                     sort_reads=False):
     import pyarrow.parquet as pq
 
     from . import parquet as P
@@ -306,6 +344,9 @@ def _transform_table(A, table, batch, inp, out, mark_duplicates, recalibrate, db
     # the new file first, then the old output goes (a failed write leaves the
     # previous output in place); a leftover part-file directory at the
     # .partial path (_check_out allowed it under overwrite) is removed first
+    if sort_reads:  # the last step before the save (cli/Transform.scala:89-93)
+        import pyarrow as pa
+        table = table.take(pa.array(table_sort_order(table, bqsr.Context.get(device)), pa.int64()))
     tmp = out + ".partial"
     if os.path.isdir(tmp):
         shutil.rmtree(tmp)
@@ -406,14 +447,25 @@ def is_bam(data) -> bool:
 
 def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bool = False,
               dbsnp: Optional[str] = None, device: int = 0, partition_bytes: int = DEFAULT_PARTITION_BYTES,
-              compression: str = "gzip", part_reads: int = 1 << 19, overwrite: bool = False) -> Dict[str, float]:
+              compression: str = "gzip", part_reads: int = 1 << 19, overwrite: bool = False,
+              sort_reads: bool = False) -> Dict[str, float]:
     """Transform.run (cli/Transform.scala:62-97) over SAM or BAM input: the
     records parsed on the device (a BAM's records become SAM lines there),
     MarkDuplicates, BQSR, then adamSave (OUT.adam / .parquet / a directory:
     ADAMRecord Parquet part files, adam_save.py) or SAM text.  ADAM Parquet
-    input goes through transform_parquet (Arrow reads it on the host)."""
+    input goes through transform_parquet (Arrow reads it on the host).
+    sort_reads: the records sorted on the device before the save (see the
+    module doc); the input must be one partition."""
     if is_parquet(inp):
-        return transform_parquet(inp, out, mark_duplicates, recalibrate, dbsnp, device, overwrite)
+        return transform_parquet(inp, out, mark_duplicates, recalibrate, dbsnp, device, overwrite, sort_reads)
+    if sort_reads and os.path.getsize(inp):  # refused before any output file or parse exists
+        with open(inp, "rb") as fh:
+            data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+            try:
+                if not is_bam(data) and len(sam_partitions(data, partition_bytes)[1]) > 1:
+                    raise ValueError("-sort_reads needs the input in one partition; raise -partition_bytes")
+            finally:
+                data.close()
     t0 = time.perf_counter()
     # ADAM output by name, or over an earlier adamSave directory (never just
     # because `out` is some existing directory: the sinks refuse that)
@@ -433,7 +485,7 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
             try:
                 bam = is_bam(data)
                 ranges = None
-                if (recalibrate or mark_duplicates) and not bam and len(data):
+                if (recalibrate or mark_duplicates or sort_reads) and not bam and len(data):
                     header, ranges = sam_partitions(data, partition_bytes)
                 if ranges is not None and len(ranges) > 1:
                     stats = _partitions(data, header, ranges, mark_duplicates, recalibrate, dbsnp, ctx, device,
@@ -456,12 +508,21 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
                                 with ph("bqsr"):
                                     job.step()
                                 p = job._ptr
+                                quals = (job.bh, p(job.out_qual), p(job.out_start), p(job.out_len), p(job.exc),
+                                         job.n_exc, job.sp)
+                                if sort_reads:  # the recalibrated text first: the apply's outputs are in input order
+                                    with ph("sort"):
+                                        check(_capi.lib().bqsr_sam_rewrite_quals(ctx.handle, sam.h, *quals))
+                                        sam.sort()
+                                    quals = None
                                 with ph("emit"):
-                                    sink.emit(0, sam, (job.bh, p(job.out_qual), p(job.out_start), p(job.out_len),
-                                                       p(job.exc), job.n_exc, job.sp))
+                                    sink.emit(0, sam, quals)
                             finally:
                                 job.close()
                         else:
+                            if sort_reads:
+                                with ph("sort"):  # (MarkDuplicates' FLAG bits go into the text there)
+                                    sam.sort()
                             with ph("emit"):
                                 sink.emit(0, sam, None)
                     finally:
@@ -488,8 +549,9 @@ def main(argv=None) -> int:
     ap.add_argument("-mark_duplicate_reads", action="store_true")
     ap.add_argument("-recalibrate_base_qualities", action="store_true")
     ap.add_argument("-dbsnp_sites", default=None)
-    for flag in ("-sort_reads", "-realignIndels"):
-        ap.add_argument(flag, action="store_true")
+    ap.add_argument("-sort_reads", action="store_true",
+                    help="sort the records by reference position before the save (one partition)")
+    ap.add_argument("-realignIndels", action="store_true")
     ap.add_argument("-coalesce", type=int, default=-1)
     ap.add_argument("-partition_bytes", type=int, default=DEFAULT_PARTITION_BYTES,
                     help="records per streamed partition, in bytes of SAM text")
@@ -499,11 +561,11 @@ def main(argv=None) -> int:
     ap.add_argument("-overwrite", action="store_true",
                     help="replace an existing output (a file, or a directory of ADAM part files only)")
     a = ap.parse_args(argv)
-    if a.sort_reads or a.realignIndels or a.coalesce != -1:
-        ap.error("-sort_reads / -coalesce / -realignIndels are outside this build")
+    if a.realignIndels or a.coalesce != -1:
+        ap.error("-coalesce / -realignIndels are outside this build")
     st = transform(a.input, a.output, a.mark_duplicate_reads, a.recalibrate_base_qualities, a.dbsnp_sites,
                    partition_bytes=a.partition_bytes, compression=a.parquet_compression, part_reads=a.part_reads,
-                   overwrite=a.overwrite)
+                   overwrite=a.overwrite, sort_reads=a.sort_reads)
     print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
     return 0
 

@@ -261,6 +261,47 @@ bqsr_status bqsr_mark_duplicates(const bqsr_dup_reads* reads, uint8_t* dup);
  * `transform -mark_duplicate_reads` does before BQSR. */
 bqsr_status bqsr_sam_mark_duplicates(bqsr_sam* s, int64_t* n_duplicates);
 
+/* Sort by reference position (`transform -sort_reads`):
+ * adamSortReadsByReferencePosition (adam-core/.../rdd/AdamRDDFunctions.scala:63-93)
+ * with ReferencePosition's ordering (models/ReferencePosition.scala:73-95,
+ * 155-166: referenceId, then pos), the last step of Transform.run
+ * (adam-cli/.../cli/Transform.scala:89-93), after MarkDuplicates and BQSR.
+ *   mapped reads (readMapped, the BQSR_F_MAPPED bit: FLAG non-zero (Q2)
+ *     without 0x4): key (referenceId, start); referenceId is the @SQ index.
+ *     A mapped read whose referenceId or start is null (RNAME "*" or not in
+ *     @SQ, POS 0) makes the reference throw a NullPointerException
+ *     (mappedPositionCheck wraps both in Some(...), the constructor unboxes
+ *     null): BQSR_ERR_NULL_FIELD naming the first such read in input order
+ *     (bqsr_last_error_read), the parse left unchanged.
+ *   every other read: key (Int.MaxValue - c, Long.MaxValue), c = n mod 10001
+ *     with n the read's 1-based ordinal among the unmapped reads of its
+ *     partition (the iterator at :70-82 counts 1 .. 10000, then 0).  They
+ *     follow all mapped reads in descending c: up to 10000 of them in the
+ *     reverse of their input order; 10002 come out as 10000, 9999, .., 1,
+ *     10002, 10001.  The whole input is one partition.
+ *   equal keys keep their input order (a stable sort: what the reference
+ *     gives on one partition; Spark leaves it to the shuffle otherwise).
+ * BQSR_ERR_UNSUPPORTED for what the packed 64-bit key cannot order: a
+ * negative referenceId or start, a start >= 2^32 - 1, a mapped referenceId >=
+ * Int.MaxValue - 10000, more than 2^32 - 1 reads.
+ *
+ * order[i] = input index of the read at sorted position i (device, [n]);
+ * flags' BQSR_F_MAPPED bit, reference_id / start with nulls marked as the
+ * parse's columns mark them (reference_id -1; start without
+ * BQSR_F_HAS_START in flags); device pointers */
+bqsr_status bqsr_sort_order(bqsr_context* ctx, int64_t n, const uint32_t* flags, const int32_t* reference_id,
+                            const int64_t* start, uint32_t* order, void* stream);
+/* the parse's records reordered as above: the new text is the header bytes
+ * unchanged (no "SO:coordinate": this is not samtools' coordinate order),
+ * then the records as bqsr_sam_rewrite_quals(b = NULL) emits them, in
+ * sorted order; the handle is then what bqsr_sam_parse of that text gives
+ * (columns, counts, referenceNames in first-appearance order, ADAM columns),
+ * with MarkDuplicates' result carried along.  BQSR_ERR_INVALID_ARG while a
+ * bqsr_sam_adam_set_quals is pending (its batch is in the old order: rewrite
+ * the text first).  Peak device memory: twice the text, and the new columns
+ * beside the old ones while the records are parsed again. */
+bqsr_status bqsr_sam_sort(bqsr_context* ctx, bqsr_sam* s, void* stream);
+
 /* MarkDuplicates across the partitions of one input (the reference's
  * groupBy spans every partition of the RDD, MarkDuplicates.scala:43-58).
  * add: one partition's parse (partitions in input order, each parsed with

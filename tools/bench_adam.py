@@ -4,8 +4,11 @@ SAM text (or BAM) in a file, the whole transform timed -- device parse,
 MarkDuplicates, BQSR, ADAM columns on the device, Parquet part files written
 by host threads -- and one JSON line printed with the phase split.
 
-    python tools/bench_adam.py --reads 10000000 [--bam] [--no-markdup]
+    python tools/bench_adam.py --reads 10000000 [--bam] [--no-markdup] [--sort_reads]
         [--compression none|snappy|gzip] [--part-reads N] [--partition-bytes B]
+
+--sort_reads adds `-sort_reads` (the "sort" phase in the stats' phase split)
+and prints record_text_bytes: the gather kernel (sort_gather) moves twice that.
 """
 import argparse
 import json
@@ -67,6 +70,7 @@ def main():
     ap.add_argument("--bam", action="store_true")
     ap.add_argument("--bgzf", type=int, default=1, help="BAM: 1 inflate on the device (default), 0 on host threads")
     ap.add_argument("--no-markdup", action="store_true")
+    ap.add_argument("--sort_reads", action="store_true", help="transform -sort_reads")
     ap.add_argument("--compression", default="snappy")
     ap.add_argument("--part-reads", type=int, default=1 << 19)
     ap.add_argument("--partition-bytes", type=int, default=8 << 30)
@@ -92,6 +96,7 @@ def main():
     with open(src, "wb") as fh:
         fh.write(data)
     n_bytes = len(data)
+    header_bytes = 0 if a.bam else len(T.sam_partitions(data, len(data))[0])
     del data
     out = os.path.join(work, "out.adam")
     try:
@@ -99,14 +104,14 @@ def main():
         log("warm-up transform")
         T.transform(src, out, mark_duplicates=not a.no_markdup, recalibrate=True,
                     partition_bytes=a.partition_bytes, compression=a.compression, part_reads=a.part_reads,
-                    overwrite=True)
+                    overwrite=True, sort_reads=a.sort_reads)
         best = None
         for _ in range(a.reps):
             log("timed transform")
             t0 = time.perf_counter()
             st = T.transform(src, out, mark_duplicates=not a.no_markdup, recalibrate=True,
                              partition_bytes=a.partition_bytes, compression=a.compression, part_reads=a.part_reads,
-                             overwrite=True)
+                             overwrite=True, sort_reads=a.sort_reads)
             dt = time.perf_counter() - t0
             if best is None or dt < best[0]:
                 best = (dt, st)
@@ -122,6 +127,7 @@ def main():
             "seconds": dt, "reads_per_s": a.reads / dt, "compression": a.compression,
             "bgzf": (("device" if a.bgzf else "host threads") if a.bam else None),
             "part_reads": a.part_reads, "partition_bytes": a.partition_bytes, "gen_seconds": t_gen,
+            "sort_reads": a.sort_reads, "record_text_bytes": None if a.bam else n_bytes - header_bytes,
             "stats": {k: v for k, v in st.items()}}))
     finally:
         if not a.dir:
