@@ -15,6 +15,8 @@
 //
 // Included by bqsr_capi.cpp after sam_ingest.hip / bam_ingest.hip.
 
+#include "adam_fields.h"  // flag_bit, referenceId / mapq / mateReferenceId of a line (shared with flagstat.hip)
+
 namespace adamk {
 
 constexpr int kStr = 6;    // readName, sequence, cigar, qual, mismatchingPositions, attributes
@@ -250,22 +252,19 @@ __device__ void adam_record(const AdamParams& P, int64_t r, AdamRec& x, Tag* tg)
   (void)samk::parse_int(t, fa[1], fb[1], &flag);  // (the parse accepted FLAG; POS when the reference is known)
   x.flag = (uint32_t)flag;
   if (P.dup_flags)  // FLAG 0x400 following duplicateRead, as bqsr_sam_rewrite_quals writes it
-    x.flag = (P.dup_flags[r] & BQSR_F_DUPLICATE) ? (x.flag | 0x400u) : (x.flag & ~0x400u);
-  int32_t sq = -1;
-  if (!(fb[2] - fa[2] == 1 && t[fa[2]] == '*')) sq = samk::name_lookup(P.sq, t + fa[2], fb[2] - fa[2]);
+    x.flag = flag_with_dup(x.flag, P.dup_flags[r]);
+  const int32_t sq = rname_id(P.sq, t, fa[2], fb[2]);
   // referenceId / referenceName / start / mapq only when the read has a reference (:36-54)
   x.i32[0] = sq;
   x.iv[0] = sq >= 0;
   const bool has_pos = sq >= 0 && samk::parse_int(t, fa[3], fb[3], &pos) && pos != 0;
   x.i64[0] = has_pos ? pos - 1 : 0;
   x.iv[4] = has_pos;
-  const bool has_mapq = sq >= 0 && samk::parse_int(t, fa[4], fb[4], &mapq) && mapq != 255;
+  const bool has_mapq = mapq_field(t, fa[4], fb[4], sq, &mapq);
   x.i32[1] = has_mapq ? (int32_t)mapq : 0;
   x.iv[1] = has_mapq;
   // the mate (:56-71): RNEXT "=" is RNAME's reference
-  int32_t msq = -1;
-  if (fb[6] - fa[6] == 1 && t[fa[6]] == '=') msq = sq;
-  else if (!(fb[6] - fa[6] == 1 && t[fa[6]] == '*')) msq = samk::name_lookup(P.sq, t + fa[6], fb[6] - fa[6]);
+  const int32_t msq = rnext_id(P.sq, t, fa[6], fb[6], sq);
   x.i32[2] = msq;
   x.iv[2] = msq >= 0;
   const bool has_mpos = msq >= 0 && samk::parse_int(t, fa[7], fb[7], &pnext) && pnext > 0;
@@ -295,26 +294,6 @@ __device__ void adam_record(const AdamParams& P, int64_t r, AdamRec& x, Tag* tg)
       x.code = code;
       x.attr_n = 0;
     }
-  }
-}
-
-// SAMRecordConverter.scala:72-108: every flag false when the FLAG word is 0;
-// the pair flags only for paired reads
-__device__ __forceinline__ bool flag_bit(uint32_t f, int k) {
-  if (f == 0) return false;
-  const bool paired = f & 0x1;
-  switch (k) {
-    case 0: return paired;                       // readPaired
-    case 1: return paired && (f & 0x2);          // properPair
-    case 2: return !(f & 0x4);                   // readMapped
-    case 3: return paired && !(f & 0x8);         // mateMapped
-    case 4: return f & 0x10;                     // readNegativeStrand
-    case 5: return paired && (f & 0x20);         // mateNegativeStrand
-    case 6: return paired && (f & 0x40);         // firstOfPair
-    case 7: return paired && (f & 0x80);         // secondOfPair
-    case 8: return !(f & 0x100);                 // primaryAlignment
-    case 9: return f & 0x200;                    // failedVendorQualityChecks
-    default: return f & 0x400;                   // duplicateRead
   }
 }
 

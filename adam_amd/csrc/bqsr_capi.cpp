@@ -256,6 +256,10 @@ struct bqsr_context {
   int tune_fronts = -1;
   int tune_keymajor = 0;
   int tune_bgzf = 1;  // BAM ingest: BGZF inflated on the device (BQSR_TUNE_BGZF), 0 by host threads
+  int tune_flagstat_grid = 0;  // flagstat kernels: at most this many workgroups (BQSR_TUNE_FLAGSTAT_GRID), 0 auto
+  // flagstat's counter block (flagstat.hip: 37 words, allocated on first use; one call at a time)
+  std::mutex flagstat_mu;
+  unsigned long long* d_flagstat = nullptr;
 };
 
 namespace {
@@ -500,6 +504,10 @@ bqsr_status bqsr_context_tune(bqsr_context* ctx, int knob, int64_t value) {
       if (value < 0 || value > 1) break;
       ctx->tune_bgzf = (int)value;
       return BQSR_OK;
+    case BQSR_TUNE_FLAGSTAT_GRID:
+      if (value < 0 || value > (1 << 20)) break;
+      ctx->tune_flagstat_grid = (int)value;
+      return BQSR_OK;
     default:
       return fail(BQSR_ERR_INVALID_ARG, "bqsr_context_tune: unknown knob");
   }
@@ -544,6 +552,7 @@ void bqsr_context_destroy(bqsr_context* c) {
   if (c->d_thr) (void)hipFree(c->d_thr);
   if (c->d_qbt) (void)hipFree(c->d_qbt);
   if (c->d_qbq) (void)hipFree(c->d_qbq);
+  if (c->d_flagstat) (void)hipFree(c->d_flagstat);
   for (int i = 0; i < 2; ++i) {
     if (c->stage[i]) (void)hipHostFree(c->stage[i]);
     if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]);
@@ -2155,6 +2164,7 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
 #include "mark_duplicates.cpp"
 #include "adam_out.hip"
 #include "sam_sort.hip"
+#include "flagstat.hip"
 #include "sam_batch.hip"
 #include "arrow_ingest.hip"
 #include "parquet_gzip.cpp"

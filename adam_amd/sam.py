@@ -8,7 +8,8 @@ columns as a RecordBatch (byte-identical to ``read_sam``);
 ``.mark_duplicates()`` runs MarkDuplicates (core/rdd/MarkDuplicates.scala:24-111)
 over the records and updates their duplicateRead bits; ``.rewrite(job)``
 puts a ResidentJob's recalibrated quality strings into the records' QUAL
-fields (the output path, core/rdd/AdamRDDFunctions.scala:37-56, as SAM text).
+fields (the output path, core/rdd/AdamRDDFunctions.scala:37-56, as SAM text);
+``.flagstat()`` counts the records as `adam flagstat` does (flagstat.py).
 """
 from __future__ import annotations
 
@@ -169,6 +170,15 @@ class SamText:
         the sorted text (``text()``, ``batch()``, the ADAM columns);
         MarkDuplicates' result travels with the records."""
         check(self.L.bqsr_sam_sort(self.ctx.handle, self.h, stream))
+
+    def flagstat(self, stream=None):
+        """`adam flagstat` over the records (bqsr_sam_flagstat,
+        core/rdd/FlagStat.scala:21-116): (failed, passed), each a
+        flagstat.FlagStatMetrics of the eighteen counts.  duplicateRead is
+        the flags column's bit: after ``mark_duplicates()`` the duplicate
+        counters follow its result."""
+        from .flagstat import sam_flagstat
+        return sam_flagstat(self, stream)
 
     def text(self) -> bytes:
         n = self.counts().text_bytes

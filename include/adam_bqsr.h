@@ -152,8 +152,19 @@ void bqsr_context_destroy(bqsr_context* ctx);
  *                        assembled and CRC-checked in LDS by a workgroup;
  *                        a file it cannot take -- a block that does not
  *                        inflate or check, a record chain it cannot prove --
- *                        falls back to 0), 0 on up to 16 host threads */
-enum { BQSR_TUNE_ORDER = 1, BQSR_TUNE_FRONTS = 2, BQSR_TUNE_KEYMAJOR = 3, BQSR_TUNE_FUSED_PREP = 4, BQSR_TUNE_BGZF = 5 };
+ *                        falls back to 0), 0 on up to 16 host threads
+ *   BQSR_TUNE_FLAGSTAT_GRID 0 auto (the flagstat kernels' grids follow the
+ *                        input and the CU count), g > 0: at most g workgroups,
+ *                        so that a small input runs every wavefront through
+ *                        many passes of its grid-stride loop (tests) */
+enum {
+  BQSR_TUNE_ORDER = 1,
+  BQSR_TUNE_FRONTS = 2,
+  BQSR_TUNE_KEYMAJOR = 3,
+  BQSR_TUNE_FUSED_PREP = 4,
+  BQSR_TUNE_BGZF = 5,
+  BQSR_TUNE_FLAGSTAT_GRID = 6
+};
 bqsr_status bqsr_context_tune(bqsr_context* ctx, int knob, int64_t value);
 
 /* ---- known sites (SnpTable.apply(File) + broadcast, SnpTable.scala:32-47,

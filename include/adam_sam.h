@@ -14,6 +14,8 @@
  *   dedup   : MarkDuplicates (adam-core/.../rdd/MarkDuplicates.scala:24-111),
  *             the `-mark_duplicate_reads` step `transform` runs before BQSR
  *             (adam-cli/.../cli/Transform.scala:73-76)
+ *   flagstat: adamFlagStat (adam-core/.../rdd/FlagStat.scala:21-116), the
+ *             counters `adam flagstat` prints, over a parse or Arrow buffers
  *
  * Same conventions as adam_bqsr.h (bqsr_status results, bqsr_last_error(),
  * library-owned handles with *_destroy, `stream` = hipStream_t as void*).
@@ -301,6 +303,90 @@ bqsr_status bqsr_sort_order(bqsr_context* ctx, int64_t n, const uint32_t* flags,
  * the text first).  Peak device memory: twice the text, and the new columns
  * beside the old ones while the records are parsed again. */
 bqsr_status bqsr_sam_sort(bqsr_context* ctx, bqsr_sam* s, void* stream);
+
+/* `adam flagstat` (adam-cli/.../cli/FlagStat.scala:43-109 over adamFlagStat,
+ * adam-core/.../rdd/FlagStat.scala:21-116): eighteen counters, kept once for
+ * the reads with failedVendorQualityChecks false (`passed`) and once for true
+ * (`failed`), in FlagStatMetrics' order (the BQSR_FS_* indices).  Per record,
+ * with the ADAMRecord fields as SAMRecordConverter.scala:26-108 sets them
+ * (every boolean false when FLAG is 0; the pair booleans only with 0x1;
+ * referenceId / mapq only when RNAME is an @SQ name, mapq only when MAPQ !=
+ * 255; mateReferenceId only when RNEXT resolves, "=" being RNAME's id):
+ *   dup = duplicateRead && primaryAlignment (primary) / && !primaryAlignment
+ *     (secondary); for either: dup; dup && readMapped && mateMapped; dup &&
+ *     readMapped && !mateMapped; dup && referenceId != mateReferenceId -- not
+ *     gated by readPaired.  The inequality is Scala's on boxed Integers: null
+ *     equals null, null differs from a value (an unpaired duplicate with RNAME
+ *     set and RNEXT "*" counts as cross chromosome).
+ *   mapped = readMapped; pairedInSequencing = readPaired; read1 / read2 /
+ *     properlyPaired = readPaired && firstOfPair / secondOfPair / properPair;
+ *     withSelfAndMateMapped / singleton = readPaired && readMapped &&
+ *     mateMapped / !mateMapped; withMateMappedToDiffChromosome = readPaired &&
+ *     readMapped && mateMapped && referenceId != mateReferenceId; ...MapQ5 =
+ *     that && mapq >= 5.  Where that holds and mapq is null the reference
+ *     unboxes null and throws: BQSR_ERR_NULL_FIELD naming the first such read
+ *     in input order (bqsr_last_error_read), `out` zeroed.
+ * `out` holds the counts of this call only; callers add results (the
+ * reference's `+`).  Device: one reduction kernel per front end
+ * (adam_amd/csrc/flagstat.hip), integer sums (independent of launch order). */
+enum {
+  BQSR_FS_TOTAL = 0,
+  BQSR_FS_DUP_PRIMARY = 1,   /* total, bothMapped, onlyReadMapped, crossChromosome */
+  BQSR_FS_DUP_SECONDARY = 5, /* the same four */
+  BQSR_FS_MAPPED = 9,
+  BQSR_FS_PAIRED_IN_SEQUENCING = 10,
+  BQSR_FS_READ1 = 11,
+  BQSR_FS_READ2 = 12,
+  BQSR_FS_PROPERLY_PAIRED = 13,
+  BQSR_FS_WITH_SELF_AND_MATE_MAPPED = 14,
+  BQSR_FS_SINGLETON = 15,
+  BQSR_FS_MATE_DIFF_CHROMOSOME = 16,
+  BQSR_FS_MATE_DIFF_CHROMOSOME_MAPQ5 = 17,
+  BQSR_FS_COUNTERS = 18
+};
+typedef struct bqsr_flagstat_metrics {
+  int64_t c[18];
+} bqsr_flagstat_metrics;
+typedef struct bqsr_flagstat {
+  bqsr_flagstat_metrics passed, failed;
+} bqsr_flagstat;
+/* over a parse (SAM or BAM): FLAG and referenceId from the parse's columns,
+ * MAPQ and RNEXT from each read's line; duplicateRead is the flags column's
+ * bit, so after bqsr_sam_mark_duplicates the counts follow its result, not
+ * the input's 0x400 */
+bqsr_status bqsr_sam_flagstat(bqsr_context* ctx, const bqsr_sam* s, void* stream, bqsr_flagstat* out);
+/* over Arrow buffers (ADAMRecord Parquet as Arrow decodes it): host pointers,
+ * uploaded as they are, one chunk per record batch (array offsets 0; chunk
+ * lengths need not be multiples of 64).  bools: readPaired, properPair,
+ * readMapped, mateMapped, firstOfPair, secondOfPair, primaryAlignment,
+ * duplicateRead, failedVendorQualityChecks as Arrow bitmaps (LSB first).  A
+ * NULL boolean column is all false, a NULL validity bitmap all valid, a NULL
+ * int column all null; a null boolean reads as false (as bqsr_arrow_chunk).
+ * Only ceil(n_reads / 8) bytes of a bitmap are read, and bits at and beyond
+ * n_reads are not counted.  NULL_FIELD's read index is global over the
+ * chunks. */
+typedef struct bqsr_flagstat_chunk {
+  int64_t n_reads;
+  const uint8_t* bools[9];
+  const uint8_t* bools_validity[9];
+  const int32_t* reference_id;
+  const uint8_t* reference_id_validity;
+  const int32_t* mate_reference_id;
+  const uint8_t* mate_reference_id_validity;
+  const int32_t* mapq;
+  const uint8_t* mapq_validity;
+} bqsr_flagstat_chunk;
+bqsr_status bqsr_flagstat_arrow(bqsr_context* ctx, const bqsr_flagstat_chunk* chunks, int32_t n_chunks, void* stream,
+                                bqsr_flagstat* out);
+/* MEASUREMENT ONLY, not part of the stable interface (it may change or go
+ * without notice; callers use bqsr_flagstat_arrow): the Arrow-form kernel
+ * alone, enqueued on `stream`, so that tools/bench_adam.py --flagstat can time
+ * it with device events.  Nothing is checked: every pointer of `chunk` must be
+ * device memory, the bitmaps padded to whole 64-bit words and 8-byte aligned;
+ * `counters` = 37 device words the sums are added into (passed[18],
+ * failed[18], then the first NULL_FIELD read, to be preset to all ones). */
+bqsr_status bqsr_flagstat_arrow_device(bqsr_context* ctx, const bqsr_flagstat_chunk* chunk, void* counters,
+                                       void* stream);
 
 /* MarkDuplicates across the partitions of one input (the reference's
  * groupBy spans every partition of the RDD, MarkDuplicates.scala:43-58).

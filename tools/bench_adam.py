@@ -9,6 +9,15 @@ by host threads -- and one JSON line printed with the phase split.
 
 --sort_reads adds `-sort_reads` (the "sort" phase in the stats' phase split)
 and prints record_text_bytes: the gather kernel (sort_gather) moves twice that.
+
+    python tools/bench_adam.py --flagstat [--reads 2000000] [--kernel-reads 64000000] [--reps 5]
+
+--flagstat measures `adam flagstat` (adam_amd/flagstat.py) instead: over the
+same synthetic reads as SAM, as BAM and as their ADAM Parquet, the parse and
+the flagstat call (host clock around calls that end in a synchronise; the
+best of --reps), Arrow's read, the upload-and-count call and the kernel alone
+(device events, buffers resident); then the Arrow-form kernel alone over
+--kernel-reads random reads on the device, as bytes/s.  One JSON line.
 """
 import argparse
 import json
@@ -63,8 +72,190 @@ def synthetic_sam(n_reads: int, read_len: int) -> bytes:
     return b"".join(parts)
 
 
+def _ms(f, reps):
+    """best wall time of f() in ms over reps calls (f ends in a device synchronise), and its last result"""
+    best, r = None, None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        r = f()
+        dt = (time.perf_counter() - t0) * 1e3
+        best = dt if best is None else min(best, dt)
+    return best, r
+
+
+def _kernel_ms(ctx, chunk, reps):
+    """flagstat_arrow alone over device buffers: device events around `reps`
+    launches (after a warm-up launch), ms per launch; the counters of one launch"""
+    import ctypes
+
+    import torch
+    from adam_amd import flagstat as FS
+    from adam_amd._capi import check
+    L = FS._lib()
+    counters = torch.zeros(37, dtype=torch.int64, device="cuda")
+    counters[36] = -1
+    sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    check(L.bqsr_flagstat_arrow_device(ctx.handle, ctypes.byref(chunk), counters.data_ptr(), sp))
+    torch.cuda.synchronize()
+    one = counters.cpu().numpy().copy()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        check(L.bqsr_flagstat_arrow_device(ctx.handle, ctypes.byref(chunk), counters.data_ptr(), sp))
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps, one
+
+
+def _device_chunk(table_or_n, seed=3):
+    """a bqsr_flagstat_chunk of device buffers (bitmaps as whole 64-bit
+    words): an Arrow table's columns, or n random reads (no read with a null
+    mapq).  Returns (chunk, keep, bytes the kernel reads)."""
+    import numpy as np
+    import torch
+    from adam_amd import flagstat as FS
+    keep = []
+    C = FS.FlagStatChunk()
+
+    def dev(t):
+        keep.append(t.cuda())
+        return keep[-1].data_ptr()
+    if isinstance(table_or_n, int):
+        n = table_or_n
+        W = (n + 63) // 64
+        g = torch.Generator(device="cuda").manual_seed(seed)
+
+        def rnd():  # 64 random bits a word
+            hi, lo = (torch.randint(0, 1 << 32, (W,), dtype=torch.int64, device="cuda", generator=g) for _ in "hl")
+            return (hi << 32) | lo
+        for k in range(9):
+            keep.append(rnd())
+            C.bools[k] = keep[-1].data_ptr()
+            keep.append(rnd() | rnd())
+            C.bools_validity[k] = keep[-1].data_ptr()
+        for attr, hi, valid in (("reference_id", 24, rnd() | rnd()), ("mate_reference_id", 24, rnd() | rnd()),
+                                ("mapq", 61, torch.full((W,), -1, dtype=torch.int64, device="cuda"))):
+            keep.append(torch.randint(0, hi, (n,), dtype=torch.int32, device="cuda", generator=g))
+            setattr(C, attr, keep[-1].data_ptr())
+            keep.append(valid)
+            setattr(C, attr + "_validity", keep[-1].data_ptr())
+        n_maps = 21
+    else:
+        import pyarrow as pa
+        t = table_or_n.combine_chunks()
+        n = t.num_rows
+        n_maps = 0
+
+        def words(buf):  # an Arrow bitmap as whole 64-bit words
+            a = np.zeros(((n + 63) // 64) * 8, np.uint8)
+            a[:(n + 7) // 8] = np.frombuffer(buf, np.uint8, (n + 7) // 8)
+            return torch.from_numpy(a.view(np.int64))
+        for k, name in enumerate(FS.BOOL_COLUMNS):
+            if name not in t.column_names:
+                continue
+            b = pa.concat_arrays([t.column(name).chunk(0)]).buffers() if n else [None, None]
+            C.bools[k] = dev(words(b[1]))
+            n_maps += 1
+            if b[0] is not None:
+                C.bools_validity[k] = dev(words(b[0]))
+                n_maps += 1
+        for name, attr in zip(FS.INT_COLUMNS, ("reference_id", "mate_reference_id", "mapq")):
+            if name not in t.column_names:
+                continue
+            arr = pa.concat_arrays([t.column(name).chunk(0).cast(pa.int32())])
+            b = arr.buffers()
+            setattr(C, attr, dev(torch.from_numpy(np.frombuffer(b[1], np.int32, n).copy())))
+            if b[0] is not None:
+                setattr(C, attr + "_validity", dev(words(b[0])))
+                n_maps += 1
+    C.n_reads = n
+    n_int = sum(1 for a in ("reference_id", "mate_reference_id", "mapq") if getattr(C, a))
+    return C, keep, n * 4 * n_int + ((n + 63) // 64) * 8 * n_maps
+
+
+def bench_flagstat(a):
+    """the --flagstat measurements (see the module doc)"""
+    import torch
+    from adam_amd import bqsr
+    from adam_amd import flagstat as FS
+    from adam_amd import parquet as P
+    from adam_amd import transform as T
+    from adam_amd.bam_writer import sam_to_bam_parallel
+    from adam_amd.sam import SamText
+    t0 = time.perf_counter()
+    sam = synthetic_sam(a.reads, a.len)
+    bam = sam_to_bam_parallel(sam, min(16, os.cpu_count() or 1))
+    log("generated %d bytes of SAM, %d of BAM in %.1f s" % (len(sam), len(bam), time.perf_counter() - t0))
+    torch.zeros(1, device="cuda")
+    ctx = bqsr.Context.get(0)
+    ctx.tune(bgzf=a.bgzf)
+    reps = max(2, a.reps)
+    res = {"metric": "adam flagstat: ms per phase at --reads (host clock, best of reps); Arrow-form kernel alone "
+                     "at --kernel-reads (device events)",
+           "reads": a.reads, "read_len": a.len, "reps": reps}
+    counts = {}
+    for name, data, is_bam in (("sam", sam, False), ("bam", bam, True)):
+        parse_ms, st = _ms(lambda: SamText(data, ctx, bam=is_bam), 1)  # warm-up (and the handle that is counted)
+        try:
+            _ms(st.flagstat, 1)
+            fs_ms, c = _ms(st.flagstat, reps)
+        finally:
+            st.close()
+
+        def parse():
+            SamText(data, ctx, bam=is_bam).close()
+        parse_ms, _ = _ms(parse, reps)
+        counts[name] = c
+        res[name] = {"input_bytes": len(data), "parse_ms": parse_ms, "flagstat_ms": fs_ms}
+        log("%s: parse %.2f ms, flagstat %.3f ms" % (name, parse_ms, fs_ms))
+    work = a.dir or tempfile.mkdtemp(prefix="bench_flagstat_")
+    os.makedirs(work, exist_ok=True)
+    try:
+        src, out = os.path.join(work, "in.sam"), os.path.join(work, "out.adam")
+        with open(src, "wb") as fh:
+            fh.write(sam)
+        del sam, bam
+        T.transform(src, out, compression=a.compression, part_reads=a.part_reads, overwrite=True)
+
+        def read():
+            t = P.read_table(out, columns=FS.PROJECTION)
+            return t, FS.table_chunks(t)
+        _ms(read, 1)
+        read_ms, (table, (chunks, keep)) = _ms(read, reps)
+        _ms(lambda: FS.arrow_flagstat(chunks, ctx), 1)
+        call_ms, c = _ms(lambda: FS.arrow_flagstat(chunks, ctx), reps)
+        counts["adam"] = c
+        C, dkeep, nbytes = _device_chunk(table)
+        k_ms, _ = _kernel_ms(ctx, C, 50)
+        res["adam"] = {"input_bytes": sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)),
+                       "compression": a.compression, "record_batches": len(chunks), "arrow_read_ms": read_ms,
+                       "upload_and_kernel_ms": call_ms, "kernel_ms": k_ms, "upload_ms": call_ms - k_ms,
+                       "kernel_bytes": nbytes}
+        log("adam: read %.2f ms, upload + kernel %.3f ms, kernel %.4f ms" % (read_ms, call_ms, k_ms))
+        del dkeep, keep
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    if not (counts["sam"] == counts["bam"] == counts["adam"]) or sum(x.total for x in counts["sam"]) != a.reads:
+        raise SystemExit("flagstat differs between SAM, BAM and ADAM: %r" % (counts,))
+    res["counts"] = {"failed": list(counts["sam"][0].counts()), "passed": list(counts["sam"][1].counts())}
+    # the Arrow-form kernel alone
+    C, dkeep, nbytes = _device_chunk(int(a.kernel_reads))
+    k_ms, one = _kernel_ms(ctx, C, 20)
+    if int(one[0]) + int(one[18]) != a.kernel_reads:
+        raise SystemExit("kernel counted %d reads of %d" % (int(one[0]) + int(one[18]), a.kernel_reads))
+    res["kernel"] = {"reads": int(a.kernel_reads), "bytes": nbytes, "ms": k_ms, "bytes_per_s": nbytes / (k_ms * 1e-3),
+                     "copy_rate_bytes_per_s": 6.29e12, "share_of_copy_rate": nbytes / (k_ms * 1e-3) / 6.29e12,
+                     "launches_timed": 20}
+    log("kernel: %d reads, %d bytes, %.4f ms" % (a.kernel_reads, nbytes, k_ms))
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--flagstat", action="store_true", help="measure adam flagstat instead of the transform")
+    ap.add_argument("--kernel-reads", type=int, default=64_000_000,
+                    help="--flagstat: random reads for the Arrow-form kernel alone")
     ap.add_argument("--reads", type=int, default=2_000_000)
     ap.add_argument("--len", type=int, default=100)
     ap.add_argument("--bam", action="store_true")
@@ -77,6 +268,8 @@ def main():
     ap.add_argument("--reps", type=int, default=1)
     ap.add_argument("--dir", default=None, help="scratch directory (default: a temporary one)")
     a = ap.parse_args()
+    if a.flagstat:
+        return bench_flagstat(a)
     t0 = time.perf_counter()
     data = synthetic_sam(a.reads, a.len)
     if a.bam:
