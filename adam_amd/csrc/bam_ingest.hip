@@ -514,17 +514,15 @@ struct RecScan {
   bqsr_status bad() const { return fail(BQSR_ERR_SAM_PARSE, "BAM: bad record size at byte " + std::to_string(p)); }
 };
 
-// The device form (bgzf_inflate.hip): the compressed file uploaded once, a
-// thread per BGZF block inflating it into d_raw, the header read back, the
-// records' offsets found and checked on the device (*d_rec, n + 1 entries,
-// from BH.body).  ok = false when it declines -- a block that does not
-// inflate or fails its CRC32, a chain the check rejects, a header it cannot
-// read -- and the caller runs the host form, which reports the file's error
-// as before.
-bqsr_status bam_inflate_device(bqsr_context* ctx, const uint8_t* data, int64_t n, const std::vector<BgzfBlk>& blks,
-                               int64_t m, uint8_t* d_raw, hipStream_t s, std::vector<void*>& tmp, BamHead& BH,
-                               SamHeader& H, std::string& hdr, uint64_t** d_rec, int64_t& nr, bool& ok) {
-  ok = false;
+// The device inflate (bgzf_inflate.hip) of a file's BGZF blocks into d_raw:
+// the compressed file uploaded once, then pass 1 (a thread per block, its
+// symbols) and pass 2 (a workgroup per block, its bytes and CRC32) over runs
+// of whole blocks.  *d_blk: the blocks on the device; hs: every block's kInf*
+// status (the bytes of a block that is not kInfOk are not written).  Shared by
+// bqsr_bam_parse's device form and bqsr_bgzf_inflate.
+bqsr_status bgzf_inflate_runs(bqsr_context* ctx, const uint8_t* data, int64_t n, const std::vector<BgzfBlk>& blks,
+                              uint8_t* d_raw, hipStream_t s, std::vector<void*>& tmp, bgzfk::Blk** d_blk_out,
+                              std::vector<int32_t>& hs) {
   const int64_t nb = (int64_t)blks.size();
   std::vector<bgzfk::Blk> hb((size_t)nb);
   for (int64_t i = 0; i < nb; ++i) {
@@ -538,6 +536,7 @@ bqsr_status bam_inflate_device(bqsr_context* ctx, const uint8_t* data, int64_t n
   if ((st = sam_alloc(tmp, &d_comp, (size_t)n + 256)) != BQSR_OK || (st = sam_upload(tmp, &d_blk, hb, s)) != BQSR_OK ||
       (st = sam_alloc(tmp, &d_status, (size_t)std::max<int64_t>(1, nb))) != BQSR_OK)
     return st;
+  *d_blk_out = d_blk;
   if ((st = upload_staged(ctx, d_comp, data, (size_t)n, s)) != BQSR_OK) return st;
   {  // symbols, then the bytes assembled a block a workgroup in LDS (+ CRC)
     // in runs of whole blocks of at most kTokRun output bytes (1 GiB;
@@ -575,9 +574,27 @@ bqsr_status bam_inflate_device(bqsr_context* ctx, const uint8_t* data, int64_t n
       HIP_TRY(hipGetLastError());
     }
   }
-  std::vector<int32_t> hs((size_t)std::max<int64_t>(1, nb), 0);
+  hs.assign((size_t)std::max<int64_t>(1, nb), 0);
   if (nb > 0) HIP_TRY(hipMemcpyAsync(hs.data(), d_status, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return BQSR_OK;
+}
+
+// The device form (bgzf_inflate.hip): the file's blocks inflated into d_raw
+// (bgzf_inflate_runs), the header read back, the records' offsets found and
+// checked on the device (*d_rec, n + 1 entries, from BH.body).  ok = false
+// when it declines -- a block that does not inflate or fails its CRC32, a
+// chain the check rejects, a header it cannot read -- and the caller runs
+// the host form, which reports the file's error as before.
+bqsr_status bam_inflate_device(bqsr_context* ctx, const uint8_t* data, int64_t n, const std::vector<BgzfBlk>& blks,
+                               int64_t m, uint8_t* d_raw, hipStream_t s, std::vector<void*>& tmp, BamHead& BH,
+                               SamHeader& H, std::string& hdr, uint64_t** d_rec, int64_t& nr, bool& ok) {
+  ok = false;
+  const int64_t nb = (int64_t)blks.size();
+  bqsr_status st;
+  bgzfk::Blk* d_blk;
+  std::vector<int32_t> hs;
+  if ((st = bgzf_inflate_runs(ctx, data, n, blks, d_raw, s, tmp, &d_blk, hs)) != BQSR_OK) return st;
   for (int64_t i = 0; i < nb; ++i)
     if (hs[(size_t)i] != bgzfk::kInfOk) return BQSR_OK;  // (the host form reports the block)
   // the header, read back until it parses
@@ -767,6 +784,7 @@ bqsr_status bqsr_bam_parse(bqsr_context* ctx, const uint8_t* data, int64_t n, vo
   }
   const double t_lines = now_s();
   st = sam_parse_device(ctx, H, hdr.data(), d_text, n_text, s, true, out);  // (owns d_text from here)
+  if (st == BQSR_OK) (*out)->bam_form = dev ? 2 : 1;
   if (bam_timing())
     fprintf(stderr,
             "[bam_parse] %lld reads, %.2f GB inflated (%s): blocks %.3f, alloc %.3f, runs %.3f (slot waits %.3f, "
@@ -774,4 +792,41 @@ bqsr_status bqsr_bam_parse(bqsr_context* ctx, const uint8_t* data, int64_t n, vo
             (long long)nr, m / 1e9, dev ? "device" : Deflate::get().ok() ? "libdeflate" : "zlib", t_blocks - t_start, t_alloc - t_blocks, t_inflated - t_alloc, IT.wait, IT.inflate,
             IT.host, IT.read, IT.drain, t_lines - t_inflated, now_s() - t_lines);
   return st;
+}
+
+int32_t bqsr_sam_bam_form(const bqsr_sam* sm) { return sm ? sm->bam_form : 0; }
+
+bqsr_status bqsr_bgzf_inflate(bqsr_context* ctx, const uint8_t* data, int64_t n, void* stream, uint8_t* out,
+                              int64_t out_cap, int64_t* out_len, int32_t* block_status, int64_t status_cap,
+                              int64_t* n_blocks) {
+  if (!ctx || !out_len || !n_blocks || n < 0 || (n > 0 && !data))
+    return fail(BQSR_ERR_INVALID_ARG, "bqsr_bgzf_inflate: bad arguments");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = S(stream);
+  std::vector<BgzfBlk> blks;
+  int64_t m = 0;
+  bqsr_status st = bgzf_blocks(data, n, blks, m);
+  if (st != BQSR_OK) return st;
+  const int64_t nb = (int64_t)blks.size();
+  *out_len = m;
+  *n_blocks = nb;
+  if (!out) return ok();  // (the size query)
+  if (out_cap < m || status_cap < nb || (nb > 0 && !block_status))
+    return fail(BQSR_ERR_INVALID_ARG, "bqsr_bgzf_inflate: out or block_status too small");
+  std::vector<void*> tmp;
+  struct Free {
+    std::vector<void*>& v;
+    ~Free() {
+      for (void* q : v) (void)hipFree(q);
+    }
+  } free_tmp{tmp};
+  uint8_t* d_raw;
+  if ((st = sam_alloc(tmp, &d_raw, (size_t)m + 64)) != BQSR_OK) return st;
+  HIP_TRY(hipMemsetAsync(d_raw, 0, (size_t)m + 64, s));
+  bgzfk::Blk* d_blk;
+  std::vector<int32_t> hs;
+  if ((st = bgzf_inflate_runs(ctx, data, n, blks, d_raw, s, tmp, &d_blk, hs)) != BQSR_OK) return st;
+  if (m > 0) HIP_TRY(hipMemcpy(out, d_raw, (size_t)m, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < nb; ++i) block_status[i] = hs[(size_t)i];
+  return ok();
 }

@@ -57,7 +57,8 @@ constexpr int kInfThreadsDeep = 12;
 constexpr int kLitRoot = 9;      // the decode tables' root index bits
 constexpr int kLitCap = 512;     // and their second-level entries (zlib's bound for 286 codes, root 9: 852 in all)
 constexpr int kDistRoot = 8;
-constexpr int kDistCap = 256;    // (a code needing more fails the block over to the host form)
+constexpr int kDistCap = 256;    // (no complete code of <= 30 symbols needs more than 144, tools/huff_table_bound.py;
+                                 // a code that did would fail the block over to the host form)
 enum : int32_t { kInfOk = 0, kInfBadCode = 1, kInfOverrun = 2, kInfShort = 3, kInfCrc = 4, kInfBadBlock = 5 };
 
 // canonical Huffman code of a DEFLATE block (RFC 1951 §3.2.2): symbols by
@@ -378,12 +379,13 @@ __global__ void __launch_bounds__(kThreads) bgzf_tokens_kernel(const uint8_t* co
       if (st != kInfOk) break;
       if (L.len[256] == 0) { st = kInfBadBlock; break; }  // no end-of-block code
       const int el = huff_build(L.lit, L.offs, L.len, nlen);
-      if (el < 0 || (el > 0 && nlen - L.lit.count[0] != 1)) { st = kInfBadBlock; break; }
+      // (an incomplete code only as zlib and libdeflate take it: a single code of length 1)
+      if (el < 0 || (el > 0 && (nlen - L.lit.count[0] != 1 || L.lit.count[1] != 1))) { st = kInfBadBlock; break; }
       if (!table_build<kLitRoot, kLitCap>(L.tlit, L.lit)) { st = kInfBadBlock; break; }
       // (the distance lengths start at len[nlen]: copied down for the build)
       for (int i = 0; i < ndist; ++i) L.len[i] = L.len[nlen + i];
       const int ed = huff_build(L.dist, L.offs, L.len, ndist);
-      if (ed < 0 || (ed > 0 && ndist - L.dist.count[0] != 1)) { st = kInfBadBlock; break; }
+      if (ed < 0 || (ed > 0 && (ndist - L.dist.count[0] != 1 || L.dist.count[1] != 1))) { st = kInfBadBlock; break; }
       if (!table_build<kDistRoot, kDistCap>(L.tdist, L.dist)) { st = kInfBadBlock; break; }
     }
     // the block's codes

@@ -892,6 +892,7 @@ struct bqsr_sam {
   bool dup_marked = false;  // bqsr_sam_mark_duplicates ran: FLAG 0x400 rewritten on output
   bool flag_text_current = false;  // the text's FLAG fields carry MarkDuplicates' bits (rewritten since it ran)
   bool from_bam = false;    // bqsr_bam_parse: d_text holds the records converted to SAM text on the device
+  int32_t bam_form = 0;     // bqsr_sam_bam_form: 1 the BGZF blocks inflated by host threads, 2 on the device
   samk::NameTable sq_tab{}, rg_tab{};  // @SQ / @RG name tables on the device (ADAM columns)
   std::string header_text;  // the header lines (host copy)
   void* adam = nullptr;     // ADAM column buffers (adam_out.hip), freed with the handle

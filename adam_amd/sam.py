@@ -70,6 +70,9 @@ def _lib():
             "bqsr_dup_set_destroy": (None, [vp]),
             "bqsr_sort_order": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, vp]),
             "bqsr_sam_sort": (ctypes.c_int, [vp, vp, vp]),
+            "bqsr_sam_bam_form": (i32, [vp]),
+            "bqsr_bgzf_inflate": (ctypes.c_int, [vp, ctypes.c_char_p, i64, vp, vp, i64, ctypes.POINTER(i64), vp, i64,
+                                                 ctypes.POINTER(i64)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -102,6 +105,12 @@ class SamText:
         with open(path, "rb") as fh:
             data = fh.read()
         return cls(data, ctx, bam=data[:4] == b"\x1f\x8b\x08\x04")
+
+    @property
+    def bam_form(self) -> int:
+        """Which BGZF inflate served the parse (bqsr_sam_bam_form): 0 not a
+        BAM, 1 the host form, 2 the device form."""
+        return int(self.L.bqsr_sam_bam_form(self.h))
 
     def counts(self) -> SamCounts:
         c = SamCounts()
@@ -196,6 +205,23 @@ class SamText:
             self.close()
         except Exception:
             pass
+
+
+def bgzf_inflate(data: bytes, ctx: Optional[bqsr.Context] = None, stream=None):
+    """The device BGZF inflate alone (bqsr_bgzf_inflate): (out, status) --
+    the inflated stream as a uint8 array, member i's bytes at the sum of the
+    ISIZE fields before it, and the members' status (int32; 0: inflated and
+    CRC32 checked, non-zero: declined, its bytes unspecified)."""
+    L = _lib()
+    ctx = ctx or bqsr.Context.get(0)
+    n, nb = ctypes.c_int64(), ctypes.c_int64()
+    check(L.bqsr_bgzf_inflate(ctx.handle, data, len(data), stream, None, 0, ctypes.byref(n), None, 0,
+                              ctypes.byref(nb)))
+    out = np.zeros(max(1, n.value), np.uint8)
+    status = np.full(max(1, nb.value), -1, np.int32)
+    check(L.bqsr_bgzf_inflate(ctx.handle, data, len(data), stream, out.ctypes.data, n.value, ctypes.byref(n),
+                              status.ctypes.data, nb.value, ctypes.byref(nb)))
+    return out[:n.value], status[:nb.value]
 
 
 class DupSet:

@@ -54,6 +54,22 @@ void bqsr_sam_destroy(bqsr_sam* s);
  * on a SAM parse -- rewrite, text download, MarkDuplicates, ADAM columns --
  * serves BAM input too. */
 bqsr_status bqsr_bam_parse(bqsr_context* ctx, const uint8_t* bam, int64_t n_bytes, void* stream, bqsr_sam** out);
+/* Which form of the BGZF inflate served a parse: 0 not a BAM parse, 1 the
+ * host form (BQSR_TUNE_BGZF 0, or a file the device form declined), 2 the
+ * device form. */
+int32_t bqsr_sam_bam_form(const bqsr_sam* s);
+/* The device form's inflate alone, with bqsr_bam_parse's code: the BGZF
+ * members of `bgzf` (host memory) located, uploaded and inflated by the two
+ * device passes; no BAM header or record work.  out (host, out_cap bytes)
+ * receives the inflated stream, member i's bytes at the sum of the ISIZE
+ * fields before it; block_status[i] (status_cap entries) is 0 for a member
+ * that inflated to ISIZE bytes with its CRC32, non-zero for one the device
+ * declines (its bytes in `out` are unspecified).  *out_len = the stream's
+ * bytes, *n_blocks = the members; out == NULL returns only these two.
+ * BQSR_ERR_SAM_PARSE for bytes that are no chain of BGZF members. */
+bqsr_status bqsr_bgzf_inflate(bqsr_context* ctx, const uint8_t* bgzf, int64_t n_bytes, void* stream, uint8_t* out,
+                              int64_t out_cap, int64_t* out_len, int32_t* block_status, int64_t status_cap,
+                              int64_t* n_blocks);
 
 typedef struct bqsr_sam_counts {
   int64_t n_reads;     /* records (empty lines skipped)   */

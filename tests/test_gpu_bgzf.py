@@ -6,7 +6,10 @@ and run-length strategies -- and with members of 100 B to 64 KiB (records
 spanning several members, members without a record start) parses to the
 same columns.  The records' offsets are found on the device and checked as a
 chain; a damaged file takes the host form and fails as before
-(test_gpu_sam.py::test_bam_ingest_rejects_damaged_bgzf)."""
+(test_gpu_sam.py::test_bam_ingest_rejects_damaged_bgzf).  Every parse here
+also says which form served it (SamText.bam_form): a device form that
+declined would otherwise compare the host form with itself.  The decoder's
+bytes are held to zlib's in test_gpu_bgzf_bytes.py."""
 import os
 import struct
 import zlib
@@ -50,6 +53,7 @@ def _columns(data: bytes, bgzf: int):
     with bqsr.Context.get(0).tuned(bgzf=bgzf):
         s = SamText(data, bam=True)
         try:
+            assert s.bam_form == (2 if bgzf else 1)
             return s.batch()
         finally:
             s.close()
@@ -109,3 +113,79 @@ def test_device_inflate_many_blocks(raw_bam):
     data = _reblock(raw_bam, 250, 6, zlib.Z_DEFAULT_STRATEGY)
     assert len(raw_bam) // 250 > 256 * 32
     assert_same_columns(_columns(data, 1), _columns(data, 0))
+
+
+def _member(raw: bytes, chunk: bytes) -> bytes:
+    bsize = 18 + len(raw) + 8 - 1
+    return (struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, bsize) + raw +
+            struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
+
+
+def _reblock_at(raw: bytes, cuts) -> bytes:
+    cuts = sorted(set([0, len(raw)] + [c for c in cuts if 0 < c < len(raw)]))
+    out = []
+    for a, b in zip(cuts, cuts[1:]):
+        c = zlib.compressobj(6, zlib.DEFLATED, -15)
+        out.append(_member(c.compress(raw[a:b]) + c.flush(), raw[a:b]))
+    return b"".join(out + [EOF_BLOCK])
+
+
+def _sam_columns(text: bytes):
+    s = SamText(text)
+    try:
+        assert s.bam_form == 0
+        return s.batch()
+    finally:
+        s.close()
+
+
+def test_device_inflate_thirty_distance_codes():
+    # a member written with all 30 distance codes declared, 9- to 15-bit ones in three root prefixes
+    # (_bgzf_cases.DIST30): within the decoder's second-level table, as every complete distance code is, so
+    # the device form serves the file
+    import _bgzf_cases as C
+    text = _dup_sam(300, 11, 30000)
+    raw = _inflate(sam_to_bam(text))
+    chunk = raw[2000:5000]
+    toks = C.lz_tokens(chunk)
+    assert any(not isinstance(t, int) for t in toks)
+    m = C.dyn("dist30", toks, C.lens_for(toks, nlen=286)[0], C.DIST30)
+    assert zlib.decompress(m.raw, -15) == chunk == m.data
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    head = c.compress(raw[:2000]) + c.flush()
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    tail = c.compress(raw[5000:]) + c.flush()
+    data = _member(head, raw[:2000]) + _member(m.raw, chunk) + _member(tail, raw[5000:]) + EOF_BLOCK
+    assert_same_columns(_columns(data, 1), _sam_columns(text))
+
+
+def test_device_declines_fake_records_in_qual():
+    # one read's QUAL bytes spell two consecutive plausible records (block_size 40, ref 0, pos 0, l_name 4, a
+    # NUL-terminated name, every other field 0, 4 spare bytes; all bytes legal qualities), and a member starts
+    # exactly at the first: that member's guess is the fake record, whose walk joins the true chain two records
+    # on, but the member before it lands on the true next record, not on the guess -- the chain check rejects,
+    # the host form serves the file, and the columns are the SAM text's.  (An accepted chain is the true one.)
+    fake = struct.pack("<iiiBBHHHiiii", 40, 0, 0, 4, 0, 0, 0, 0, 0, 0, 0, 0) + b"AAA\0" + b"\0\0\0\0"
+    assert len(fake) == 44 and max(fake) <= 93
+    lines = _dup_sam(300, 12, 30000).split(b"\n")
+    k = next(i for i, l in enumerate(lines) if l and not l.startswith(b"@")) + 100
+    f = lines[k].split(b"\t")[:11]
+    f[5], f[9], f[10] = b"88M", b"ACGT" * 22, bytes(b + 33 for b in fake + fake)
+    lines[k] = b"\t".join(f)
+    text = b"\n".join(lines)
+    raw = _inflate(sam_to_bam(text))
+    at = raw.index(fake + fake)
+    assert raw.count(fake + fake) == 1
+    want = _sam_columns(text)
+    every = list(range(3000, len(raw), 3000))
+    data = _reblock_at(raw, [c for c in every if not at - 200 < c < at + 200] + [at])
+    with bqsr.Context.get(0).tuned(bgzf=1):
+        s = SamText(data, bam=True)
+        try:
+            assert s.bam_form == 1
+            assert_same_columns(s.batch(), want)
+        finally:
+            s.close()
+    # a member starting at the true record after them instead: the device form serves the same file
+    data = _reblock_at(raw, [c for c in every if not at - 200 < c < at + 200] + [at + 88])
+    assert_same_columns(_columns(data, 1), want)
