@@ -18,9 +18,9 @@ BQSR_OK = 0
 STAGE_RESET, STAGE_KERNEL, STAGE_FOLD, STAGE_PREP, STAGE_LUT, STAGE_NO_LUT = 1, 2, 4, 8, 16, 32
 STATUS_NAMES = ["OK", "NULL_RG", "MD_PARSE", "CIGAR_SHORT", "BAD_REVCOMP_BASE", "EMPTY_TABLE", "MISSING_KEY",
                 "QUAL_RANGE", "NULL_FIELD", "SEQ_SHORT", "CIGAR_INVALID", "INVALID_ARG", "DEVICE", "UNSUPPORTED",
-                "SAM_PARSE"]
+                "SAM_PARSE", "PILEUP"]
 (NULL_RG, MD_PARSE, CIGAR_SHORT, BAD_REVCOMP_BASE, EMPTY_TABLE, MISSING_KEY, QUAL_RANGE, NULL_FIELD, SEQ_SHORT,
- CIGAR_INVALID, INVALID_ARG, DEVICE, UNSUPPORTED, SAM_PARSE) = range(1, 15)
+ CIGAR_INVALID, INVALID_ARG, DEVICE, UNSUPPORTED, SAM_PARSE, PILEUP) = range(1, 16)
 
 # every symbol include/adam_bqsr.h declares
 EXPORTS = [
@@ -38,6 +38,8 @@ EXPORTS = [
     "bqsr_sort_order", "bqsr_sam_sort",  # include/adam_sam.h
     "bqsr_sam_flagstat", "bqsr_flagstat_arrow", "bqsr_flagstat_arrow_device",
     "bqsr_bgzf_inflate", "bqsr_sam_bam_form",
+    "bqsr_sam_pileup_prepare", "bqsr_sam_pileup_columns", "bqsr_arrow_pileup_prepare", "bqsr_arrow_pileup_columns",
+    "bqsr_pileup_kernel_times",
 ]
 
 

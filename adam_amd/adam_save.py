@@ -65,6 +65,24 @@ HUFFMAN_COLS = ("sequence", "qual")
 STATS_COLS = [n for n, k in ADAM_FIELDS if n not in PER_READ_STRINGS]
 
 
+# adam.avdl:70-88: the Base enum's symbols, in order (parquet-avro stores an enum as its name)
+BASES = ("A", "C", "T", "G", "U", "N", "X", "K", "M", "R", "Y", "S", "W", "B", "V", "H", "D")
+# ADAMPileup, adam.avdl:99-128, in order
+PILEUP_FIELDS: List[Tuple[str, str]] = [
+    ("referenceName", "string"), ("referenceId", "int32"), ("position", "int64"), ("rangeOffset", "int32"),
+    ("rangeLength", "int32"), ("referenceBase", "string"), ("readBase", "string"), ("sangerQuality", "int32"),
+    ("mapQuality", "int32"), ("numSoftClipped", "int32"), ("numReverseStrand", "int32"),
+    ("countAtPosition", "int32"), ("readName", "string"), ("readStart", "int64"), ("readEnd", "int64"),
+    ("recordGroupSequencingCenter", "string"), ("recordGroupDescription", "string"),
+    ("recordGroupRunDateEpoch", "int64"), ("recordGroupFlowOrder", "string"), ("recordGroupKeySequence", "string"),
+    ("recordGroupLibrary", "string"), ("recordGroupPredictedMedianInsertSize", "int32"),
+    ("recordGroupPlatform", "string"), ("recordGroupPlatformUnit", "string"), ("recordGroupSample", "string"),
+]
+# reads2ref part files: dictionary pages for everything but the positions
+PILEUP_DICT_COLS = [n for n, k in PILEUP_FIELDS if n != "position"]
+PILEUP_STATS_COLS = [n for n, k in PILEUP_FIELDS]
+
+
 class AdamSizes(ctypes.Structure):
     _fields_ = [("n_reads", ctypes.c_int64), ("str_bytes", ctypes.c_int64 * 6), ("bitmap_words", ctypes.c_int64)]
 
@@ -199,6 +217,13 @@ def schema():
     return pa.schema([pa.field(n, t[k], nullable=True) for n, k in ADAM_FIELDS])
 
 
+def pileup_schema():
+    """ADAMPileup (adam.avdl:99-128): 25 optional fields; a Base is its symbol's name"""
+    import pyarrow as pa
+    t = {"string": pa.string(), "int32": pa.int32(), "int64": pa.int64()}
+    return pa.schema([pa.field(n, t[k], nullable=True) for n, k in PILEUP_FIELDS])
+
+
 def _pinned(nbytes: int) -> np.ndarray:
     """a pinned host block (numpy view of a torch pinned tensor; the view
     keeps the tensor alive)"""
@@ -325,7 +350,16 @@ class AdamWriter:
     as the tables arrive (``OUT.partial`` renamed to ``OUT`` on ``close``)."""
 
     def __init__(self, path: str, compression: str = "gzip", threads: Optional[int] = None,
-                 overwrite: bool = False, native_gzip: bool = True):
+                 overwrite: bool = False, native_gzip: bool = True, dict_cols=None, stats_cols=None,
+                 huffman_cols=None, max_pending: int = 64):
+        """dict_cols / stats_cols / huffman_cols: the columns written with
+        dictionary pages / statistics / as literal-only Huffman blocks
+        (default: ADAMRecord's); max_pending: the tables held while the pool
+        writes them."""
+        self.dict_cols = DICT_COLS if dict_cols is None else list(dict_cols)
+        self.stats_cols = STATS_COLS if stats_cols is None else list(stats_cols)
+        self.huffman_cols = HUFFMAN_COLS if huffman_cols is None else tuple(huffman_cols)
+        self.max_pending = max(1, int(max_pending))
         self.path = path
         self.tmp = path + ".partial"
         # adamSave goes through Hadoop's FileOutputFormat, which refuses an
@@ -363,18 +397,18 @@ class AdamWriter:
         path = os.path.join(self.tmp, name)
         if self.compression != "gzip" or not self.native_gzip:
             pq.write_table(table, path, compression=self.compression, compression_level=self.level,
-                           use_dictionary=DICT_COLS, write_statistics=STATS_COLS, store_schema=False)
+                           use_dictionary=self.dict_cols, write_statistics=self.stats_cols, store_schema=False)
             return
         # gzip: Arrow encodes the pages uncompressed in memory, the library
         # writes them gzip-compressed (bqsr_parquet_gzip: quals and bases as
         # literal-only Huffman blocks, the rest at zlib's level 6)
         buf = pa.BufferOutputStream()
-        pq.write_table(table, buf, compression="none", use_dictionary=DICT_COLS, write_statistics=STATS_COLS,
-                       store_schema=False)
+        pq.write_table(table, buf, compression="none", use_dictionary=self.dict_cols,
+                       write_statistics=self.stats_cols, store_schema=False)
         data = buf.getvalue()
         n = ctypes.c_int64()
         check(_lib().bqsr_parquet_gzip(ctypes.c_void_p(data.address), data.size, path.encode(), self.level,
-                                       b",".join(c.encode() for c in HUFFMAN_COLS), self.gzip_threads,
+                                       b",".join(c.encode() for c in self.huffman_cols), self.gzip_threads,
                                        ctypes.byref(n)))
 
     def add(self, table):
@@ -382,7 +416,7 @@ class AdamWriter:
         self.parts += 1
         self.rows += table.num_rows
         self.futures.append(self.pool.submit(self._write, table, name))
-        if len(self.futures) > 64:  # bound the tables held in memory
+        while len(self.futures) > self.max_pending:  # bound the tables held in memory
             self.futures.pop(0).result()
 
     def emit(self, sam, part_reads: int = 1 << 20, stream=None):

@@ -308,6 +308,7 @@ struct bqsr_arrow {
   int32_t* q_off = nullptr;
   uint8_t* q_valid = nullptr;
   int64_t q_bytes = -1;
+  std::shared_ptr<void> pileup;  // pileup scratch and columns (pileup.hip)
   std::vector<void*> allocs;
   ~bqsr_arrow() {
     for (void* p : allocs) (void)hipFree(p);

@@ -61,7 +61,8 @@ hipStream_t S(void* s) { return s ? (hipStream_t)s : hipStreamPerThread; }
 
 const char* kStatusNames[] = {"OK",          "NULL_RG",      "MD_PARSE",       "CIGAR_SHORT", "BAD_REVCOMP_BASE",
                               "EMPTY_TABLE", "MISSING_KEY",  "QUAL_RANGE",     "NULL_FIELD",  "SEQ_SHORT",
-                              "CIGAR_INVALID", "INVALID_ARG", "DEVICE",        "UNSUPPORTED", "SAM_PARSE"};
+                              "CIGAR_INVALID", "INVALID_ARG", "DEVICE",        "UNSUPPORTED", "SAM_PARSE",
+                              "PILEUP"};
 
 // map a device error key to (status, read) and record the message
 bqsr_status from_err_key(unsigned long long k, int64_t read_base) {
@@ -257,6 +258,7 @@ struct bqsr_context {
   int tune_keymajor = 0;
   int tune_bgzf = 1;  // BAM ingest: BGZF inflated on the device (BQSR_TUNE_BGZF), 0 by host threads
   int tune_flagstat_grid = 0;  // flagstat kernels: at most this many workgroups (BQSR_TUNE_FLAGSTAT_GRID), 0 auto
+  int tune_pileup_grid = 0;    // pileup kernels: at most this many workgroups (BQSR_TUNE_PILEUP_GRID), 0 auto
   // flagstat's counter block (flagstat.hip: 37 words, allocated on first use; one call at a time)
   std::mutex flagstat_mu;
   unsigned long long* d_flagstat = nullptr;
@@ -478,7 +480,7 @@ int bqsr_abi_version(void) { return BQSR_ABI_VERSION; }
 const char* bqsr_last_error(void) { return g_err.c_str(); }
 int64_t bqsr_last_error_read(void) { return g_err_read; }
 const char* bqsr_status_name(bqsr_status s) {
-  if ((int)s < 0 || (int)s > 14) return "UNKNOWN";
+  if ((int)s < 0 || (int)s > 15) return "UNKNOWN";
   return kStatusNames[(int)s];
 }
 
@@ -507,6 +509,10 @@ bqsr_status bqsr_context_tune(bqsr_context* ctx, int knob, int64_t value) {
     case BQSR_TUNE_FLAGSTAT_GRID:
       if (value < 0 || value > (1 << 20)) break;
       ctx->tune_flagstat_grid = (int)value;
+      return BQSR_OK;
+    case BQSR_TUNE_PILEUP_GRID:
+      if (value < 0 || value > (1 << 20)) break;
+      ctx->tune_pileup_grid = (int)value;
       return BQSR_OK;
     default:
       return fail(BQSR_ERR_INVALID_ARG, "bqsr_context_tune: unknown knob");
@@ -2167,6 +2173,7 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
 #include "flagstat.hip"
 #include "sam_batch.hip"
 #include "arrow_ingest.hip"
+#include "pileup.hip"
 #include "parquet_gzip.cpp"
 
 // ---- streamed outputs: compaction (uses the SAM code's scans) ----

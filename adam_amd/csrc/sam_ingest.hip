@@ -896,6 +896,7 @@ struct bqsr_sam {
   samk::NameTable sq_tab{}, rg_tab{};  // @SQ / @RG name tables on the device (ADAM columns)
   std::string header_text;  // the header lines (host copy)
   void* adam = nullptr;     // ADAM column buffers (adam_out.hip), freed with the handle
+  std::shared_ptr<void> pileup;  // pileup scratch and columns (pileup.hip)
   std::vector<void*> allocs;
   ~bqsr_sam();
 };

@@ -314,6 +314,7 @@ class ArrowReads:
         check(self.L.bqsr_arrow_load(self.ctx.handle, arr, len(chunks), stream, ctypes.byref(self.h)))
         del keep
         self.n_reads = n
+        self.table = table  # (pileups: mapq and the read-level columns come from it)
 
     def device_batch(self, contigs: Optional[Sequence[str]] = None, stream=None) -> ctypes.c_void_p:
         """A BQSR batch of the reads (the caller owns it)."""
@@ -365,6 +366,13 @@ class ArrowReads:
         valid = np.empty(max(1, (n + 7) // 8), np.uint8)
         check(self.L.bqsr_arrow_qual_column(self.h, off.ctypes.data, data.ctypes.data, valid.ctypes.data))
         return pa.StringArray.from_buffers(n, pa.py_buffer(off), pa.py_buffer(data[:nb.value]), pa.py_buffer(valid))
+
+    def pileups(self, r0: int = 0, n: Optional[int] = None, stream=None):
+        """`adam reads2ref` over reads [r0, r0 + n) (bqsr_arrow_pileup_*): their
+        ADAMPileup records as a pyarrow table, as ``SamText.pileups``.  The
+        table is taken as loaded: reads2ref.locus_filter is the caller's."""
+        from .reads2ref import arrow_pileups
+        return arrow_pileups(self, r0, n, stream)
 
     def close(self):
         if self.h:

@@ -9,7 +9,8 @@ columns as a RecordBatch (byte-identical to ``read_sam``);
 over the records and updates their duplicateRead bits; ``.rewrite(job)``
 puts a ResidentJob's recalibrated quality strings into the records' QUAL
 fields (the output path, core/rdd/AdamRDDFunctions.scala:37-56, as SAM text);
-``.flagstat()`` counts the records as `adam flagstat` does (flagstat.py).
+``.flagstat()`` counts the records as `adam flagstat` does (flagstat.py);
+``.pileups()`` converts them to ADAMPileup records (reads2ref.py).
 """
 from __future__ import annotations
 
@@ -188,6 +189,16 @@ class SamText:
         counters follow its result."""
         from .flagstat import sam_flagstat
         return sam_flagstat(self, stream)
+
+    def pileups(self, r0: int = 0, n: Optional[int] = None, stream=None):
+        """`adam reads2ref` over reads [r0, r0 + n) (bqsr_sam_pileup_*,
+        core/rdd/Reads2PileupProcessor.scala:34-197): their ADAMPileup records
+        as a pyarrow table (adam_save.pileup_schema's columns), reads in input
+        order, a read's pileups in reverse walk order.  Every read is
+        converted (LocusPredicate does not apply to SAM / BAM input); a read
+        the reference throws on raises BQSRError (``.read``)."""
+        from .reads2ref import sam_pileups
+        return sam_pileups(self, r0, n, stream=stream)
 
     def text(self) -> bytes:
         n = self.counts().text_bytes

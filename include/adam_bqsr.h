@@ -60,7 +60,8 @@ typedef enum bqsr_status {
   BQSR_ERR_INVALID_ARG = 11,     /* bad call: null pointer, inconsistent sizes, dims mismatch            */
   BQSR_ERR_DEVICE = 12,          /* HIP runtime failure                                                  */
   BQSR_ERR_UNSUPPORTED = 13,     /* input outside what the device path handles          */
-  BQSR_ERR_SAM_PARSE = 14        /* malformed SAM text where read_sam / SAMRecordConverter throws (adam_sam.h) */
+  BQSR_ERR_SAM_PARSE = 14,       /* malformed SAM text where read_sam / SAMRecordConverter throws (adam_sam.h) */
+  BQSR_ERR_PILEUP = 15           /* reads2ref: an exception inside Reads2PileupProcessor's CIGAR walk (adam_sam.h) */
 } bqsr_status;
 
 /* ADAMRecord boolean fields (adam-format/.../adam.avdl:28-38) and null-ness
@@ -156,14 +157,18 @@ void bqsr_context_destroy(bqsr_context* ctx);
  *   BQSR_TUNE_FLAGSTAT_GRID 0 auto (the flagstat kernels' grids follow the
  *                        input and the CU count), g > 0: at most g workgroups,
  *                        so that a small input runs every wavefront through
- *                        many passes of its grid-stride loop (tests) */
+ *                        many passes of its grid-stride loop (tests)
+ *   BQSR_TUNE_PILEUP_GRID 0 auto, g > 0: at most g workgroups for the two
+ *                        pileup kernels (adam_sam.h bqsr_sam_pileup_*), as
+ *                        BQSR_TUNE_FLAGSTAT_GRID */
 enum {
   BQSR_TUNE_ORDER = 1,
   BQSR_TUNE_FRONTS = 2,
   BQSR_TUNE_KEYMAJOR = 3,
   BQSR_TUNE_FUSED_PREP = 4,
   BQSR_TUNE_BGZF = 5,
-  BQSR_TUNE_FLAGSTAT_GRID = 6
+  BQSR_TUNE_FLAGSTAT_GRID = 6,
+  BQSR_TUNE_PILEUP_GRID = 7
 };
 bqsr_status bqsr_context_tune(bqsr_context* ctx, int knob, int64_t value);
 

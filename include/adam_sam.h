@@ -16,6 +16,8 @@
  *             (adam-cli/.../cli/Transform.scala:73-76)
  *   flagstat: adamFlagStat (adam-core/.../rdd/FlagStat.scala:21-116), the
  *             counters `adam flagstat` prints, over a parse or Arrow buffers
+ *   reads2ref: Reads2PileupProcessor (adam-core/.../rdd/Reads2PileupProcessor.scala:34-197),
+ *             the ADAMPileup rows `adam reads2ref` writes
  *
  * Same conventions as adam_bqsr.h (bqsr_status results, bqsr_last_error(),
  * library-owned handles with *_destroy, `stream` = hipStream_t as void*).
@@ -403,6 +405,94 @@ bqsr_status bqsr_flagstat_arrow(bqsr_context* ctx, const bqsr_flagstat_chunk* ch
  * failed[18], then the first NULL_FIELD read, to be preset to all ones). */
 bqsr_status bqsr_flagstat_arrow_device(bqsr_context* ctx, const bqsr_flagstat_chunk* chunk, void* counters,
                                        void* stream);
+
+/* `adam reads2ref` (adam-cli/.../cli/Reads2Ref.scala:53-75 over
+ * Reads2PileupProcessor.readToPileups, adam-core/.../rdd/Reads2PileupProcessor.
+ * scala:34-197): reads [r0, r0 + n) of a parse as ADAMPileup rows
+ * (adam-format/.../avro/adam.avdl:99-128), one per M, I, D or S base of the
+ * read's CIGAR; N, H, P, = and X elements produce none.  Reads in input
+ * order; a read's rows in REVERSE walk order (the reference prepends).
+ *   A read without CIGAR or without MD (no MD:Z tag) gives no rows.  Otherwise
+ *   a null start is BQSR_ERR_NULL_FIELD, an MD tag MdTag.apply rejects
+ *   BQSR_ERR_MD_PARSE (MdTag.scala:38-98; "" is the empty tag), and the walk
+ *   starts with referencePos = start, readPos = 0; the MD is looked up at
+ *   referencePos - start, also after an N (which the MD does not count: the
+ *   reference looks in the wrong place, and so does this).
+ *     M  referenceBase = the read's base where the MD says match, else the
+ *        MD's mismatch base; readBase; rangeOffset / rangeLength null
+ *     I  readBase; rangeOffset = index in the element, rangeLength = its
+ *        length; referenceBase null; position = the unchanged referencePos
+ *     D  referenceBase = the MD's deleted base; readBase null; range as I;
+ *        sangerQuality from the NEXT read base (a trailing D throws)
+ *     S  as I, and numSoftClipped = 1
+ *   every row: position, sangerQuality = (int)(signed byte)(qual - 33),
+ *   mapQuality = mapq (nullable), numReverseStrand = readNegativeStrand,
+ *   readStart = start, readEnd = start + the reference-consuming lengths.
+ *   BQSR_ERR_PILEUP where the walk throws: a sequence char outside the Base
+ *   enum ("*", "=", ".", lower case: the MD is upper-cased, the sequence is
+ *   not); sequence or quals shorter than the CIGAR's read bases; an M base
+ *   the MD has as a delete or not at all; a D base the MD has no delete for;
+ *   a read with readMapped false that would give a row (record.end is None) --
+ *   which, with quirk Q2, includes every FLAG-0 SAM record with CIGAR and MD.
+ *   A null sequence or qual reached by the walk is BQSR_ERR_NULL_FIELD.  The
+ *   first exception in the reference's evaluation order decides a read's
+ *   status; the first throwing read in input order decides the call's
+ *   (bqsr_last_error_read; no rows).
+ *   Nothing is filtered here: LocusPredicate applies to Parquet input only
+ *   (AdamContext.scala:318-332) and is the caller's (adam_amd/reads2ref.py).
+ *   The flags column is used as it stands and only readMapped and
+ *   readNegativeStrand are read, so bqsr_sam_mark_duplicates changes nothing.
+ * BQSR_ERR_UNSUPPORTED: more than 2^31 - 1 rows in one call; per read, a
+ * mismatch or deleted base 2^26 or more reference positions after start, or
+ * 2^31 or more rows or read bases (field lengths of 65535 stay far inside).
+ * prepare: the count / validate pass and the scan (no column memory: a cheap
+ * call, also for choosing ranges by n_rows); columns: the emit pass (a lane
+ * per row) and the copies into the caller's host buffers (NULL skips one).
+ * Device: adam_amd/csrc/pileup.hip.  `read` = the row's read, counted from
+ * r0; the Base columns hold the enum ordinal (A C T G U N X K M R Y S W B V H
+ * D); slots of null entries hold 0; bitmaps are Arrow's, bits at and beyond
+ * n_rows clear; countAtPosition is the constant 1. */
+typedef struct bqsr_pileup_sizes {
+  int64_t n_reads;
+  int64_t n_rows;
+  int64_t bitmap_words; /* ceil(n_rows / 64) u64 words per bitmap */
+} bqsr_pileup_sizes;
+typedef struct bqsr_pileup_host {
+  int32_t* read;
+  int64_t* position;
+  int32_t* range_offset;
+  int32_t* range_length;
+  uint8_t* reference_base;
+  uint8_t* read_base;
+  int32_t* sanger_quality;
+  int32_t* map_quality;
+  int32_t* num_soft_clipped;
+  int32_t* num_reverse_strand;
+  int64_t* read_start;
+  int64_t* read_end;
+  uint64_t* range_valid; /* rangeOffset and rangeLength */
+  uint64_t* reference_base_valid;
+  uint64_t* read_base_valid;
+  uint64_t* map_quality_valid;
+} bqsr_pileup_host;
+bqsr_status bqsr_sam_pileup_prepare(bqsr_context* ctx, bqsr_sam* s, int64_t r0, int64_t n, void* stream,
+                                    bqsr_pileup_sizes* out);
+bqsr_status bqsr_sam_pileup_columns(bqsr_context* ctx, bqsr_sam* s, const bqsr_pileup_host* dst, void* stream);
+/* The same over a bqsr_arrow handle (the parse layout bqsr_arrow_load built).
+ * mapq is not part of bqsr_arrow_chunk: it comes here, one int32 array and
+ * validity bitmap (NULL: all valid; a NULL array: all null) per chunk of
+ * chunk_reads[c] reads, host memory, covering the handle's reads; it is kept
+ * with the handle, so later calls may pass n_chunks = 0 (never given: every
+ * mapQuality null).  A null boolean reads as false (as bqsr_arrow_chunk). */
+bqsr_status bqsr_arrow_pileup_prepare(bqsr_context* ctx, bqsr_arrow* a, int64_t r0, int64_t n,
+                                      const int64_t* chunk_reads, const int32_t* const* mapq,
+                                      const uint8_t* const* mapq_validity, int32_t n_chunks, void* stream,
+                                      bqsr_pileup_sizes* out);
+bqsr_status bqsr_arrow_pileup_columns(bqsr_context* ctx, bqsr_arrow* a, const bqsr_pileup_host* dst, void* stream);
+/* MEASUREMENT ONLY, not part of the stable interface: the device-event times
+ * of the count and the emit kernel of the calling thread's last prepare /
+ * columns call, in milliseconds (tools/bench_adam.py --reads2ref). */
+bqsr_status bqsr_pileup_kernel_times(double* count_ms, double* emit_ms);
 
 /* MarkDuplicates across the partitions of one input (the reference's
  * groupBy spans every partition of the RDD, MarkDuplicates.scala:43-58).

@@ -18,6 +18,19 @@ the flagstat call (host clock around calls that end in a synchronise; the
 best of --reps), Arrow's read, the upload-and-count call and the kernel alone
 (device events, buffers resident); then the Arrow-form kernel alone over
 --kernel-reads random reads on the device, as bytes/s.  One JSON line.
+
+    python tools/bench_adam.py --reads2ref [--reads 2000000] [--part-reads N] [--compression snappy]
+
+--reads2ref measures `adam reads2ref` (adam_amd/reads2ref.py) over the same
+synthetic reads as SAM text: the job's steps run one after the other in the
+main thread, each timed by the host clock around calls that end in a
+synchronise -- parse, count (bqsr_sam_pileup_prepare), emit + D2H
+(bqsr_sam_pileup_columns: the kernel by device events, the copies as the
+rest of the call), the read-level columns and the Arrow table -- while the
+writer's host threads encode the part files behind it (their busy seconds
+summed; `close` is the wait for them at the end).  The two kernels' times are
+device events; the emit kernel's bytes written per second stand beside the
+copy rate DESIGN.md uses.  One JSON line.
 """
 import argparse
 import json
@@ -251,8 +264,122 @@ def bench_flagstat(a):
     print(json.dumps(res))
 
 
+def bench_reads2ref(a):
+    """the --reads2ref measurements (see the module doc)"""
+    import ctypes
+    import threading
+    import torch
+    from adam_amd import adam_save, bqsr
+    from adam_amd import reads2ref as R
+    from adam_amd._capi import check
+    from adam_amd.sam import SamText
+    t0 = time.perf_counter()
+    sam = synthetic_sam(a.reads, a.len)
+    log("generated %d bytes of SAM in %.1f s" % (len(sam), time.perf_counter() - t0))
+    torch.zeros(1, device="cuda")
+    ctx = bqsr.Context.get(0)
+    L = R._lib()
+    work = a.dir or tempfile.mkdtemp(prefix="bench_reads2ref_")
+    os.makedirs(work, exist_ok=True)
+    part_reads = a.part_reads if a.part_reads != 1 << 19 else R.DEFAULT_PART_READS
+    ROW_BYTES = 3 * 8 + 7 * 4 + 2  # the device columns of one row; four validity bits on top
+
+    def run(out):
+        ph = {k: 0.0 for k in ("parse", "count", "count_kernel", "columns", "emit_kernel", "host_buffers",
+                               "read_level_and_table", "add", "close")}
+        busy = [0.0]
+        lock = threading.Lock()
+        t_all = time.perf_counter()
+        W = adam_save.AdamWriter(out, a.compression, overwrite=True, dict_cols=adam_save.PILEUP_DICT_COLS,
+                                 stats_cols=adam_save.PILEUP_STATS_COLS, huffman_cols=(), max_pending=2)
+        write = W._write
+
+        def timed_write(table, name):
+            t = time.perf_counter()
+            write(table, name)
+            with lock:
+                busy[0] += time.perf_counter() - t
+        W._write = timed_write
+        rows = 0
+        ok = False
+        try:
+            t = time.perf_counter()
+            st = SamText(sam, ctx)
+            ph["parse"] += time.perf_counter() - t
+            try:
+                hdr = adam_save.header_info(st)
+                n = st.counts().n_reads
+                for r0 in range(0, n, part_reads):
+                    m = min(part_reads, n - r0)
+                    sz = R.PileupSizes()
+                    t = time.perf_counter()
+                    check(L.bqsr_sam_pileup_prepare(ctx.handle, st.h, r0, m, None, ctypes.byref(sz)))
+                    ph["count"] += time.perf_counter() - t
+                    ph["count_kernel"] += R.kernel_times()[0] * 1e-3
+                    t = time.perf_counter()
+                    H, arrays = R._host_columns(sz.n_rows)
+                    ph["host_buffers"] += time.perf_counter() - t
+                    t = time.perf_counter()
+                    check(L.bqsr_sam_pileup_columns(ctx.handle, st.h, ctypes.byref(H), None))
+                    ph["columns"] += time.perf_counter() - t
+                    ph["emit_kernel"] += R.kernel_times()[1] * 1e-3
+                    t = time.perf_counter()
+                    table = R._table(sz.n_rows, arrays, R._sam_read_level(st, r0, m, hdr))
+                    ph["read_level_and_table"] += time.perf_counter() - t
+                    rows += sz.n_rows
+                    t = time.perf_counter()
+                    W.add(table)
+                    ph["add"] += time.perf_counter() - t
+                    del table, arrays, H
+            finally:
+                st.close()
+            ok = True
+        finally:
+            t = time.perf_counter()
+            W.close(ok)
+            ph["close"] += time.perf_counter() - t
+        return time.perf_counter() - t_all, rows, ph, busy[0], W.parts
+
+    try:
+        out = os.path.join(work, "out.adam")
+        log("warm-up run")
+        run(out)
+        best = None
+        for _ in range(max(1, a.reps)):
+            log("timed run")
+            r = run(out)
+            if best is None or r[0] < best[0]:
+                best = r
+        dt, rows, ph, busy, parts = best
+        out_bytes = sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out))
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    emit_bytes = rows * ROW_BYTES + 4 * ((rows + 63) // 64) * 8
+    d2h = ph["columns"] - ph["emit_kernel"]
+    res = {"metric": "adam reads2ref SAM -> ADAMPileup Parquet: seconds per phase (host clock around synchronising "
+                     "calls, main thread), the two kernels by device events, writer threads' busy seconds",
+           "reads": a.reads, "read_len": a.len, "rows": rows, "input_bytes": len(sam), "output_bytes": out_bytes,
+           "compression": a.compression, "part_reads": part_reads, "parts": parts, "seconds": dt,
+           "rows_per_s": rows / dt, "reads_per_s": a.reads / dt,
+           "phases_s": {"parse": ph["parse"], "count": ph["count"], "emit": ph["emit_kernel"], "d2h": d2h,
+                        "host_buffers": ph["host_buffers"], "read_level_and_table": ph["read_level_and_table"],
+                        "add_waiting_for_writers": ph["add"], "close": ph["close"]},
+           "parquet_encode_busy_s": busy,
+           "kernels": {"count_ms": ph["count_kernel"] * 1e3, "emit_ms": ph["emit_kernel"] * 1e3,
+                       "emit_bytes_written": emit_bytes,
+                       "emit_bytes_per_s": emit_bytes / ph["emit_kernel"] if ph["emit_kernel"] else None,
+                       "copy_rate_bytes_per_s": 6.29e12,
+                       "share_of_copy_rate": emit_bytes / ph["emit_kernel"] / 6.29e12 if ph["emit_kernel"] else None,
+                       "count_reads_per_s": a.reads / ph["count_kernel"] if ph["count_kernel"] else None},
+           "d2h_bytes": emit_bytes, "d2h_bytes_per_s": emit_bytes / d2h if d2h > 0 else None}
+    log("%.2f s, %d rows, emit %.3f ms, count %.3f ms" % (dt, rows, ph["emit_kernel"] * 1e3, ph["count_kernel"] * 1e3))
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--reads2ref", action="store_true", help="measure adam reads2ref instead of the transform")
     ap.add_argument("--flagstat", action="store_true", help="measure adam flagstat instead of the transform")
     ap.add_argument("--kernel-reads", type=int, default=64_000_000,
                     help="--flagstat: random reads for the Arrow-form kernel alone")
@@ -270,6 +397,8 @@ def main():
     a = ap.parse_args()
     if a.flagstat:
         return bench_flagstat(a)
+    if a.reads2ref:
+        return bench_reads2ref(a)
     t0 = time.perf_counter()
     data = synthetic_sam(a.reads, a.len)
     if a.bam:
