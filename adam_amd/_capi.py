@@ -40,6 +40,8 @@ EXPORTS = [
     "bqsr_bgzf_inflate", "bqsr_sam_bam_form",
     "bqsr_sam_pileup_prepare", "bqsr_sam_pileup_columns", "bqsr_arrow_pileup_prepare", "bqsr_arrow_pileup_columns",
     "bqsr_pileup_kernel_times",
+    "bqsr_sam_bam_prepare", "bqsr_sam_bam_records", "bqsr_sam_bam_header", "bqsr_bgzf_compress",
+    "bqsr_bam_kernel_times",
 ]
 
 

@@ -3,7 +3,11 @@ reference loads BAM through Hadoop-BAM (core/rdd/AdamContext.scala:122-137),
 so its SAM fixtures are converted here, record by record, as samtools would
 write them (SAM v1 BAM encoding: 4-bit SEQ codes, QUAL - 33 or 0xFF, CIGAR
 words, typed optional fields; integers in the smallest fitting type).
-Pure Python (zlib): test and tool infrastructure, not the ingest path."""
+Pure Python (zlib): test and tool infrastructure, not the ingest path and not
+the output path -- `transform IN OUT.bam` writes BAM through the device
+encoder (csrc/bam_out.hip, sam.SamText.bam_records, transform._BamOut), which
+follows the spec where this file does not: B arrays are written here as Z
+strings, and the bin of an unplaced read is not reg2bin(-1, 0)."""
 from __future__ import annotations
 
 import struct

@@ -10,7 +10,9 @@ over the records and updates their duplicateRead bits; ``.rewrite(job)``
 puts a ResidentJob's recalibrated quality strings into the records' QUAL
 fields (the output path, core/rdd/AdamRDDFunctions.scala:37-56, as SAM text);
 ``.flagstat()`` counts the records as `adam flagstat` does (flagstat.py);
-``.pileups()`` converts them to ADAMPileup records (reads2ref.py).
+``.pileups()`` converts them to ADAMPileup records (reads2ref.py);
+``.bam_header()`` / ``.bam_records()`` encode them as BAM on the device
+(bam_out.hip) and ``bgzf_compress`` cuts such a stream into BGZF members.
 """
 from __future__ import annotations
 
@@ -33,6 +35,13 @@ class SamCounts(ctypes.Structure):
 class SamColumns(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("flags", "rg_id", "ref_index", "start", "seq_offset", "seq",
                                                "qual_offset", "qual", "cigar_offset", "cigar", "md_offset", "md")]
+
+
+class BamSizes(ctypes.Structure):
+    _fields_ = [("n_reads", ctypes.c_int64), ("bytes", ctypes.c_int64), ("n_floats", ctypes.c_int64)]
+
+
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")  # the empty last member
 
 
 class DupReads(ctypes.Structure):
@@ -72,6 +81,12 @@ def _lib():
             "bqsr_sort_order": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, vp]),
             "bqsr_sam_sort": (ctypes.c_int, [vp, vp, vp]),
             "bqsr_sam_bam_form": (i32, [vp]),
+            "bqsr_sam_bam_prepare": (ctypes.c_int, [vp, vp, i64, i64, vp, ctypes.POINTER(BamSizes)]),
+            "bqsr_sam_bam_records": (ctypes.c_int, [vp, vp, vp, vp]),
+            "bqsr_sam_bam_header": (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i64)]),
+            "bqsr_bgzf_compress": (ctypes.c_int, [vp, i64, i32, vp, i64, ctypes.POINTER(i64)]),
+            "bqsr_bam_kernel_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double),
+                                                     ctypes.POINTER(ctypes.c_double)]),
             "bqsr_bgzf_inflate": (ctypes.c_int, [vp, ctypes.c_char_p, i64, vp, vp, i64, ctypes.POINTER(i64), vp, i64,
                                                  ctypes.POINTER(i64)]),
         }
@@ -200,6 +215,28 @@ class SamText:
         from .reads2ref import sam_pileups
         return sam_pileups(self, r0, n, stream=stream)
 
+    def bam_header(self) -> bytes:
+        """The BAM header of the parse (bqsr_sam_bam_header): magic, the
+        header text unchanged, the @SQ lines as the reference list."""
+        n = ctypes.c_int64()
+        check(self.L.bqsr_sam_bam_header(self.h, None, 0, ctypes.byref(n)))
+        buf = np.zeros(max(1, n.value), np.uint8)
+        check(self.L.bqsr_sam_bam_header(self.h, buf.ctypes.data, n.value, ctypes.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def bam_records(self, r0: int = 0, n: Optional[int] = None, stream=None) -> np.ndarray:
+        """Records [r0, r0 + n) of the current text as BAM records
+        (bqsr_sam_bam_prepare / _records: encoded on the device, float tags
+        final), a uint8 array.  Use after ``rewrite`` / ``sort``.  A record
+        BAM cannot hold raises BQSRError (UNSUPPORTED, ``.read``)."""
+        if n is None:
+            n = self.counts().n_reads - r0
+        sz = BamSizes()
+        check(self.L.bqsr_sam_bam_prepare(self.ctx.handle, self.h, int(r0), int(n), stream, ctypes.byref(sz)))
+        out = np.empty(max(1, sz.bytes), np.uint8)
+        check(self.L.bqsr_sam_bam_records(self.ctx.handle, self.h, out.ctypes.data, stream))
+        return out[:sz.bytes]
+
     def text(self) -> bytes:
         n = self.counts().text_bytes
         buf = ctypes.create_string_buffer(max(1, n))
@@ -233,6 +270,27 @@ def bgzf_inflate(data: bytes, ctx: Optional[bqsr.Context] = None, stream=None):
     check(L.bqsr_bgzf_inflate(ctx.handle, data, len(data), stream, out.ctypes.data, n.value, ctypes.byref(n),
                               status.ctypes.data, nb.value, ctypes.byref(nb)))
     return out[:n.value], status[:nb.value]
+
+
+def bgzf_compress(data, level: int = 6) -> bytes:
+    """BGZF members of a byte stream (bqsr_bgzf_compress: 65280 bytes each,
+    compressed by host threads; level 0: stored).  No EOF member: append
+    BGZF_EOF once at the end of the file."""
+    L = _lib()
+    a = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    n = int(a.size)
+    cap = n + 64 * (n // 65280 + 1)
+    out = np.empty(cap, np.uint8)
+    got = ctypes.c_int64()
+    check(L.bqsr_bgzf_compress(a.ctypes.data if n else None, n, int(level), out.ctypes.data, cap, ctypes.byref(got)))
+    return out[:got.value].tobytes()
+
+
+def bam_kernel_times():
+    """(pass 1 ms, pass 2 ms) of this thread's last ``bam_records`` (measurement only)"""
+    a, b = ctypes.c_double(), ctypes.c_double()
+    check(_lib().bqsr_bam_kernel_times(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
 
 
 class DupSet:

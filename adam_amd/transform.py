@@ -4,9 +4,18 @@
     python -m adam_amd.transform INPUT.sam OUTPUT.sam [-mark_duplicate_reads]
         [-recalibrate_base_qualities] [-dbsnp_sites SITES.vcf]
     python -m adam_amd.transform INPUT.{adam,parquet,sam} OUTPUT.{adam,parquet} [...]
+    python -m adam_amd.transform INPUT.{sam,bam} OUTPUT.bam [-bam_compression_level N] [...]
 
-SAM or BAM in goes through the device path described below, out as SAM text
-or as ADAMRecord Parquet part files (adamSave, adam_save.py).  ADAMRecord
+SAM or BAM in goes through the device path described below, out as SAM text,
+as BAM (an output name ending in .bam: the records encoded on the device,
+sam.SamText.bam_records, cut into BGZF members compressed by host threads,
+sam.bgzf_compress; see _BamOut) or as ADAMRecord Parquet part files (adamSave,
+adam_save.py).  BAM holds what the SAM spec allows: a record it cannot hold
+-- the reference's trimmed recalibrated QUAL strings and its chars above
+0x7F among them, which the SAM text sink writes as they are -- fails the job
+with BQSRError (UNSUPPORTED) naming the read, and no output appears.
+ADAMRecord Parquet input cannot be written as BAM (that path has no SAM lines
+to encode): a ValueError before anything is read.  ADAMRecord
 Parquet in goes through ``transform_parquet``: Arrow decodes the Parquet
 pages on host threads, the column buffers go to the device as they are
 (parquet.ArrowReads), MarkDuplicates, the BQSR batch and the recalibrated
@@ -395,6 +404,100 @@ class _SamOut:
             os.remove(self.tmp)
 
 
+# Records per encoded piece of BAM output.  A record of a 100-150 base read is
+# 250-350 bytes of BAM, so 2^19 records are 130-180 MB: on the device next to
+# the text they are encoded from, in host memory as the downloaded stream,
+# and once more as BGZF members while the next piece is encoded and downloaded
+# -- a few hundred MB in flight whatever the partition's size, small beside HBM
+# and host memory; large enough (2000+ members) that the 16 compressing
+# threads stay busy and a piece's fixed costs (two launches, a scan, three
+# copies) do not show; far below the 2^31 bytes one piece may hold.
+BAM_PIECE_READS = 1 << 19
+
+
+class _BamOut:
+    """BAM output with _SamOut's contract (records appended partition by
+    partition; the file appears when the job succeeds): the header once,
+    then per emit the records in pieces of `piece_reads`, each encoded on the
+    device (SamText.bam_records) and compressed into BGZF members by host
+    threads (sam.bgzf_compress) while the next piece is encoded and
+    downloaded; the EOF marker at close(ok=True).  A piece ends in a short
+    member."""
+
+    def __init__(self, path: str, level: int = 6, piece_reads: int = BAM_PIECE_READS, overwrite: bool = False):
+        from concurrent.futures import ThreadPoolExecutor
+        if not 0 <= int(level) <= 9:
+            raise ValueError("-bam_compression_level must be 0..9")
+        _check_out(path, overwrite, False)
+        self.path = path
+        self.tmp = path + ".partial"
+        self.level = int(level)
+        self.piece_reads = max(1, int(piece_reads))
+        self.fh = open(self.tmp, "wb")
+        self.first = True
+        self.pool = ThreadPoolExecutor(1)
+        self.pending = None
+        # measured: the two kernels' device-event ms, stream / file bytes, seconds inside the compressor
+        self.stats = {"len_ms": 0.0, "write_ms": 0.0, "record_bytes": 0, "text_bytes": 0, "file_bytes": 0,
+                      "compress_s": 0.0}
+
+    def _compress(self, data):
+        from .sam import bgzf_compress
+        t0 = time.perf_counter()
+        out = bgzf_compress(data, self.level)
+        self.stats["compress_s"] += time.perf_counter() - t0
+        return out
+
+    def _drain(self):
+        if self.pending is not None:
+            f, self.pending = self.pending, None
+            out = f.result()
+            self.fh.write(out)
+            self.stats["file_bytes"] += len(out)
+
+    def _submit(self, data):
+        self._drain()  # one piece compressing while the next is encoded
+        self.pending = self.pool.submit(self._compress, data)
+
+    def emit(self, i, sam, quals=None):
+        """as _SamOut.emit: the text rewritten (QUAL from the apply, FLAG
+        after MarkDuplicates), then its records encoded and appended"""
+        from .sam import bam_kernel_times
+        if quals is None:
+            sam.rewrite(None)
+        else:
+            check(_capi.lib().bqsr_sam_rewrite_quals(sam.ctx.handle, sam.h, *quals))
+        if self.first:
+            self._submit(sam.bam_header())
+            self.first = False
+        c = sam.counts()
+        self.stats["text_bytes"] += c.text_bytes
+        for r0 in range(0, c.n_reads, self.piece_reads):
+            rec = sam.bam_records(r0, min(self.piece_reads, c.n_reads - r0))
+            a, b = bam_kernel_times()
+            self.stats["len_ms"] += a
+            self.stats["write_ms"] += b
+            self.stats["record_bytes"] += int(rec.size)
+            self._submit(rec)
+
+    def close(self, ok: bool = True):
+        from .sam import BGZF_EOF
+        try:
+            if ok:
+                ok = False
+                self._drain()
+                self.fh.write(BGZF_EOF)
+                self.stats["file_bytes"] += len(BGZF_EOF)
+                ok = True
+        finally:
+            self.pool.shutdown(wait=True)
+            self.fh.close()
+            if ok:
+                os.replace(self.tmp, self.path)
+            elif os.path.exists(self.tmp):
+                os.remove(self.tmp)
+
+
 class _AdamOut:
     """ADAM output (adamSave): part files of `part_reads` records each."""
 
@@ -448,14 +551,20 @@ def is_bam(data) -> bool:
 def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bool = False,
               dbsnp: Optional[str] = None, device: int = 0, partition_bytes: int = DEFAULT_PARTITION_BYTES,
               compression: str = "gzip", part_reads: int = 1 << 19, overwrite: bool = False,
-              sort_reads: bool = False) -> Dict[str, float]:
+              sort_reads: bool = False, bam_level: int = 6,
+              bam_piece_reads: int = BAM_PIECE_READS) -> Dict[str, float]:
     """Transform.run (cli/Transform.scala:62-97) over SAM or BAM input: the
     records parsed on the device (a BAM's records become SAM lines there),
     MarkDuplicates, BQSR, then adamSave (OUT.adam / .parquet / a directory:
-    ADAMRecord Parquet part files, adam_save.py) or SAM text.  ADAM Parquet
-    input goes through transform_parquet (Arrow reads it on the host).
-    sort_reads: the records sorted on the device before the save (see the
-    module doc); the input must be one partition."""
+    ADAMRecord Parquet part files, adam_save.py), BAM (OUT.bam, _BamOut:
+    bam_level 0-9, records per encoded piece bam_piece_reads) or SAM text.
+    ADAM Parquet input goes through transform_parquet (Arrow reads it on the
+    host).  sort_reads: the records sorted on the device before the save (see
+    the module doc); the input must be one partition."""
+    bam_out = out.endswith(".bam")
+    if bam_out and is_parquet(inp):  # before anything is read
+        raise ValueError("ADAM Parquet input cannot be written as BAM (no SAM lines to encode): "
+                         "use a .adam / .parquet output, or SAM / BAM input")
     if is_parquet(inp):
         return transform_parquet(inp, out, mark_duplicates, recalibrate, dbsnp, device, overwrite, sort_reads)
     if sort_reads and os.path.getsize(inp):  # refused before any output file or parse exists
@@ -470,8 +579,9 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
     # ADAM output by name, or over an earlier adamSave directory (never just
     # because `out` is some existing directory: the sinks refuse that)
     from .adam_save import is_adam_output
-    adam_out = out.endswith((".adam", ".parquet")) or is_adam_output(out)
-    sink = _AdamOut(out, compression, part_reads, overwrite) if adam_out else _SamOut(out, overwrite)
+    adam_out = not bam_out and (out.endswith((".adam", ".parquet")) or is_adam_output(out))
+    sink = (_BamOut(out, bam_level, bam_piece_reads, overwrite) if bam_out
+            else _AdamOut(out, compression, part_reads, overwrite) if adam_out else _SamOut(out, overwrite))
     try:
         ctx = bqsr.Context.get(device)
     except BaseException:
@@ -538,6 +648,8 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
         stats.setdefault("phases", {})["close"] = time.perf_counter() - t1
     if adam_out:
         stats["parts"] = sink.w.parts
+    if bam_out:
+        stats["bam"] = sink.stats
     stats["seconds"] = time.perf_counter() - t0
     return stats
 
@@ -558,6 +670,9 @@ def main(argv=None) -> int:
     ap.add_argument("-parquet_compression", default="gzip", choices=("gzip", "snappy", "zstd", "none"),
                     help="ADAM output: the part files' codec (adamSave's default: GZIP)")
     ap.add_argument("-part_reads", type=int, default=1 << 19, help="ADAM output: records per part file")
+    ap.add_argument("-bam_compression_level", type=int, default=6, choices=range(10), metavar="N",
+                    help="BAM output (OUTPUT.bam): the BGZF members' DEFLATE level, 0-9 (0: stored; default 6, "
+                         "zlib's and samtools')")
     ap.add_argument("-overwrite", action="store_true",
                     help="replace an existing output (a file, or a directory of ADAM part files only)")
     a = ap.parse_args(argv)
@@ -565,7 +680,7 @@ def main(argv=None) -> int:
         ap.error("-coalesce / -realignIndels are outside this build")
     st = transform(a.input, a.output, a.mark_duplicate_reads, a.recalibrate_base_qualities, a.dbsnp_sites,
                    partition_bytes=a.partition_bytes, compression=a.parquet_compression, part_reads=a.part_reads,
-                   overwrite=a.overwrite, sort_reads=a.sort_reads)
+                   overwrite=a.overwrite, sort_reads=a.sort_reads, bam_level=a.bam_compression_level)
     print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
     return 0
 

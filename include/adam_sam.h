@@ -249,6 +249,77 @@ bqsr_status bqsr_sam_adam_set_quals(bqsr_context* ctx, bqsr_sam* s, const bqsr_b
 /* the header lines of the parse (SAM input, or a BAM's header text) */
 bqsr_status bqsr_sam_header_text(const bqsr_sam* s, char* dst, int64_t cap, int64_t* len);
 
+/* BAM records (SAM spec §4.2, little endian) of records [r0, r0 + n) of the
+ * parse, from its current text (after bqsr_sam_rewrite_quals / bqsr_sam_sort:
+ * QUAL and FLAG final; a BAM-born parse holds SAM lines too), its CIGAR
+ * words and its @SQ index, encoded on the device.  Per record, block_size
+ * first:
+ *   refID        the @SQ index of RNAME ("*": -1)
+ *   pos          POS - 1
+ *   l_read_name  QNAME length + 1
+ *   mapq         as given
+ *   bin          the spec's reg2bin(pos, end), arithmetic shifts; end = pos +
+ *                the CIGAR's reference length (M D N = X), pos + 1 when that
+ *                is 0 or CIGAR is "*" (so pos = -1 gives 4680)
+ *   n_cigar_op   the parse's CIGAR element count
+ *   flag         as given (0x400 following MarkDuplicates when it ran)
+ *   l_seq        SEQ length, 0 for "*"
+ *   next_refID   "=": refID; "*": -1
+ *   next_pos     PNEXT - 1
+ *   tlen         as given
+ *   read_name    QNAME, NUL
+ *   cigar        the parse's u32 words (len << 4 | op), none for "*"
+ *   seq          4-bit codes of "=ACMGRSVTWYHKDBN", upper-cased, anything else
+ *                15, high nibble first
+ *   qual         each byte - 33; l_seq bytes of 0xFF for "*"
+ *   tags, in input order: A; i as the smallest of c C s S i I that holds the
+ *                value, the signed type when both fit; f as binary32 (what C
+ *                strtof gives for the text: the slots are filled on the host
+ *                before the bytes are handed out); Z and H as the bytes and a
+ *                NUL; B:t,v,... for t in cCsSiIf as the type byte, an int32
+ *                count and the values ("B:c" alone: count 0).
+ * BQSR_ERR_UNSUPPORTED, with the first offending read in input order
+ * (bqsr_last_error_read) and nothing written, for what BAM cannot hold or
+ * the spec forbids: RNAME / RNEXT that is neither "*" (nor "=") nor an @SQ
+ * name; QNAME above 254 bytes; more than 65535 CIGAR elements; POS - 1 /
+ * PNEXT - 1 / TLEN outside int32; FLAG outside 16 bits, MAPQ outside 8; a
+ * QUAL other than "*" whose byte length differs from SEQ's or with a byte
+ * outside '!'..'~' (the reference's trimmed recalibrated strings and its
+ * chars above 0x7F, which the SAM text sink keeps writing); an unknown tag
+ * type letter; an 'i' value outside [-2^31, 2^32 - 1]; a B value outside its
+ * element type; an odd-length or non-hex H; a value that is not of its type.
+ * prepare: pass 1 (the checks, every record's size) and the byte count;
+ * records: pass 2 and the copy into dst (sizes.bytes bytes of host memory),
+ * floats final. */
+typedef struct bqsr_bam_sizes {
+  int64_t n_reads;
+  int64_t bytes;    /* of the records, block_size words included */
+  int64_t n_floats; /* f values (tags and B:f elements) converted on the host */
+} bqsr_bam_sizes;
+bqsr_status bqsr_sam_bam_prepare(bqsr_context* ctx, bqsr_sam* s, int64_t r0, int64_t n, void* stream,
+                                 bqsr_bam_sizes* out);
+bqsr_status bqsr_sam_bam_records(bqsr_context* ctx, bqsr_sam* s, uint8_t* dst, void* stream);
+/* The BAM header of the parse: "BAM\1", l_text, the header text unchanged (no
+ * SO: edit, as bqsr_sam_sort), n_ref, and every @SQ line in order as l_name,
+ * name, NUL, LN (0 when absent).  *len: its size; at most cap bytes are
+ * copied (dst NULL with cap 0: the size only). */
+bqsr_status bqsr_sam_bam_header(const bqsr_sam* s, uint8_t* dst, int64_t cap, int64_t* len);
+/* BGZF members of a byte stream (SAM spec §4.1), by min(16, hardware
+ * threads) host threads: `in` cut into members of 65280 bytes (a record may
+ * straddle two), each raw DEFLATE at `level` (1-9: libdeflate, zlib at
+ * windowBits -15 when absent; 0, or a member DEFLATE would not shrink: one
+ * stored block) with BSIZE in the BC extra field, CRC32 and ISIZE.  No EOF
+ * member: the caller appends the 28-byte marker once.  *out_len: the size,
+ * also when it exceeds cap (BQSR_ERR_INVALID_ARG then); n + 64 * (n / 65280
+ * + 1) bytes always suffice.  No device call. */
+bqsr_status bqsr_bgzf_compress(const uint8_t* in, int64_t n, int32_t level, uint8_t* out, int64_t cap,
+                               int64_t* out_len);
+/* MEASUREMENT ONLY, not part of the stable interface: the device-event times
+ * of the calling thread's last bqsr_sam_bam_prepare (pass 1) and
+ * bqsr_sam_bam_records (pass 2) kernels, in milliseconds
+ * (tools/bench_adam.py --bam-out). */
+bqsr_status bqsr_bam_kernel_times(double* len_ms, double* write_ms);
+
 /* MarkDuplicates (§8 f3): adam-core/.../rdd/MarkDuplicates.scala:24-111 over
  * SingleReadBucket (models/SingleReadBucket.scala:27-37: reads grouped by
  * (recordGroupId, readName)) and ReferencePositionPair

@@ -31,6 +31,18 @@ writer's host threads encode the part files behind it (their busy seconds
 summed; `close` is the wait for them at the end).  The two kernels' times are
 device events; the emit kernel's bytes written per second stand beside the
 copy rate DESIGN.md uses.  One JSON line.
+
+    python tools/bench_adam.py --bam-out [--reads 2000000] [--bam-level 6]
+
+--bam-out measures `transform IN.sam OUT.bam` (transform._BamOut) next to
+`transform IN.sam OUT.sam` over the same input in the same run (both warmed,
+the best of --reps): MarkDuplicates and BQSR over synthetic reads generated
+without Q <= 2 read ends (BAM refuses the reference's trimmed recalibrated
+strings; should a recalibrated char still leave '!'..'~' the refusal is
+reported and both legs rerun without BQSR).  Reads/s and the phase split of
+both legs, the two encoder kernels by device events with the bytes they move
+(pass 1 reads the record text; pass 2 reads it again and writes the records)
+as a fraction of 8 TB/s, and the compressor's MB/s of stream.  One JSON line.
 """
 import argparse
 import json
@@ -54,19 +66,22 @@ def log(msg):
 def _chunk(args):
     from adam_amd import synth
     from adam_amd.samgen import sam_text
-    r0, n, read_len, total = args
-    b = synth.generate(n, (read_len,), 2, 20261015 + 2, first_read=r0)
+    r0, n, read_len, total = args[:4]
+    kw = {"p_q2tail": args[4]} if len(args) > 4 else {}
+    b = synth.generate(n, (read_len,), 2, 20261015 + 2, first_read=r0, **kw)
     text = sam_text(b, n_rg=2, qname="c%d_" % (r0 // CHUNK))
     if r0:  # the header once
         text = b"".join(l + b"\n" for l in text.split(b"\n") if l and not l.startswith(b"@"))
     return text
 
 
-def synthetic_sam(n_reads: int, read_len: int) -> bytes:
+def synthetic_sam(n_reads: int, read_len: int, p_q2tail=None) -> bytes:
     """cfg2-like reads as SAM text, generated in slices by a process pool
-    (before the GPU is touched); QNAMEs unique per read"""
+    (before the GPU is touched); QNAMEs unique per read.  p_q2tail: the share
+    of reads with a Q2 tail (None: the generator's default)"""
     from multiprocessing import get_context
-    jobs = [(r0, min(CHUNK, n_reads - r0), read_len, n_reads) for r0 in range(0, n_reads, CHUNK)]
+    extra = () if p_q2tail is None else (p_q2tail,)
+    jobs = [(r0, min(CHUNK, n_reads - r0), read_len, n_reads) + extra for r0 in range(0, n_reads, CHUNK)]
     # close() + join(), not the context manager: its terminate() SIGTERMs
     # workers still unwinding (under rocprofv3 the signal handler prints an
     # abort trace)
@@ -377,8 +392,79 @@ def bench_reads2ref(a):
     print(json.dumps(res))
 
 
+def bench_bam_out(a):
+    t0 = time.perf_counter()
+    data = synthetic_sam(a.reads, a.len, p_q2tail=0.0)
+    log("generated %d bytes in %.1f s" % (len(data), time.perf_counter() - t0))
+    import torch
+    from adam_amd import _capi
+    from adam_amd import transform as T
+    torch.zeros(1, device="cuda")
+    work = a.dir or tempfile.mkdtemp(prefix="bench_adam_")
+    os.makedirs(work, exist_ok=True)
+    src = os.path.join(work, "in.sam")
+    with open(src, "wb") as fh:
+        fh.write(data)
+    n_bytes = len(data)
+    del data
+
+    def leg(out, recal, **kw):
+        best = None
+        for i in range(1 + max(1, a.reps)):  # the first run warms
+            log("%s transform -> %s" % ("warm-up" if i == 0 else "timed", os.path.basename(out)))
+            t = time.perf_counter()
+            st = T.transform(src, out, mark_duplicates=not a.no_markdup, recalibrate=recal,
+                             partition_bytes=a.partition_bytes, overwrite=True, **kw)
+            dt = time.perf_counter() - t
+            if i and (best is None or dt < best[0]):
+                best = (dt, st)
+        if best[1]["reads"] != a.reads:
+            raise SystemExit("transformed %d reads, expected %d" % (best[1]["reads"], a.reads))
+        return best
+
+    try:
+        recal, refused = True, None
+        try:
+            bdt, bst = leg(os.path.join(work, "out.bam"), True, bam_level=a.bam_level)
+        except _capi.BQSRError as e:
+            if e.status != _capi.UNSUPPORTED:
+                raise
+            recal, refused = False, str(e)
+            log("BAM refused the recalibrated records (%s): both legs without BQSR" % e)
+            bdt, bst = leg(os.path.join(work, "out.bam"), False, bam_level=a.bam_level)
+        sdt, sst = leg(os.path.join(work, "out.sam"), recal)
+        bam_bytes = os.path.getsize(os.path.join(work, "out.bam"))
+        sam_bytes = os.path.getsize(os.path.join(work, "out.sam"))
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    b = bst["bam"]
+    peak = 8e12
+    k1 = b["text_bytes"] / (b["len_ms"] * 1e-3) if b["len_ms"] else None
+    moved2 = b["text_bytes"] + b["record_bytes"]
+    k2 = moved2 / (b["write_ms"] * 1e-3) if b["write_ms"] else None
+    print(json.dumps({
+        "metric": "transform SAM -> BAM (records encoded on the device, BGZF members by host threads) next to "
+                  "SAM -> SAM text, same input, same run; %sMarkDuplicates%s" % (
+                      "" if not a.no_markdup else "no ", ", BQSR" if recal else ", no BQSR"),
+        "reads": a.reads, "read_len": a.len, "input_bytes": n_bytes, "recalibrate": recal, "refused": refused,
+        "bam": {"seconds": bdt, "reads_per_s": a.reads / bdt, "output_bytes": bam_bytes, "level": a.bam_level,
+                "phases_s": bst.get("phases"), "record_bytes": b["record_bytes"],
+                "compress_s": b["compress_s"],
+                "compress_MB_per_s": b["record_bytes"] / b["compress_s"] / 1e6 if b["compress_s"] else None,
+                "kernels": {"len_ms": b["len_ms"], "len_bytes_read": b["text_bytes"], "len_bytes_per_s": k1,
+                            "len_share_of_8TBps": k1 / peak if k1 else None,
+                            "write_ms": b["write_ms"], "write_bytes_moved": moved2, "write_bytes_per_s": k2,
+                            "write_share_of_8TBps": k2 / peak if k2 else None}},
+        "sam": {"seconds": sdt, "reads_per_s": a.reads / sdt, "output_bytes": sam_bytes,
+                "phases_s": sst.get("phases")}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--bam-out", action="store_true",
+                    help="measure transform SAM -> BAM next to SAM -> SAM text instead of the ADAM transform")
+    ap.add_argument("--bam-level", type=int, default=6, help="--bam-out: the BGZF members' DEFLATE level")
     ap.add_argument("--reads2ref", action="store_true", help="measure adam reads2ref instead of the transform")
     ap.add_argument("--flagstat", action="store_true", help="measure adam flagstat instead of the transform")
     ap.add_argument("--kernel-reads", type=int, default=64_000_000,
@@ -399,6 +485,8 @@ def main():
         return bench_flagstat(a)
     if a.reads2ref:
         return bench_reads2ref(a)
+    if a.bam_out:
+        return bench_bam_out(a)
     t0 = time.perf_counter()
     data = synthetic_sam(a.reads, a.len)
     if a.bam:
