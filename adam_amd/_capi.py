@@ -42,6 +42,8 @@ EXPORTS = [
     "bqsr_pileup_kernel_times",
     "bqsr_sam_bam_prepare", "bqsr_sam_bam_records", "bqsr_sam_bam_header", "bqsr_bgzf_compress",
     "bqsr_bam_kernel_times",
+    "bqsr_compare_create", "bqsr_compare_destroy", "bqsr_compare_check_terms", "bqsr_compare_sam", "bqsr_compare_sides",
+    "bqsr_compare_values", "bqsr_compare_baseqs", "bqsr_compare_rows", "bqsr_compare_kernel_times",
 ]
 
 

@@ -587,6 +587,122 @@ bqsr_status bqsr_dup_set_finish(bqsr_dup_set* d, int64_t* n_duplicates);
 bqsr_status bqsr_dup_set_apply(bqsr_dup_set* d, int64_t part, bqsr_sam* s, int64_t* n_duplicates);
 void bqsr_dup_set_destroy(bqsr_dup_set* d);
 
+/* `adam compare` and `adam findreads` (adam-cli/.../cli/CompareAdam.scala,
+ * FindReads.scala over rdd/comparisons/ComparisonTraversalEngine.scala:40-59
+ * and metrics/AvailableComparisons.scala:44-177): the reads of two inputs in
+ * ReadBuckets by (recordGroupId, readName), the buckets joined by readName
+ * (two buckets of one name in different record groups both join), and the
+ * five comparisons -- 0 overmatched, 1 dupemismatch, 2 positions, 3 mapqs,
+ * 4 baseqs, DefaultComparisons' order -- aggregated into histograms with
+ * 64-bit counts.  Both inputs are resident at once, one parse per side.
+ *
+ * options (NULL: the defaults): hash_bits masks both the bucket hash and the
+ * name hash of the join down to that many bits (0 or 64: unmasked; smaller
+ * values are for tests, which make collisions common with them);
+ * utf8_1 / utf8_2: the side's QUAL bytes are UTF-8 and one Java char each (a
+ * 4-byte sequence two), else one char per byte; comparisons: bit k selects
+ * comparison k; flush_chars: the chars a workgroup of the baseqs pass takes
+ * between two flushes of its private 32-bit table (0: 2^31; at least 16384,
+ * at most BQSR_COMPARE_MAX_FLUSH_CHARS; tests lower it); baseq_groups: the
+ * workgroups of the baseqs pass (0: two per compute unit; tests lower it so
+ * that a workgroup takes several chunks and flushes in between).
+ *
+ * bqsr_compare_sam runs the selected comparisons and those the filter terms
+ * name.  A term is (comparison, op, a, b): op 0 `=`, 1 `!=`, 2 `<`, 3 `>`;
+ * overmatched takes `=` with a = 0 / 1, positions `=`, `<`, `>` with a,
+ * the point comparisons `=`, `!=` with the 32-bit point (a, b)
+ * (bqsr_compare_check_terms: BQSR_ERR_INVALID_ARG otherwise, no device
+ * call).  A joined pair is a row when every term is met by some value its
+ * comparison produced for the pair; rows are ordered by bucket 1's first
+ * read, then bucket 2's.
+ *
+ * Results: the totals, uniques and the two small histograms in `out`;
+ * positions and mapqs as (value, count) lists (bqsr_compare_values: int64
+ * values for positions, (uint32 mapq1 << 32 | uint32 mapq2) for mapqs, counts
+ * int64, n_positions / n_mapqs entries, ascending); baseqs as a 256 x 256
+ * table of int64 indexed by the two scores' low bytes (bqsr_compare_baseqs);
+ * the rows as the two buckets' allReads.head read indices (bqsr_compare_rows,
+ * n_rows entries each).  They stay with the handle until its next run.
+ *
+ * out->collision = 1 (status BQSR_OK, nothing else filled in): two
+ * (recordGroupId, readName) keys of one input share a hash -- detected by
+ * comparing every read's name with its run head's; the caller takes another
+ * path.  A collision of name hashes in the join is harmless: candidates are
+ * accepted by their bytes.
+ * BQSR_ERR_NULL_FIELD where the reference unboxes a null -- start of a
+ * singly matched read whose referenceIds compare equal (positions), mapq
+ * (mapqs), qual (baseqs): the first comparison in order that met one, side 1
+ * before side 2, the first such read of that side (out->null_comparison,
+ * null_side, null_read; bqsr_last_error_read).  A comparison neither selected
+ * nor named by a term never fails the call.
+ * BQSR_ERR_SAM_PARSE for QUAL bytes of a UTF-8 side that are no UTF-8.
+ * BQSR_ERR_UNSUPPORTED: more than BQSR_COMPARE_MAX_READS reads on a side,
+ * joined pairs, or matched read pairs; more than 16 terms. */
+#define BQSR_COMPARE_MAX_READS 4294967295ll
+#define BQSR_COMPARE_MAX_FLUSH_CHARS 2147483648ll
+typedef struct bqsr_compare bqsr_compare;
+typedef struct bqsr_compare_options {
+  int32_t hash_bits;
+  int32_t utf8_1, utf8_2;
+  uint32_t comparisons;
+  int64_t flush_chars;
+  int32_t baseq_groups;
+  int32_t reserved; /* 0 */
+} bqsr_compare_options;
+typedef struct bqsr_compare_term {
+  int32_t comparison, op;
+  int64_t a, b;
+} bqsr_compare_term;
+typedef struct bqsr_compare_result {
+  int64_t total1, unique1, total2, unique2; /* buckets, not reads */
+  int64_t n_pairs;                          /* joined pairs */
+  int64_t overmatched[2];                   /* false, true */
+  int64_t dupemismatch[4];                  /* (d1, d2) at 2 * d1 + d2 */
+  int64_t n_positions, n_mapqs, n_rows;
+  int32_t collision;
+  int32_t null_comparison, null_side; /* NULL_FIELD: the comparison, side 1 or 2 */
+  int32_t flushes;                    /* flushes of private tables in the baseqs pass */
+  int64_t null_read;
+  int64_t baseq_chars; /* chars the baseqs pass zipped */
+} bqsr_compare_result;
+bqsr_status bqsr_compare_create(bqsr_context* ctx, const bqsr_compare_options* options, bqsr_compare** out);
+void bqsr_compare_destroy(bqsr_compare* c);
+bqsr_status bqsr_compare_check_terms(const bqsr_compare_term* terms, int32_t n_terms);
+bqsr_status bqsr_compare_sam(bqsr_compare* c, const bqsr_sam* s1, const bqsr_sam* s2, const bqsr_compare_term* terms,
+                             int32_t n_terms, void* stream, bqsr_compare_result* out);
+/* The same over sides of either kind: exactly one of `sam` (a bqsr_sam_parse
+ * / bqsr_bam_parse result) and `arrow` (a bqsr_arrow_load result with the
+ * read_name and reference_id columns of its chunks given) is set.  For an
+ * Arrow side, firstOfPair and mapq are not part of bqsr_arrow_chunk: they
+ * come here, per chunk of chunk_reads[k] reads covering the load's reads, as
+ * host buffers at array offset 0 -- first_of_pair[k] a boolean bitmap and
+ * mapq[k] an int32 array, each with a validity bitmap (a NULL validity: all
+ * valid; a NULL array or list: all null).  They are read before the call
+ * returns.  A null boolean reads as false; a null readName is one name of its
+ * own, distinct from ""; referenceId, start, mapq and qual may be null (see
+ * BQSR_ERR_NULL_FIELD above); qual chars are the load's (UTF-8 -> Java chars),
+ * so utf8_1 / utf8_2 do not apply to an Arrow side. */
+typedef struct bqsr_compare_side {
+  const bqsr_sam* sam;
+  const bqsr_arrow* arrow;
+  const int64_t* chunk_reads;
+  const uint8_t* const* first_of_pair;
+  const uint8_t* const* first_of_pair_validity;
+  const int32_t* const* mapq;
+  const uint8_t* const* mapq_validity;
+  int32_t n_chunks;
+} bqsr_compare_side;
+bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* side1, const bqsr_compare_side* side2,
+                               const bqsr_compare_term* terms, int32_t n_terms, void* stream,
+                               bqsr_compare_result* out);
+bqsr_status bqsr_compare_values(const bqsr_compare* c, int32_t comparison, void* values, int64_t* counts);
+bqsr_status bqsr_compare_baseqs(const bqsr_compare* c, int64_t* table);
+bqsr_status bqsr_compare_rows(const bqsr_compare* c, uint32_t* head1, uint32_t* head2);
+/* MEASUREMENT ONLY: the device-event times of the handle's last run: the
+ * join, the scalar pass and the baseqs pass (with the UTF-8 decode pass of a
+ * side read as UTF-8), in milliseconds (tools/bench_compare.py). */
+bqsr_status bqsr_compare_kernel_times(const bqsr_compare* c, double* join_ms, double* scalar_ms, double* baseqs_ms);
+
 /* adamSave's GZIP part files (AdamRDDFunctions.scala:37-48 through
  * parquet-mr; ParquetArgs.scala:27: GZIP by default).  `in` is a Parquet file
  * written UNCOMPRESSED (Arrow's writer: schema, encodings, dictionary pages,
