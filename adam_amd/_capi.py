@@ -18,9 +18,9 @@ BQSR_OK = 0
 STAGE_RESET, STAGE_KERNEL, STAGE_FOLD, STAGE_PREP, STAGE_LUT, STAGE_NO_LUT = 1, 2, 4, 8, 16, 32
 STATUS_NAMES = ["OK", "NULL_RG", "MD_PARSE", "CIGAR_SHORT", "BAD_REVCOMP_BASE", "EMPTY_TABLE", "MISSING_KEY",
                 "QUAL_RANGE", "NULL_FIELD", "SEQ_SHORT", "CIGAR_INVALID", "INVALID_ARG", "DEVICE", "UNSUPPORTED",
-                "SAM_PARSE", "PILEUP"]
+                "SAM_PARSE", "PILEUP", "ATTRIBUTE"]
 (NULL_RG, MD_PARSE, CIGAR_SHORT, BAD_REVCOMP_BASE, EMPTY_TABLE, MISSING_KEY, QUAL_RANGE, NULL_FIELD, SEQ_SHORT,
- CIGAR_INVALID, INVALID_ARG, DEVICE, UNSUPPORTED, SAM_PARSE, PILEUP) = range(1, 16)
+ CIGAR_INVALID, INVALID_ARG, DEVICE, UNSUPPORTED, SAM_PARSE, PILEUP, ATTRIBUTE) = range(1, 17)
 
 # every symbol include/adam_bqsr.h declares
 EXPORTS = [
@@ -44,6 +44,8 @@ EXPORTS = [
     "bqsr_bam_kernel_times",
     "bqsr_compare_create", "bqsr_compare_destroy", "bqsr_compare_check_terms", "bqsr_compare_sam", "bqsr_compare_sides",
     "bqsr_compare_values", "bqsr_compare_baseqs", "bqsr_compare_rows", "bqsr_compare_kernel_times",
+    "bqsr_sam_tag_counts", "bqsr_arrow_tag_counts", "bqsr_sam_tag_values", "bqsr_arrow_tag_values",
+    "bqsr_tag_values_fetch", "bqsr_tags_kernel_times",
 ]
 
 

@@ -110,6 +110,42 @@ struct Tag {
   uint8_t type;
 };
 
+constexpr uint32_t kTagMD = (uint32_t)'D' << 8 | 'M';
+
+// The optional fields of a line -- t[p, e), p just behind the eleventh
+// field's tab, `more` = there are any -- as htsjdk keeps them: a list sorted
+// by binary tag (insertion), a repeated tag replacing the earlier value.
+// Returns the number of tags in tg[kMaxTags]; *code = kAdamOk, or what the
+// record fails with (shared by adam_record and tags.hip's tags_scan_sam).
+__device__ int collect_tags(const uint8_t* t, int64_t p, int64_t e, bool more, Tag* tg, uint32_t* code) {
+  int nt = 0;
+  *code = kAdamOk;
+  while (more) {
+    const int64_t ta = p;
+    while (p < e && t[p] != '\t') ++p;
+    const int64_t tb = p;
+    more = p < e;
+    if (more) ++p;
+    if (tb - ta < 5 || t[ta + 2] != ':' || t[ta + 4] != ':') {  // htsjdk: a two-char tag and a one-char type
+      *code = kAdamTagValue;
+      continue;
+    }
+    Tag g{(uint32_t)t[ta] | ((uint32_t)t[ta + 1] << 8), ta + 5, tb, t[ta + 3]};  // "TG:T:value"
+    int k = 0;
+    while (k < nt && tg[k].id < g.id) ++k;
+    if (k < nt && tg[k].id == g.id) {
+      tg[k] = g;
+    } else if (nt == kMaxTags) {
+      *code = kAdamTags;
+    } else {
+      for (int j = nt; j > k; --j) tg[j] = tg[j - 1];
+      tg[k] = g;
+      ++nt;
+    }
+  }
+  return nt;
+}
+
 // The attributes string: SAMRecordConverter.scala:110-121 folds
 // getAttributes -- htsjdk keeps them sorted by binary tag, a repeated tag
 // replacing the earlier value -- into `tags ::= attr` (so, descending) and
@@ -213,39 +249,15 @@ __device__ void adam_record(const AdamParams& P, int64_t r, AdamRec& x, Tag* tg)
     fb[f] = p;
     if (p < e) ++p;
   }
-  bool more = fb[10] < e;
-  // tags: htsjdk's sorted list (insertion by binary tag, a repeat replacing)
-  x.nt = 0;
-  x.code = kAdamOk;
+  x.nt = collect_tags(t, p, e, fb[10] < e, tg, &x.code);
   int64_t md_a = -1, md_b = -1, rg_a = -1, rg_b = -1;
-  while (more) {
-    const int64_t ta = p;
-    while (p < e && t[p] != '\t') ++p;
-    const int64_t tb = p;
-    more = p < e;
-    if (more) ++p;
-    if (tb - ta < 5 || t[ta + 2] != ':' || t[ta + 4] != ':') {  // htsjdk: a two-char tag and a one-char type
-      x.code = kAdamTagValue;
-      continue;
-    }
-    Tag g{(uint32_t)t[ta] | ((uint32_t)t[ta + 1] << 8), ta + 5, tb, t[ta + 3]};  // "TG:T:value"
-    if (g.id == ((uint32_t)'D' << 8 | 'M')) {
-      md_a = g.a;
-      md_b = g.b;
-    } else if (g.id == ((uint32_t)'G' << 8 | 'R')) {
-      rg_a = g.a;
-      rg_b = g.b;
-    }
-    int k = 0;
-    while (k < x.nt && tg[k].id < g.id) ++k;
-    if (k < x.nt && tg[k].id == g.id) {
-      tg[k] = g;
-    } else if (x.nt == kMaxTags) {
-      x.code = kAdamTags;
-    } else {
-      for (int j = x.nt; j > k; --j) tg[j] = tg[j - 1];
-      tg[k] = g;
-      ++x.nt;
+  for (int k = 0; k < x.nt; ++k) {
+    if (tg[k].id == kTagMD) {
+      md_a = tg[k].a;
+      md_b = tg[k].b;
+    } else if (tg[k].id == ((uint32_t)'G' << 8 | 'R')) {
+      rg_a = tg[k].a;
+      rg_b = tg[k].b;
     }
   }
   int64_t flag = 0, pos = 0, mapq = 255, pnext = 0;
@@ -442,6 +454,15 @@ void adam_quals(adamk::AdamParams& P, const AdamBufs& A, const bqsr_sam* s) {
   }
   P.dup_flags = s->dup_marked ? s->flags : nullptr;
 }
+// what a record whose tags the converter cannot convert fails with (an adamk::kAdam* code)
+bqsr_status adam_code_fail(uint32_t code, int64_t read) {
+  const char* what = code == adamk::kAdamTagType   ? "an H or B tag (the reference's attribute conversion throws)"
+                     : code == adamk::kAdamIntRange ? "an integer tag outside Int (the reference's attribute conversion fails)"
+                     : code == adamk::kAdamTagValue ? "an integer / float tag value that does not parse"
+                                                    : "more tags than supported";
+  return fail(code == adamk::kAdamTagValue ? BQSR_ERR_SAM_PARSE : BQSR_ERR_UNSUPPORTED,
+              "ADAM record of read " + std::to_string(read) + ": " + what, read);
+}
 }  // namespace
 
 extern "C" {
@@ -550,16 +571,7 @@ bqsr_status bqsr_sam_adam_prepare(bqsr_context* ctx, bqsr_sam* s, int64_t r0, in
   for (int c = 0; c < adamk::kStr && n > 0; ++c)
     HIP_TRY(hipMemcpyAsync(&tot[c], A.off + (size_t)c * (n + 1) + n, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (ew != ~0ull) {
-    const uint32_t code = (uint32_t)(ew & 0xFF);
-    const int64_t read = r0 + (int64_t)(ew >> 8);
-    const char* what = code == adamk::kAdamTagType   ? "an H or B tag (the reference's attribute conversion throws)"
-                       : code == adamk::kAdamIntRange ? "an integer tag outside Int (the reference's attribute conversion fails)"
-                       : code == adamk::kAdamTagValue ? "an integer / float tag value that does not parse"
-                                                      : "more tags than supported";
-    return fail(code == adamk::kAdamTagValue ? BQSR_ERR_SAM_PARSE : BQSR_ERR_UNSUPPORTED,
-                "ADAM record of read " + std::to_string(read) + ": " + what, read);
-  }
+  if (ew != ~0ull) return adam_code_fail((uint32_t)(ew & 0xFF), r0 + (int64_t)(ew >> 8));
   for (int c = 0; c < adamk::kStr; ++c) {
     if ((int64_t)tot[c] > INT32_MAX)
       return fail(BQSR_ERR_UNSUPPORTED, "bqsr_sam_adam_prepare: a string column above 2 GiB (take fewer records)");

@@ -205,6 +205,24 @@ class SamText:
         from .flagstat import sam_flagstat
         return sam_flagstat(self, stream)
 
+    def tag_counts(self, stream=None):
+        """`adam print_tags` over the records (bqsr_sam_tag_counts,
+        core/rdd/AdamRDDFunctions.scala:200-209): ({tag: count}, kept
+        records) of the records with FLAG 0x200 clear, every attribute
+        validated as AttributeUtils.parseAttribute does."""
+        from .print_tags import sam_tag_counts
+        return sam_tag_counts(self, stream)
+
+    def tag_values(self, tag, hash_bits: int = 64, stream=None):
+        """The distinct values of `tag` among the kept records with their
+        counts (bqsr_sam_tag_values, AdamRDDFunctions.scala:211-219):
+        {(type letter, value text): count}.  Runs ``tag_counts()`` first, which
+        validates the records.  A tag whose length is not 2 raises ValueError."""
+        from .print_tags import _tag_bytes, sam_tag_values
+        _tag_bytes(tag)
+        self.tag_counts(stream)
+        return sam_tag_values(self, tag, hash_bits, stream)
+
     def pileups(self, r0: int = 0, n: Optional[int] = None, stream=None):
         """`adam reads2ref` over reads [r0, r0 + n) (bqsr_sam_pileup_*,
         core/rdd/Reads2PileupProcessor.scala:34-197): their ADAMPileup records

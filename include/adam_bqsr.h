@@ -61,7 +61,8 @@ typedef enum bqsr_status {
   BQSR_ERR_DEVICE = 12,          /* HIP runtime failure                                                  */
   BQSR_ERR_UNSUPPORTED = 13,     /* input outside what the device path handles          */
   BQSR_ERR_SAM_PARSE = 14,       /* malformed SAM text where read_sam / SAMRecordConverter throws (adam_sam.h) */
-  BQSR_ERR_PILEUP = 15           /* reads2ref: an exception inside Reads2PileupProcessor's CIGAR walk (adam_sam.h) */
+  BQSR_ERR_PILEUP = 15,          /* reads2ref: an exception inside Reads2PileupProcessor's CIGAR walk (adam_sam.h) */
+  BQSR_ERR_ATTRIBUTE = 16        /* print_tags: what AttributeUtils.parseAttribute throws at (adam_sam.h)    */
 } bqsr_status;
 
 /* ADAMRecord boolean fields (adam-format/.../adam.avdl:28-38) and null-ness

@@ -16,6 +16,9 @@
  *             (adam-cli/.../cli/Transform.scala:73-76)
  *   flagstat: adamFlagStat (adam-core/.../rdd/FlagStat.scala:21-116), the
  *             counters `adam flagstat` prints, over a parse or Arrow buffers
+ *   print_tags: adamCharacterizeTags / adamCharacterizeTagValues
+ *             (adam-core/.../rdd/AdamRDDFunctions.scala:200-229), the tag and
+ *             tag-value counts `adam print_tags` prints
  *   reads2ref: Reads2PileupProcessor (adam-core/.../rdd/Reads2PileupProcessor.scala:34-197),
  *             the ADAMPileup rows `adam reads2ref` writes
  *
@@ -476,6 +479,94 @@ bqsr_status bqsr_flagstat_arrow(bqsr_context* ctx, const bqsr_flagstat_chunk* ch
  * failed[18], then the first NULL_FIELD read, to be preset to all ones). */
 bqsr_status bqsr_flagstat_arrow_device(bqsr_context* ctx, const bqsr_flagstat_chunk* chunk, void* counters,
                                        void* stream);
+
+/* `adam print_tags` (adam-cli/.../cli/PrintTags.scala:35-91 over
+ * adamCharacterizeTags / adamCharacterizeTagValues, adam-core/.../rdd/
+ * AdamRDDFunctions.scala:200-229, RichADAMRecord.tags, .../rich/
+ * RichADAMRecord.scala:46, and AttributeUtils, .../util/AttributeUtils.scala:
+ * 28-99): how often each two-char tag occurs among the attributes of the
+ * records with failedVendorQualityChecks false, how many such records there
+ * are, and -- a tag a call -- the distinct values of a tag with their counts.
+ *
+ * Rules (adam_amd/csrc/tags.hip):
+ *   - a record's attributes are its string split on tabs, empty pieces dropped;
+ *     every piece must match ([^:]{2}):([AifZHB]):(.*) as a whole (Java's `.`
+ *     stops at \n, \r, U+0085, U+2028, U+2029) and its value must convert: A a
+ *     first char, i Integer.valueOf, f Float.valueOf, H decimal digits only, B
+ *     comma-separated Float.valueOf (pieces with '.') / Integer.valueOf.  What
+ *     the reference throws at is BQSR_ERR_ATTRIBUTE.  Values are converted for
+ *     every attribute of every kept record, counted or not.
+ *   - a tag byte >= 0x80, or one inside an A / i / f / H / B value, is
+ *     BQSR_ERR_UNSUPPORTED (Z values may hold any bytes).
+ *   - a null failedVendorQualityChecks, or null attributes on a kept record, is
+ *     BQSR_ERR_NULL_FIELD (the reference unboxes / dereferences null).
+ *   - over a parse, a record's attributes are what SAMRecordConverter builds
+ *     (bqsr_sam_adam_*: htsjdk's tag list, a repeated tag replaced by its later
+ *     value, MD left out), and a record the converter cannot convert fails the
+ *     call with what bqsr_sam_adam_prepare returns for it -- kept or not.  At
+ *     most 48 tags a record.  Kept = FLAG 0x200 clear.
+ *   - over Arrow buffers every occurrence of a tag counts; the value of a
+ *     record under bqsr_arrow_tag_values is that of its first attribute with
+ *     the tag, over a parse that of the surviving one.
+ *   - the first failing record in input order is reported
+ *     (bqsr_last_error_read; global over the chunks).  Within a record:
+ *     conversion errors, then NULL_FIELD, then the first bad attribute in
+ *     string order.
+ * counts[b0 * 128 + b1] is the count of the tag with bytes b0, b1.  `out`
+ * holds the results of this call only; callers add them.  Integer sums,
+ * independent of launch order. */
+typedef struct bqsr_tag_counts {
+  int64_t counts[128 * 128];
+  int64_t total; /* the kept records */
+} bqsr_tag_counts;
+/* one Arrow record batch, host pointers uploaded as they are: `attributes` as
+ * Arrow string (int32 offsets [n_reads + 1], bytes, validity) and the
+ * failedVendorQualityChecks bitmap with its validity (LSB first).  Array
+ * offsets 0; attr_offsets[0] need not be 0.  Bitmaps are read to
+ * ceil(n_reads / 8) bytes.  A NULL validity is all valid; NULL attr_offsets is
+ * a column of nulls, NULL failed a column of nulls. */
+typedef struct bqsr_tags_chunk {
+  int64_t n_reads;
+  const int32_t* attr_offsets;
+  const uint8_t* attr_bytes;
+  const uint8_t* attr_validity;
+  const uint8_t* failed;
+  const uint8_t* failed_validity;
+} bqsr_tags_chunk;
+bqsr_status bqsr_sam_tag_counts(bqsr_context* ctx, const bqsr_sam* s, void* stream, bqsr_tag_counts* out);
+bqsr_status bqsr_arrow_tag_counts(bqsr_context* ctx, const bqsr_tags_chunk* chunks, int32_t n_chunks, void* stream,
+                                  bqsr_tag_counts* out);
+/* The values of tag (two bytes) as runs: (type letter of A i f Z H, count,
+ * first record in input order, value text -- the char, the decimal int,
+ * Float.toString, or the bytes of a Z / H value).  Two runs may carry the same
+ * (type, text): callers merge them, and the results of several calls.  Values
+ * are grouped by a 64-bit key (type, then the scalar or a hash of the bytes cut
+ * to hash_bits, 1..64; 64 in normal use, fewer to force collisions in tests);
+ * equal keys with different bytes make different runs.  A value of type B is
+ * BQSR_ERR_UNSUPPORTED (the reference keys the array by identity).  The values
+ * calls do not validate: run the counts call over the same records first.
+ * prepare / fetch: the sizes of the calling thread's last values call, then
+ * bqsr_tag_values_fetch into buffers of n_runs (text_offsets: n_runs + 1) and
+ * text_bytes elements. */
+typedef struct bqsr_tag_value_sizes {
+  int64_t n_runs, text_bytes;
+} bqsr_tag_value_sizes;
+typedef struct bqsr_tag_value_host {
+  uint8_t* type;
+  int64_t* count;
+  int64_t* first_read;
+  int64_t* text_offsets;
+  uint8_t* text;
+} bqsr_tag_value_host;
+bqsr_status bqsr_sam_tag_values(bqsr_context* ctx, const bqsr_sam* s, const char* tag, int32_t hash_bits,
+                                void* stream, bqsr_tag_value_sizes* out);
+bqsr_status bqsr_arrow_tag_values(bqsr_context* ctx, const bqsr_tags_chunk* chunks, int32_t n_chunks, const char* tag,
+                                  int32_t hash_bits, void* stream, bqsr_tag_value_sizes* out);
+bqsr_status bqsr_tag_values_fetch(const bqsr_tag_value_host* dst);
+/* MEASUREMENT ONLY, not part of the stable interface: device-event times of
+ * the calling thread's last counts call (the scan kernels) and last values
+ * call (the value kernels with their sorts and scans), in ms */
+bqsr_status bqsr_tags_kernel_times(double* scan_ms, double* values_ms);
 
 /* `adam reads2ref` (adam-cli/.../cli/Reads2Ref.scala:53-75 over
  * Reads2PileupProcessor.readToPileups, adam-core/.../rdd/Reads2PileupProcessor.

@@ -43,6 +43,22 @@ reported and both legs rerun without BQSR).  Reads/s and the phase split of
 both legs, the two encoder kernels by device events with the bytes they move
 (pass 1 reads the record text; pass 2 reads it again and writes the records)
 as a fraction of 8 TB/s, and the compressor's MB/s of stream.  One JSON line.
+
+    python tools/bench_adam.py --print-tags [--reads 2000000] [--variant-lib LIB.so]
+
+--print-tags measures `adam print_tags` (adam_amd/print_tags.py) over the same
+synthetic reads as SAM text with aligner-like fields appended to every line
+(NM:i, AS:i, XS:i, and XA:Z on about 5 % of the lines; samgen alone writes MD
+and RG): once each, in this process, print_tags without -count, print_tags
+-count NM,XA, flagstat on the same file (the yardstick: both are one parse
+plus one pass over each record) and the single-threaded Python restatement
+(tests/_tags_ref.py) on the first 200 000 reads; end-to-end seconds with the
+phase split, the scan kernel's and the value kernels' device-event ms and the
+bytes of record text the scan covers.  --variant-lib names a build of the
+library with the other histogram form (tools/variants/tags_hist_plain.diff):
+the scan kernel alone is then timed (best of --reps, device events, one parse)
+by a child process per library, three times each, alternating, and both
+forms' ms are reported.  One JSON line.
 """
 import argparse
 import json
@@ -279,6 +295,130 @@ def bench_flagstat(a):
     print(json.dumps(res))
 
 
+def _tagged_sam(sam: bytes) -> bytes:
+    """aligner-like optional fields appended to every record line"""
+    out = []
+    i = 0
+    for l in sam.split(b"\n"):
+        if not l:
+            continue
+        if l[:1] != b"@":
+            h = (i * 2654435761) & 0xFFFFFFFF
+            l += b"\tNM:i:%d\tAS:i:%d\tXS:i:%d" % (h % 7, 100 - h % 31, (h >> 8) % 90)
+            if h % 20 == 0:
+                l += b"\tXA:Z:chr%d,+%d,100M,%d;" % (1 + h % 22, 1 + (h >> 4) % 100000, h % 4)
+            i += 1
+        out.append(l)
+    return b"\n".join(out) + b"\n"
+
+
+def _scan_only(path, reps):
+    """the scan kernel alone over one parse of `path`: best device-event ms of reps calls"""
+    import torch
+    from adam_amd import bqsr
+    from adam_amd import print_tags as PT
+    from adam_amd.sam import SamText
+    torch.zeros(1, device="cuda")
+    with open(path, "rb") as fh:
+        st = SamText(fh.read(), bqsr.Context.get(0))
+    try:
+        st.tag_counts()
+        best = None
+        for _ in range(reps):
+            st.tag_counts()
+            ms = PT.kernel_times()[0]
+            best = ms if best is None else min(best, ms)
+    finally:
+        st.close()
+    return best
+
+
+def bench_print_tags(a):
+    """the --print-tags measurements (see the module doc)"""
+    import subprocess
+    if a.scan_only:  # the child of a --variant-lib run
+        print(json.dumps({"scan_ms": _scan_only(a.scan_only, max(3, a.reps))}))
+        return
+    import torch
+    from adam_amd import _capi, bqsr
+    from adam_amd import flagstat as FS
+    from adam_amd import print_tags as PT
+    from adam_amd import transform as T
+    t0 = time.perf_counter()
+    sam = _tagged_sam(synthetic_sam(a.reads, a.len))
+    header = T.sam_partitions(sam, len(sam))[0]
+    log("generated %d bytes of SAM in %.1f s" % (len(sam), time.perf_counter() - t0))
+    work = a.dir or tempfile.mkdtemp(prefix="bench_print_tags_")
+    os.makedirs(work, exist_ok=True)
+    res = {"metric": "adam print_tags at --reads: end-to-end seconds (host clock, one run each after a warm-up on a "
+                     "small file), kernels by device events", "reads": a.reads, "read_len": a.len,
+           "input_bytes": len(sam), "record_text_bytes": len(sam) - len(header)}
+    try:
+        src, small = os.path.join(work, "in.sam"), os.path.join(work, "small.sam")
+        with open(src, "wb") as fh:
+            fh.write(sam)
+        n_small = min(a.reads, 200_000)
+        cut = len(header)
+        for _ in range(n_small):
+            cut = sam.index(b"\n", cut) + 1
+        with open(small, "wb") as fh:
+            fh.write(sam[:cut])
+        del sam
+        torch.zeros(1, device="cuda")
+        bqsr.Context.get(0)
+        # warm-up: the context, the kernels' code objects, pyarrow
+        PT._run(small, None, ("NM", "XA"), 0, a.partition_bytes)
+        FS._flagstat(small, 0, a.partition_bytes)
+
+        def run(f):
+            t = time.perf_counter()
+            r = f()
+            return time.perf_counter() - t, r
+        s1, r1 = run(lambda: PT._run(src, None, (), 0, a.partition_bytes))
+        s2, r2 = run(lambda: PT._run(src, None, ("NM", "XA"), 0, a.partition_bytes))
+        s3, r3 = run(lambda: FS._flagstat(src, 0, a.partition_bytes))
+        if r1[3] != a.reads or r1[1] != r2[1] or sum(r2[2]["NM"].values()) != a.reads:
+            raise SystemExit("print_tags counted %r of %d reads" % (r1[3], a.reads))
+        res["print_tags"] = {"seconds": s1, "phases_s": r1[4]["phases"], "scan_kernel_ms": r1[4]["kernel_ms"]["scan"]}
+        res["print_tags_count_NM_XA"] = {"seconds": s2, "phases_s": r2[4]["phases"],
+                                         "scan_kernel_ms": r2[4]["kernel_ms"]["scan"],
+                                         "value_kernels_ms": r2[4]["kernel_ms"]["values"],
+                                         "distinct_values": {t: len(v) for t, v in r2[2].items()}}
+        res["flagstat"] = {"seconds": s3, "phases_s": r3[2]["phases"]}
+        res["print_tags_over_flagstat"] = s1 / s3
+        res["tags"] = r1[1]
+        # the restatement, single-threaded, on the first 200 000 reads
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from _adam_ref import convert_sam
+        from _tags_ref import characterize_tags, sam_records
+        with open(small, "rb") as fh:
+            text = fh.read()
+        s4, want = run(lambda: characterize_tags(sam_records(convert_sam(text))))
+        got = PT._run(small, None, (), 0, a.partition_bytes)
+        if (got[1], got[3]) != want:
+            raise SystemExit("print_tags differs from the restatement on %d reads" % n_small)
+        res["python_restatement"] = {"reads": n_small, "seconds": s4}
+        log("print_tags %.3f s, -count NM,XA %.3f s, flagstat %.3f s, restatement (%d reads) %.1f s"
+            % (s1, s2, s3, n_small, s4))
+        if a.variant_lib:  # the scan kernel alone, a child process per library, the two alternating
+            libs = (("leader_loop", _capi.LIB_PATH), ("plain_lds_atomics", os.path.abspath(a.variant_lib)))
+            runs = {name: [] for name, _ in libs}
+            for _ in range(3):
+                for name, lib in libs:
+                    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--print-tags", "--scan-only",
+                                          src, "--reps", str(max(3, a.reps))],
+                                         env=dict(os.environ, ADAM_BQSR_LIB=lib), check=True, capture_output=True,
+                                         text=True).stdout
+                    runs[name].append(json.loads(out.strip().splitlines()[-1])["scan_ms"])
+                    log("%s: scan %.4f ms" % (name, runs[name][-1]))
+            forms = {name: {"best_ms": min(v), "runs_ms": v} for name, v in runs.items()}
+            res["histogram_forms_scan_ms"] = forms
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps(res))
+
+
 def bench_reads2ref(a):
     """the --reads2ref measurements (see the module doc)"""
     import ctypes
@@ -467,6 +607,10 @@ def main():
     ap.add_argument("--bam-level", type=int, default=6, help="--bam-out: the BGZF members' DEFLATE level")
     ap.add_argument("--reads2ref", action="store_true", help="measure adam reads2ref instead of the transform")
     ap.add_argument("--flagstat", action="store_true", help="measure adam flagstat instead of the transform")
+    ap.add_argument("--print-tags", action="store_true", help="measure adam print_tags instead of the transform")
+    ap.add_argument("--variant-lib", default=None,
+                    help="--print-tags: a library built with the other histogram form, for the A/B of the scan kernel")
+    ap.add_argument("--scan-only", default=None, metavar="SAM", help=argparse.SUPPRESS)
     ap.add_argument("--kernel-reads", type=int, default=64_000_000,
                     help="--flagstat: random reads for the Arrow-form kernel alone")
     ap.add_argument("--reads", type=int, default=2_000_000)
@@ -483,6 +627,8 @@ def main():
     a = ap.parse_args()
     if a.flagstat:
         return bench_flagstat(a)
+    if a.print_tags:
+        return bench_print_tags(a)
     if a.reads2ref:
         return bench_reads2ref(a)
     if a.bam_out:
