@@ -351,8 +351,7 @@ struct bqsr_batch {
   ReadInfo* d_info = nullptr;
   uint64_t* d_sbits = nullptr;  // slot bitmap (PrepParams::sbits)
   uint32_t* d_work = nullptr;   // prep worklist (PrepParams::work), count at d_work[n_reads]
-  uint64_t* d_bnd = nullptr;    // prep pass 1 wavefront-boundary shares (PrepParams::bnd)
-  int64_t sbits_words = 0;      // even: the apply kernel clears it 16 B at a time
+  int64_t sbits_words = 0;      // its size in u64 words, the passes' read-ahead included (finish_batch)
   bool err_fresh = false;     // bqsr_job_reset_async reset the error words since the last prep
   bool prepped = false;
   const bqsr_sites* prep_sites = nullptr;
@@ -537,7 +536,7 @@ bqsr_status bqsr_context_create(int device, bqsr_context** out) {
   if (e == hipSuccess) e = hipMemcpy(c->d_qbt, buckets().thr.data(), kQbN * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(c->d_qbq, buckets().q.data(), kQbN * sizeof(int16_t), hipMemcpyHostToDevice);
   for (const void* f : {(const void*)bqsr_apply_kernel, (const void*)bqsr_observe_chunks,
-                        (const void*)bqsr_observe_lean<true>})
+                        (const void*)bqsr_observe_lean<true, false>, (const void*)bqsr_observe_lean<true, true>})
     if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)bqsr_fold_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_hist_lds());
@@ -690,10 +689,13 @@ bqsr_status finish_batch(bqsr_batch* b, int64_t max_slot_len) {
   }
   if ((st = dalloc(b->allocs, &b->d_err, kErrWords)) != BQSR_OK) return st;
   if ((st = dalloc(b->allocs, &b->d_info, (size_t)std::max<int64_t>(1, n))) != BQSR_OK) return st;
-  b->sbits_words = (b->rd.n_slots / 32 + 5) & ~(int64_t)1;  // the per-base passes read 3 words from any slot's word
+  // the slot bitmap, 2 bits a slot (PrepParams::sbits), never filled: prep
+  // writes every word a pass loads.  Aligned slots: a u32 word per 16-slot
+  // chunk, and bqsr_observe_lean loads 8 words from any chunk's; else a u64
+  // word per 32 slots, the per-base passes reading 5 words from any slot's.
+  b->sbits_words = b->rd.slots_aligned ? (b->rd.n_slots / 16 + 8 + 1) / 2 : b->rd.n_slots / 32 + 5;
   if ((st = dalloc(b->allocs, &b->d_sbits, (size_t)b->sbits_words)) != BQSR_OK) return st;
   if ((st = dalloc(b->allocs, &b->d_em, 2)) != BQSR_OK) return st;
-  if ((st = dalloc(b->allocs, &b->d_bnd, (size_t)2 * (size_t)(n / 64 + kPrepChunk / 64 + 1))) != BQSR_OK) return st;
   if ((st = dalloc(b->allocs, &b->d_work,
                    (size_t)(n + kPrepChunk) + (size_t)std::max<int64_t>(n / kPrepChunk + 1, kMaxFoldBlocks))) != BQSR_OK)
     return st;
@@ -1422,13 +1424,14 @@ bqsr_status launch_prep(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* site
     PrepParams P{};
     P.rd = b->rd;
     if (sites) P.sites = sites->dev();
-    // with known sites and reads of <= 128 bases, pass 1 stores every bitmap
-    // word (no zeroing pass, no read-modify-write atomics: cfg3 prep 3.0 ->
-    // 2.2 ms); without sites the few mismatch bits as atomics onto a zeroed
-    // bitmap cost less (cfg2: 0.25 + 0.03 ms against 0.30)
-    P.store_words = b->dims.max_len <= 128 && P.sites.n_contigs > 0;
-    P.bnd = b->d_bnd;
-    // (the atomic form's workgroups clear their own slots' words first: no fill)
+    // the bitmap's words (prep_fast's forms).  Aligned slots, every batch the
+    // packers here make: u32 words private to a read, nothing cleared.  With
+    // known sites and reads of <= 128 bases pass 1 stores the words of every
+    // usable read; otherwise only the reads that have a bit store theirs
+    // (cfg2: about one in seven).  A device batch without aligned slots
+    // keeps u64 words, cleared by the workgroups, the bits OR-ed atomically.
+    const bool w32 = b->rd.slots_aligned;
+    const bool store = w32 && b->dims.max_len <= 128 && P.sites.n_contigs > 0;
     P.info = b->d_info;
     P.sbits = b->d_sbits;
     P.err = b->d_err;
@@ -1437,11 +1440,13 @@ bqsr_status launch_prep(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* site
     // pass 1: the common reads in lock step; the rest, one thread each (in
     // pass 1's workgroups, or pass 2 after word stores)
     const int64_t blocks = (b->rd.n_reads + kPrepChunk - 1) / kPrepChunk;
-    if (P.store_words) {
-      hipLaunchKernelGGL(bqsr_prep_kernel<true>, dim3((unsigned)blocks), dim3(kPrepThreads), 0, s, P);
+    if (store) {
+      hipLaunchKernelGGL(bqsr_prep_kernel<kPrepStore>, dim3((unsigned)blocks), dim3(kPrepThreads), 0, s, P);
       hipLaunchKernelGGL(bqsr_prep_complex, dim3((unsigned)blocks), dim3(kComplexThreads), 0, s, P);
-    } else {  // the listed reads finished by the same workgroups
-      hipLaunchKernelGGL(bqsr_prep_kernel<false>, dim3((unsigned)blocks), dim3(kPrepThreads), 0, s, P);
+    } else if (w32) {  // the listed reads finished by the same workgroups
+      hipLaunchKernelGGL(bqsr_prep_kernel<kPrepW32>, dim3((unsigned)blocks), dim3(kPrepThreads), 0, s, P);
+    } else {
+      hipLaunchKernelGGL(bqsr_prep_kernel<kPrepU64>, dim3((unsigned)blocks), dim3(kPrepThreads), 0, s, P);
     }
     HIP_TRY(hipGetLastError());
     if (b->bucketed && !b->perm_static) {  // counting sort of the reads by read group
@@ -1550,7 +1555,10 @@ bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_site
     P.n_blocks = lean ? b->n_blocks : b->pass_blocks();  // (fronts: a chunk-walk workgroup per piece)
     const size_t lds = lean ? lean_lds(P.w.qw, P.orow, P.wcells) : observe_lds(P.w.qw, P.wcells, true);
     if (lean) {
-      hipLaunchKernelGGL((bqsr_observe_lean<true>), dim3(P.n_blocks), dim3(kBlockThreads), lds, s, P);
+      if (P.rd.slots_aligned)
+        hipLaunchKernelGGL((bqsr_observe_lean<true, true>), dim3(P.n_blocks), dim3(kBlockThreads), lds, s, P);
+      else
+        hipLaunchKernelGGL((bqsr_observe_lean<true, false>), dim3(P.n_blocks), dim3(kBlockThreads), lds, s, P);
     } else {
       hipLaunchKernelGGL(bqsr_observe_chunks, dim3(P.n_blocks), dim3(kBlockThreads), lds, s, P);
     }

@@ -169,15 +169,23 @@ __host__ __device__ inline uint64_t slot_span(uint64_t lq, uint64_t ls) {
   return (sl + 15) & ~(uint64_t)15;
 }
 
-// Slot bitmap: u64 word i covers base slots 32i .. 32i+31 of the batch, bit j
-// of the low half = slot 32i+j is masked, of the high half = it mismatches.
+// Slot bitmap, 2 bits per base slot (masked, mismatch), in one of two word
+// formats:
+//  * ReadsDev::slots_aligned (every batch the packers make): u32 word i covers
+//    the 16-slot chunk 16i .. 16i+15, bit j of the low half = slot 16i+j is
+//    masked, of the high half = it mismatches.  Reads start on chunks, so a
+//    word belongs to one read: prep writes all the words of a read that has
+//    bits (zeros included) with plain stores and none of a kInfoNoBits read,
+//    whose words no pass loads.  Nothing is cleared and nothing carries over
+//    from one job to the next.
+//  * otherwise: u64 word i covers slots 32i .. 32i+31, masked bits in the low
+//    half, mismatch bits in the high half; neighbouring reads share words, so
+//    each prep workgroup clears its reads' words and ORs bits in atomically.
 struct PrepParams {
   ReadsDev rd;
   SitesDev sites;
   ReadInfo* info;      // [n_reads]
-  uint64_t* sbits;     // [n_slots / 32 + 4]: each workgroup clears its reads' words first, or (store_words) pass 1 writes them whole
-  int32_t store_words; // pass 1 stores every sbits word (reads of <= 128 bases), no zeroing, no atomics
-  uint64_t* bnd;       // store_words: per wavefront of pass 1 [bits, word] its first read's share of the word the previous wavefront stored
+  uint64_t* sbits;     // the bitmap: u32 [n_slots / 16 + 8] (aligned slots) or u64 [n_slots / 32 + 5]
   unsigned long long* err;  // error words
   uint32_t* work;      // [n_reads] reads bqsr_prep_kernel left to bqsr_prep_complex, per workgroup segment
   uint32_t* n_work;    // [workgroups] their count per segment

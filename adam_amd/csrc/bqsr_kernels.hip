@@ -124,11 +124,26 @@ __device__ int refpos_to_offset(CigPtr cig, int ncig, int64_t unclipped, int64_t
   return -1;
 }
 
-// set bits [lo, hi) (absolute base slots) of the batch's slot bitmap: word i
-// holds slots 32i..32i+31 at bit `half` (0 masked, 32 mismatch).  Two reads
+// set bits [lo, hi) (absolute base slots) of the batch's slot bitmap, `half`
+// 0 masked, 32 mismatch (PrepParams::sbits: the two word formats).
+// kW32 false: u64 word i holds slots 32i..32i+31 at bit `half`.  Two reads
 // can share a word, hence the atomics (few per read: most reads have no
-// masked base and a handful of mismatches).
+// masked base and a handful of mismatches) onto words cleared before.
+// kW32: u32 word i holds slots 16i..16i+15 at bit `half` / 2.  The word is
+// the calling thread's read's alone; the thread has written it before
+// (own_words_clear, store_chunk_words) and ORs into what it wrote.
+template <bool kW32>
 __device__ void set_sbits(uint64_t* sb, uint64_t lo, uint64_t hi, int half) {
+  if (kW32) {
+    uint32_t* sw = (uint32_t*)sb;
+    while (lo < hi) {
+      const int b = (int)(lo & 15);
+      const int n = (int)min((uint64_t)(16 - b), hi - lo);
+      atomicOr(&sw[lo >> 4], (((1u << n) - 1u) << b) << (half >> 1));
+      lo += (uint64_t)n;
+    }
+    return;
+  }
   while (lo < hi) {
     const uint64_t i = lo >> 5;
     const int b = (int)(lo & 31);
@@ -137,6 +152,17 @@ __device__ void set_sbits(uint64_t* sb, uint64_t lo, uint64_t hi, int half) {
     atomicOr((unsigned long long*)&sb[i], (unsigned long long)m << half);
     lo += (uint64_t)n;
   }
+}
+// (u32 words) A thread's plain stores to its read's words complete before the
+// atomic ORs it then issues to the same words.
+__device__ __forceinline__ void own_words_order() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
+// (u32 words) The words of a read of lq bases at slot rs zeroed by the thread
+// about to OR the read's bits into them: whatever an earlier job left there
+// goes, and no other read's bits are near.
+__device__ __forceinline__ void own_words_clear(uint64_t* sb, uint64_t rs, int lq) {
+  uint32_t* sw = (uint32_t*)sb + (rs >> 4);
+  for (int k = 0; 16 * k < lq; ++k) sw[k] = 0u;
+  own_words_order();
 }
 
 // ---------------------------------------------------------------- prep -----
@@ -224,10 +250,11 @@ constexpr int kPrepCig = 4, kPrepCigStride = 5;
 constexpr int kPrepMd = 32, kPrepMdStride = 9;
 constexpr int kPrepChunk = 2048;  // reads per workgroup of bqsr_prep_kernel (8 per thread)
 
-template <class CigPtr, class MdPtr>
+template <bool kW32, class CigPtr, class MdPtr>
 __device__ void prep_one_rest(const PrepParams& P, int64_t r, const ReadMeta& m, const ReadAlign& a, ReadInfo inf,
                               int st, int en, bool usable, CigPtr cig, MdPtr md);
 
+template <bool kW32>
 __device__ __forceinline__ void prep_one(const PrepParams& P, int64_t r, uint32_t* s_cig, uint32_t* s_md) {  // (inline: see bqsr_prep_kernel)
   const ReadMeta m = P.rd.meta[r];
   const ReadAlign a = P.rd.align[r];  // issued with the meta load: one round trip for both
@@ -306,15 +333,16 @@ __device__ __forceinline__ void prep_one(const PrepParams& P, int64_t r, uint32_
     lm[5] = m1.y;
     lm[6] = m1.z;
     lm[7] = m1.w;
-    prep_one_rest(P, r, m, a, inf, st, en, usable, (LdsCW)lc, (LdsCB)lm);
+    prep_one_rest<kW32>(P, r, m, a, inf, st, en, usable, (LdsCW)lc, (LdsCB)lm);
   } else {
-    prep_one_rest(P, r, m, a, inf, st, en, usable, gcig, gmd);
+    prep_one_rest<kW32>(P, r, m, a, inf, st, en, usable, gcig, gmd);
   }
 }
 
 // prep_one after its checks of the record: the CIGAR / MD walks, errors, the
-// ReadInfo and the bits (cig / md: LDS-typed or global pointers)
-template <class CigPtr, class MdPtr>
+// ReadInfo and the bits (cig / md: LDS-typed or global pointers).  kW32: the
+// thread zeroes its read's words, then ORs into them.
+template <bool kW32, class CigPtr, class MdPtr>
 __device__ void prep_one_rest(const PrepParams& P, int64_t r, const ReadMeta& m, const ReadAlign& a, ReadInfo inf,
                               int st, int en, bool usable, CigPtr cig, MdPtr md) {
   const uint16_t f = m.flags;
@@ -386,6 +414,7 @@ __device__ void prep_one_rest(const PrepParams& P, int64_t r, const ReadMeta& m,
   // ---- masked / mismatch bits over [st, en) ----
   uint64_t* bw = P.sbits;
   const uint64_t rs = m.slot;
+  if (kW32) own_words_clear(bw, rs, m.lq);
   {
     int ro = 0;
     int64_t pos = unclipped;
@@ -398,14 +427,14 @@ __device__ void prep_one_rest(const PrepParams& P, int64_t r, const ReadMeta& m,
           int64_t w0 = (int64_t)ro + (start - pos), w1 = (int64_t)ro + (ref_end - pos);
           int a0 = (int)min(max(w0, (int64_t)lo), (int64_t)hi);
           int a1 = (int)min(max(w1, (int64_t)lo), (int64_t)hi);
-          set_sbits(bw, rs + (uint64_t)(lo), rs + (uint64_t)(a0), 0);
-          set_sbits(bw, rs + (uint64_t)(max(a1, a0)), rs + (uint64_t)(hi), 0);
+          set_sbits<kW32>(bw, rs + (uint64_t)(lo), rs + (uint64_t)(a0), 0);
+          set_sbits<kW32>(bw, rs + (uint64_t)(max(a1, a0)), rs + (uint64_t)(hi), 0);
         }
         ro += len;
         pos += len;
       } else if (op == BQSR_CIGAR_I) {  // insertion: refPos None
         int lo = max(ro, st), hi = min(ro + (int)len, en);
-        set_sbits(bw, rs + (uint64_t)(lo), rs + (uint64_t)(max(lo, hi)), 0);
+        set_sbits<kW32>(bw, rs + (uint64_t)(lo), rs + (uint64_t)(max(lo, hi)), 0);
         ro += len;
       } else if (op != BQSR_CIGAR_H) {
         pos += len;
@@ -418,7 +447,7 @@ __device__ void prep_one_rest(const PrepParams& P, int64_t r, const ReadMeta& m,
     int64_t p = start + prel;
     if (p >= ref_end) return;
     int o = refpos_to_offset(cig, ncig, unclipped, p);
-    if (o >= st && o < en) set_sbits(bw, rs + (uint64_t)(o), rs + (uint64_t)(o + 1), 32);
+    if (o >= st && o < en) set_sbits<kW32>(bw, rs + (uint64_t)(o), rs + (uint64_t)(o + 1), 32);
   });
   // positions past the MD span but before `end` are not matches either
   if (start + md_total < ref_end) {
@@ -431,7 +460,7 @@ __device__ void prep_one_rest(const PrepParams& P, int64_t r, const ReadMeta& m,
         int64_t p0 = max(pos, t0), p1 = min(pos + (int64_t)len, ref_end);
         if (p0 < p1) {
           int lo = max(ro + (int)(p0 - pos), st), hi = min(ro + (int)(p1 - pos), en);
-          if (lo < hi) set_sbits(bw, rs + (uint64_t)(lo), rs + (uint64_t)(hi), 32);
+          if (lo < hi) set_sbits<kW32>(bw, rs + (uint64_t)(lo), rs + (uint64_t)(hi), 32);
         }
         ro += len;
         pos += len;
@@ -461,7 +490,7 @@ __device__ void prep_one_rest(const PrepParams& P, int64_t r, const ReadMeta& m,
       while (j < ns && sp[j] < lo_p) ++j;
       for (; j < ns && sp[j] < hi_p; ++j) {
         int o = refpos_to_offset(cig, ncig, unclipped, sp[j]);
-        if (o >= st && o < en) set_sbits(bw, rs + (uint64_t)(o), rs + (uint64_t)(o + 1), 0);
+        if (o >= st && o < en) set_sbits<kW32>(bw, rs + (uint64_t)(o), rs + (uint64_t)(o + 1), 0);
       }
     }
   }
@@ -471,6 +500,7 @@ __device__ void prep_one_rest(const PrepParams& P, int64_t r, const ReadMeta& m,
 // unclipped + o for every offset (CIGAR [S]M[S]): mask the trimmed offsets
 // [st, en) holding a site (SnpTable.isMaskedAtReadOffset, raw VCF POS vs
 // 0-based refPos, Q7).
+template <bool kW32>
 __device__ void mask_sites_linear(const PrepParams& P, int32_t contig, int64_t unclipped, int st, int en,
                                   uint64_t rs) {
   if (contig < 0 || contig >= P.sites.n_contigs) return;
@@ -486,7 +516,7 @@ __device__ void mask_sites_linear(const PrepParams& P, int32_t contig, int64_t u
   while (j < ns && sp[j] < lo_p) ++j;
   for (; j < ns && sp[j] < hi_p; ++j) {
     const uint64_t o = (uint64_t)(sp[j] - unclipped);
-    set_sbits(P.sbits, rs + o, rs + o + 1, 0);
+    set_sbits<kW32>(P.sbits, rs + o, rs + o + 1, 0);
   }
 }
 
@@ -494,6 +524,7 @@ __device__ void mask_sites_linear(const PrepParams& P, int32_t contig, int64_t u
 // funnel shift of two bitmap words (the next step reuses the second), an
 // atomic OR per sbits word only where a site falls.  False when the contig
 // has no bitmap.
+template <bool kW32>
 __device__ __forceinline__ bool mask_sites_bitmap(const PrepParams& P, int32_t contig, int64_t unclipped, int lq,
                                                   uint64_t rs) {
   const SitesDev& S = P.sites;
@@ -511,6 +542,15 @@ __device__ __forceinline__ bool mask_sites_bitmap(const PrepParams& P, int32_t c
     lo = hi;
     if (lq - o < 64) m &= (1ull << (lq - o)) - 1ull;
     if (!m) continue;
+    if (kW32) {  // rs and o are multiples of 16: four of the read's own words
+      uint32_t* sw = (uint32_t*)P.sbits + ((rs + (uint64_t)o) >> 4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t p = (uint32_t)(m >> (16 * k)) & 0xFFFFu;
+        if (p) atomicOr(sw + k, p);
+      }
+      continue;
+    }
     // slots s .. s + 63 span sbits words s >> 5 .. (s >> 5) + 2 (masked half: the low 32 bits)
     const uint64_t s = rs + (uint64_t)o;
     const uint32_t sb = (uint32_t)(s & 31);
@@ -528,15 +568,16 @@ constexpr int kFastCigOps = 5;  // CIGAR elements of a common read: S? M ((I|D) 
 struct PrepRec {
   ReadMeta m;
   ReadAlign a;
-  uint64_t nslot;  // store_words, last lane of a wavefront: the next read's slot (n_slots past the batch)
 };
 struct PrepCols {
   uint4 c4, md4;
   uint32_t c5;  // the fifth CIGAR word
 };
-// A read's sbits words in registers (prep_fast, reads whose bits fit in
-// kAccWords words): bit b of the accumulator = slot (rs & ~31) + b; static
-// indices only (a dynamic one would put the array in scratch).
+// A read's bits in registers (prep_fast, reads whose bits fit in kAccWords
+// u64 words, masked bits in the low halves, mismatch bits in the high ones):
+// bit b of the accumulator = slot (rs & ~31) + b for the u64 bitmap words,
+// which it then matches, or slot rs + b for the u32 ones (store_chunk_words);
+// static indices only (a dynamic one would put the array in scratch).
 constexpr int kAccWords = 5;
 __device__ __forceinline__ void acc_range(uint64_t acc[kAccWords], uint32_t lo, uint32_t hi, int half) {
 #pragma unroll
@@ -551,6 +592,47 @@ __device__ __forceinline__ void acc_bit(uint64_t acc[kAccWords], uint32_t b, int
 #pragma unroll
   for (int j = 0; j < kAccWords; ++j) acc[j] |= (b >> 5) == (uint32_t)j ? 1ull << ((b & 31) + half) : 0ull;
 }
+// (u32 words) The accumulator of a read of lq <= 32 kAccWords bases at slot
+// rs, offset 0 at bit 0, out as the read's words: every one of them, zeros
+// included, by plain stores (4-B aligned; a pair of words per store).
+struct __attribute__((packed, aligned(4))) WordPair {
+  uint32_t a, b;
+};
+__device__ __forceinline__ void store_chunk_words(uint64_t* sb, uint64_t rs, int lq, const uint64_t acc[kAccWords]) {
+  uint32_t* sw = (uint32_t*)sb + (rs >> 4);
+#pragma unroll
+  for (int j = 0; j < kAccWords; ++j) {
+    const uint32_t lo = (uint32_t)acc[j], hi = (uint32_t)(acc[j] >> 32);
+    const uint32_t w0 = (lo & 0xFFFFu) | (hi << 16), w1 = (lo >> 16) | (hi & 0xFFFF0000u);
+    if (32 * j + 16 < lq)
+      *(WordPair*)(sw + 2 * j) = WordPair{w0, w1};
+    else if (32 * j < lq)
+      sw[2 * j] = w0;
+  }
+}
+
+// (u32 words) The lean accumulator of a read of lq <= 64 N bases without known
+// sites (N = 2, or 4 for the longer reads): its masked bits m[N] and mismatch bits x[N], offset o at bit o & 63
+// of word o >> 6 (a range costs two 64-bit masks, a letter one shift: the five
+// mixed words above cost 2-3 times the VALU, which prep's lock-step loop pays
+// on every wavefront, profiles/r07w_bitmap_words_ab.txt).
+__device__ __forceinline__ uint64_t bits_below(int n) { return n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << n) - 1ull; }
+__device__ __forceinline__ uint64_t bits_range(int lo, int hi) { return bits_below(hi) & ~bits_below(lo); }
+template <int N>
+__device__ __forceinline__ void store_chunk_words_lean(uint64_t* sb, uint64_t rs, int lq, const uint64_t m[N],
+                                                       const uint64_t x[N]) {
+  uint32_t* sw = (uint32_t*)sb + (rs >> 4);
+#pragma unroll
+  for (int j = 0; j < 2 * N; ++j) {  // 32 slots: two words
+    const uint32_t lo = (uint32_t)(m[j >> 1] >> (32 * (j & 1))), hi = (uint32_t)(x[j >> 1] >> (32 * (j & 1)));
+    const uint32_t w0 = (lo & 0xFFFFu) | (hi << 16), w1 = (lo >> 16) | (hi & 0xFFFF0000u);
+    if (32 * j + 16 < lq)
+      *(WordPair*)(sw + 2 * j) = WordPair{w0, w1};
+    else if (32 * j < lq)
+      sw[2 * j] = w0;
+  }
+}
+
 // mask_sites_bitmap into the accumulator (offsets 0 .. lq-1 at bits r0 + o)
 __device__ __forceinline__ bool sites_bitmap_acc(const SitesDev& S, int32_t contig, int64_t unclipped, int lq,
                                                  uint32_t r0, uint64_t acc[kAccWords]) {
@@ -610,8 +692,6 @@ __device__ __forceinline__ PrepRec prep_rec(const PrepParams& P, int64_t r) {
     x.m = P.rd.meta[r];
     x.a = P.rd.align[r];
   }
-  if (P.store_words && (threadIdx.x & 63) == 63)
-    x.nslot = r + 1 < P.rd.n_reads ? P.rd.meta[r + 1].slot : (uint64_t)P.rd.n_slots;
   return x;
 }
 // (the columns have 32 B of padding; only reads prep_fast may take load)
@@ -851,9 +931,51 @@ constexpr uint16_t kFastNeed = BQSR_F_HAS_QUAL | BQSR_F_HAS_RG | BQSR_F_HAS_SEQ 
 // inside [st, en) are listed -- a read ending in a Q2 run has every trimmed
 // base in its MD as a mismatch (cfg2's listed reads: ~10 of 2048, prep_one
 // 66 us of the launch)
-template <bool kStore, bool kLong = false>
+// The words of a common read without known sites (its MD letters listed),
+// gathered in the lean accumulator and stored
+template <int N>
+__device__ __forceinline__ void lean_words(uint64_t* sb, uint64_t rs, const FastCig& c, const FastMd& md, int st,
+                                           int en) {
+  uint64_t am[N], ax[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) am[j] = ax[j] = 0ull;
+  FastMd me = md;
+  me.lst = 0;  // (its letters: the loop below)
+  fast_emit(c, me, st, en, [&](int lo, int hi, int half) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const uint64_t b = bits_range(lo - 64 * j, hi - 64 * j);
+      if (half)
+        ax[j] |= b;
+      else
+        am[j] |= b;
+    }
+  });
+  for (uint64_t l = md.lst; l; l >>= 8) {
+    const uint32_t o = (uint32_t)(l & 0xFFu) - 1u;
+    const uint64_t b = 1ull << (o & 63u);
+#pragma unroll
+    for (int j = 0; j < N; ++j) ax[j] |= (o >> 6) == (uint32_t)j ? b : 0ull;
+  }
+  store_chunk_words_lean<N>(sb, rs, en, am, ax);
+}
+
+// kForm: the bitmap's word format and how the bits get there.
+//   kPrepU64    u64 words shared between neighbouring reads (a batch without
+//               ReadsDev::slots_aligned), cleared by the workgroup, bits OR-ed
+//               atomically;
+//   kPrepW32    u32 words private to the read, no clear: a read with bits
+//               gathers them in registers and stores all its words
+//               (store_chunk_words; a read over 32 kAccWords bases zeroes them
+//               and ORs), a read without (kInfoNoBits) writes nothing;
+//   kPrepStore  the same words with known sites and reads of <= 128 bases:
+//               every usable read stores its words, the listed reads wait
+//               for bqsr_prep_complex.
+enum : int { kPrepU64 = 0, kPrepW32 = 1, kPrepStore = 2 };
+template <int kForm, bool kLong = false>
 __device__ __forceinline__ bool prep_fast(const PrepParams& P, int64_t r, const PrepRec& x, const PrepCols& cols,
-                          uint64_t acc_out[kAccWords], uint4 md4b = make_uint4(0, 0, 0, 0)) {
+                                          uint4 md4b = make_uint4(0, 0, 0, 0)) {
+  constexpr bool kW32 = kForm != kPrepU64;
   const ReadMeta m = x.m;
   const ReadAlign a = x.a;
   const uint16_t f = m.flags;
@@ -875,7 +997,7 @@ __device__ __forceinline__ bool prep_fast(const PrepParams& P, int64_t r, const 
   FastCig c;
   if (!fast_cigar(cw, a.n_cigar, m, a.start, c)) return false;
   const uint64_t rs = m.slot;
-  bool nobits = false;  // (kStore false) the read sets no bit: kInfoNoBits, the passes skip its words
+  bool nobits = false;  // the read sets no bit: kInfoNoBits, the passes skip its words (not kPrepStore)
   if (usable) {
     FastMd md;
     if (kLong) {
@@ -885,44 +1007,79 @@ __device__ __forceinline__ bool prep_fast(const PrepParams& P, int64_t r, const 
       md = fast_md(cols.md4, a.md_len, c, st, en);
     }
     if (!md.ok) return false;  // prep_one raises MD_PARSE at the right offset
-    // with known sites (several bits per read, from three sources) the bits
-    // are gathered per word first; without, the few bits go straight out
-    // (measured: the gathering costs more than it saves on cfg2's reads)
-    if (kStore && (int64_t)(rs & 31) + en > 32 * kAccWords) return false;  // (not with <= 128 bases)
-    if ((kStore || P.sites.n_contigs > 0) && (int64_t)(rs & 31) + en <= 32 * kAccWords) {
-      // the read's sbits words in registers, one atomic OR per word with bits
-      // (measured: plain stores of the words a read owns alone, mixed with
-      // the neighbours' atomics on the same lines, were 2x slower)
+    const bool site_contig = a.contig >= 0 && a.contig < P.sites.n_contigs;
+    // the read's bits without its known sites: clips, an insertion, a tag shorter than the span, MD letters
+    const bool plain = c.lead <= st && (c.del || c.x == 0) && c.o_end >= en && md.listed && md.lst == 0 &&
+                       md.md_total >= c.span;
+    if (kForm == kPrepStore) {
+      // the read's words in registers (several bits per read, from three
+      // sources), out by plain stores; a contig without a site bitmap goes to
+      // pass 2, which rewrites the words
+      if (en > 32 * kAccWords || !md.listed) return false;  // (not with <= 128 bases; a list overflow)
+      uint64_t acc[kAccWords] = {0, 0, 0, 0, 0};
+      bool linear;
+      fast_bits(P.sites, a.contig, c, md, st, en, 0u, acc, &linear);
+      if (linear) return false;
+      store_chunk_words(P.sbits, rs, en, acc);
+    } else if (kW32 && P.sites.n_contigs == 0 && en < 256) {
+      // without known sites the read's fields tell whether it has a bit
+      // (about 85 % of cfg2's reads have none: nothing gathered, nothing
+      // written); the others gather theirs in the lean accumulator
+      nobits = plain;
+      if (!nobits) {
+        if (!md.listed) return false;  // (a list overflow: prep_long lists the trimmed range's only)
+        if (en <= 128)
+          lean_words<2>(P.sbits, rs, c, md, st, en);
+        else
+          lean_words<4>(P.sbits, rs, c, md, st, en);
+      }
+    } else if (kW32 && en <= 32 * kAccWords) {
+      // known sites: the words gathered with fast_bits, which tell whether
+      // the read has a bit
+      nobits = P.sites.n_contigs == 0 && plain;
+      if (!nobits) {
+        if (!md.listed) return false;  // (a list overflow: prep_long lists the trimmed range's only)
+        uint64_t acc[kAccWords] = {0, 0, 0, 0, 0};
+        bool linear;
+        fast_bits(P.sites, a.contig, c, md, st, en, 0u, acc, &linear);
+        if (linear && c.x > 0) return false;  // (mask_sites_linear maps offsets as unclipped + o)
+        if (P.sites.n_contigs > 0) nobits = !linear && !(acc[0] | acc[1] | acc[2] | acc[3] | acc[4]);
+        if (!nobits) {
+          store_chunk_words(P.sbits, rs, en, acc);
+          if (linear) {
+            own_words_order();
+            mask_sites_linear<true>(P, a.contig, c.unclipped, st, en, rs);
+          }
+        }
+      }
+    } else if (!kW32 && P.sites.n_contigs > 0 && (int64_t)(rs & 31) + en <= 32 * kAccWords) {
+      // with known sites (several bits per read, from three sources) the bits
+      // are gathered per word first, one atomic OR per word with bits;
+      // without, the few bits go straight out (measured: the gathering costs
+      // more than it saves on cfg2's reads)
       if (!md.listed) return false;  // (en <= 160: only a list overflow)
       uint64_t acc[kAccWords] = {0, 0, 0, 0, 0};
       const uint32_t r0 = (uint32_t)(rs & 31);  // bit of offset 0 in acc
       bool linear;
       fast_bits(P.sites, a.contig, c, md, st, en, r0, acc, &linear);
-      if (kStore) {
-        // the words go out with the wavefront's stores (prep_store_words); a
-        // contig without a bitmap goes to pass 2, whose atomics land on them
-        if (linear) return false;
+      if (linear && c.x > 0) return false;  // (mask_sites_linear maps offsets as unclipped + o)
+      nobits = !linear && !(acc[0] | acc[1] | acc[2] | acc[3] | acc[4]);
+      const uint64_t wb = rs >> 5;
 #pragma unroll
-        for (int j = 0; j < kAccWords; ++j) acc_out[j] = acc[j];
-      } else {
-        if (linear && c.x > 0) return false;  // (mask_sites_linear maps offsets as unclipped + o)
-        nobits = !linear && !(acc[0] | acc[1] | acc[2] | acc[3] | acc[4]);
-        const uint64_t wb = rs >> 5;
-#pragma unroll
-        for (int j = 0; j < kAccWords; ++j) {
-          if (!acc[j]) continue;
-          const uint64_t wi = wb + (uint64_t)j;
-          atomicOr((unsigned long long*)&P.sbits[wi], (unsigned long long)acc[j]);
-        }
-        if (linear) mask_sites_linear(P, a.contig, c.unclipped, st, en, rs);
+      for (int j = 0; j < kAccWords; ++j) {
+        if (!acc[j]) continue;
+        const uint64_t wi = wb + (uint64_t)j;
+        atomicOr((unsigned long long*)&P.sbits[wi], (unsigned long long)acc[j]);
       }
+      if (linear) mask_sites_linear<false>(P, a.contig, c.unclipped, st, en, rs);
     } else {
-      if (a.contig >= 0 && a.contig < P.sites.n_contigs && c.x > 0) return false;  // (sites as unclipped + o)
-      // bits: clips, an insertion, a tag shorter than the span, MD letters, sites
-      nobits = c.lead <= st && (c.del || c.x == 0) && c.o_end >= en && md.listed && md.lst == 0 &&
-               md.md_total >= c.span && !(a.contig >= 0 && a.contig < P.sites.n_contigs);
+      // bits OR-ed into the words one range at a time (u32 words: a read over
+      // 32 kAccWords bases, its words zeroed first unless it has no bit)
+      if (site_contig && c.x > 0) return false;  // (sites as unclipped + o)
+      if (!md.listed && (kLong || c.x > 0)) return false;
+      nobits = plain && !site_contig;
+      if (kW32 && !nobits) own_words_clear(P.sbits, rs, en);
       if (!md.listed) {  // more than 8 non-matching positions: the tag's per-byte walk
-        if (kLong || c.x > 0) return false;
         const uint32_t w[4] = {cols.md4.x, cols.md4.y, cols.md4.z, cols.md4.w};
         int64_t num = 0, pos = 0;
 #pragma unroll
@@ -935,7 +1092,7 @@ __device__ __forceinline__ bool prep_fast(const PrepParams& P, int64_t r, const 
               pos += num;
               num = 0;
               const int64_t o = c.lead + pos;  // reference position start + pos
-              if (pos < c.m1 && o >= st && o < en) set_sbits(P.sbits, rs + (uint64_t)o, rs + (uint64_t)o + 1, 32);
+              if (pos < c.m1 && o >= st && o < en) set_sbits<kW32>(P.sbits, rs + (uint64_t)o, rs + (uint64_t)o + 1, 32);
               pos += 1;
             }
           }
@@ -944,9 +1101,9 @@ __device__ __forceinline__ bool prep_fast(const PrepParams& P, int64_t r, const 
       FastMd me = md;
       if (!md.listed) me.lst = 0;  // (its letters: the walk above)
       fast_emit(c, me, st, en,
-                [&](int lo, int hi, int half) { set_sbits(P.sbits, rs + (uint64_t)lo, rs + (uint64_t)hi, half); });
-      if (a.contig >= 0 && a.contig < P.sites.n_contigs && !mask_sites_bitmap(P, a.contig, c.unclipped, en, rs))
-        mask_sites_linear(P, a.contig, c.unclipped, st, en, rs);
+                [&](int lo, int hi, int half) { set_sbits<kW32>(P.sbits, rs + (uint64_t)lo, rs + (uint64_t)hi, half); });
+      if (site_contig && !mask_sites_bitmap<kW32>(P, a.contig, c.unclipped, en, rs))
+        mask_sites_linear<kW32>(P, a.contig, c.unclipped, st, en, rs);
     }
   }
   const uint16_t nb = nobits ? kInfoNoBits : 0;
@@ -957,6 +1114,7 @@ __device__ __forceinline__ bool prep_fast(const PrepParams& P, int64_t r, const 
 
 // a listed read through prep_fast's long form (own loads, no pipeline); false:
 // prep_one decides
+template <bool kW32>
 __device__ __forceinline__ bool prep_long(const PrepParams& P, int64_t r) {
   PrepRec x{};
   x.m = P.rd.meta[r];
@@ -969,56 +1127,7 @@ __device__ __forceinline__ bool prep_long(const PrepParams& P, int64_t r) {
     c.md4 = *(const uint4*)(P.rd.md + x.a.md_off);
     md4b = *(const uint4*)(P.rd.md + x.a.md_off + 16);
   }
-  uint64_t acc[kAccWords] = {0, 0, 0, 0, 0};
-  return prep_fast<false, true>(P, r, x, c, acc, md4b);
-}
-
-// store_words: the wavefront's sbits words as plain stores (no zeroing
-// pass, no read-modify-write atomics at the memory side: measured 1 ms of
-// cfg3's 3 ms prep).  Lane l (read r, first slot s_l) owns the words whose
-// first slot lies in [s_l, s_l+1) -- every word once, gaps included -- and
-// stores its read's bits there.  A read starting inside a word owns neither
-// that word nor its bits in it: those go down the wavefront to the owner by a
-// segmented OR scan keyed by the word (keys are nondecreasing along the
-// lanes); lane 0's go to bnd for pass 2 (the owner is in an earlier
-// wavefront).  Read 0 owns its first word outright.
-__device__ __forceinline__ uint64_t shfl_down_u64(uint64_t v, int d) {
-  const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)v, d), hi = (uint32_t)__shfl_down((int)(uint32_t)(v >> 32), d);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ void prep_store_words(const PrepParams& P, int64_t r, const PrepRec& x,
-                                                 const uint64_t acc[kAccWords]) {
-  const int lane = threadIdx.x & 63;
-  const int64_t n = P.rd.n_reads;
-  const uint64_t slot = r < n ? x.m.slot : (uint64_t)P.rd.n_slots;
-  uint64_t nslot = shfl_down_u64(slot, 1);
-  if (lane == 63) nslot = r < n ? x.nslot : (uint64_t)P.rd.n_slots;
-  const uint64_t fw = slot >> 5;
-  const bool mid = (slot & 31) != 0 && r != 0;  // starts inside a word it does not own
-  const uint64_t own_lo = mid ? fw + 1 : fw, own_hi = (nslot + 31) >> 5;
-  uint64_t S = mid ? acc[0] : 0ull;
-  const uint32_t key = (uint32_t)fw;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t So = shfl_down_u64(S, d);
-    const uint32_t ko = (uint32_t)__shfl_down((int)key, d);
-    if (lane + d < 64 && ko == key) S |= So;
-  }
-  const uint64_t Sn = shfl_down_u64(S, 1);
-  const uint32_t kn = (uint32_t)__shfl_down((int)key, 1);
-  const uint64_t extra = (lane < 63 && own_hi > own_lo && kn == (uint32_t)(own_hi - 1)) ? Sn : 0ull;
-  for (uint64_t w = own_lo; w < own_hi; ++w) {
-    const uint64_t j = w - fw;
-    uint64_t v = 0;
-#pragma unroll
-    for (int k = 0; k < kAccWords; ++k) v = j == (uint64_t)k ? acc[k] : v;
-    P.sbits[w] = v | (w + 1 == own_hi ? extra : 0ull);
-  }
-  if (lane == 0) {
-    const int64_t g = r >> 6;
-    P.bnd[2 * g] = mid ? S : 0ull;
-    P.bnd[2 * g + 1] = fw;
-  }
+  return prep_fast<kW32 ? kPrepW32 : kPrepU64, true>(P, r, x, c, md4b);
 }
 
 // Pass 1: workgroup w takes reads [w * kPrepChunk, (w + 1) * kPrepChunk); the
@@ -1026,10 +1135,9 @@ __device__ __forceinline__ void prep_store_words(const PrepParams& P, int64_t r,
 // in the workgroup's own segment of the worklist -- LDS-compacted, no global
 // atomics (one counter shared by every wavefront serialised at the memory
 // side: measured 1.8 ms for 10M reads).
-// (kStore = PrepParams::store_words, a template so each form gets its own registers)
-// Without word stores (kStore false: a zeroed bitmap, bits OR-ed atomically)
-// the workgroup then finishes its listed reads itself (prep_one, a thread a
-// read): no second launch waiting for every workgroup of this one, and the
+// (kForm: prep_fast's forms, a template so each gets its own registers)
+// kPrepU64 and kPrepW32: the workgroup then finishes its listed reads itself
+// (prep_one, a thread a read): no second launch waiting for every workgroup of this one, and the
 // listed reads' latency chains overlap other workgroups' lock-step work
 // (round 5, cfg2: the listed reads -- ~10 of 2048, the reads ending in a Q2
 // run, whose MD lists every trimmed base as a mismatch -- cost 66 us here
@@ -1039,13 +1147,19 @@ __device__ __forceinline__ void prep_store_words(const PrepParams& P, int64_t r,
 // takes those reads without prep_one's per-byte walks; prep_one is forced
 // inline (outlined, the call cost more than the long form saved: 308 -> 465
 // us; inline 267 us, profiles/r05ae_prep_long_ab.txt).
-// With word stores they wait for bqsr_prep_complex, whose atomics must land
-// on words every workgroup has stored.  The atomic form asks for 5 waves per
-// SIMD (round 5, with the indel fast path's registers: 329.5 -> 317.6 us
-// cfg2 against 6 waves; round 4 had 6 against 5); the store form keeps its
-// 104 VGPRs (at 6 waves it ran 2.08 -> 3.08 ms on cfg3).
-template <bool kStore>
-__global__ void __launch_bounds__(kPrepThreads, kStore ? 1 : 5) bqsr_prep_kernel(PrepParams P) {
+// With word stores (kPrepStore) they wait for bqsr_prep_complex.  The other
+// forms ask for 5 waves per SIMD (round 5, with the indel fast path's
+// registers: 329.5 -> 317.6 us cfg2 against 6 waves; round 4 had 6 against
+// 5); the store form keeps its own registers (at 6 waves it ran 2.08 -> 3.08
+// ms on cfg3).
+// Only kPrepU64 clears: its words are shared between neighbouring reads, so
+// bits can only be OR-ed in, onto zeros.  The u32 words belong to one read
+// each and are written whole by the reads that have bits; what the words of
+// the other reads hold (an earlier job's bits, a fresh allocation's bytes)
+// is never loaded.
+template <int kForm>
+__global__ void __launch_bounds__(kPrepThreads, kForm == kPrepStore ? 1 : 5) bqsr_prep_kernel(PrepParams P) {
+  constexpr bool kStore = kForm == kPrepStore, kW32 = kForm != kPrepU64;
   __shared__ uint32_t list[kPrepChunk];
   __shared__ uint32_t cnt;
   __shared__ uint32_t s_cig[kStore ? 1 : kPrepThreads * kPrepCigStride];
@@ -1055,7 +1169,7 @@ __global__ void __launch_bounds__(kPrepThreads, kStore ? 1 : 5) bqsr_prep_kernel
   const int64_t c0 = (int64_t)blockIdx.x * kPrepChunk;
   if (threadIdx.x == 0) {
     cnt = 0;
-    if (!kStore) {  // the slots of this workgroup's reads: [slot of c0, slot of the next workgroup's first)
+    if (!kW32) {  // the slots of this workgroup's reads: [slot of c0, slot of the next workgroup's first)
       s_rng[0] = c0 < n ? P.rd.meta[c0].slot : P.rd.n_slots;
       s_rng[1] = c0 + kPrepChunk < n ? P.rd.meta[c0 + kPrepChunk].slot : P.rd.n_slots;
     }
@@ -1067,13 +1181,11 @@ __global__ void __launch_bounds__(kPrepThreads, kStore ? 1 : 5) bqsr_prep_kernel
   const int64_t rt = c0 + threadIdx.x;
   PrepRec x0 = prep_rec(P, rt), x1 = prep_rec(P, rt + kPrepThreads);
   PrepCols k0 = prep_cols(P, x0);
-  if (!kStore) {
+  if (!kW32) {
     // the bitmap words of this workgroup's slots cleared before its ORs, so
     // no fill pass precedes the launch: whole words by plain stores, the two
     // shared with the neighbours' ranges by an AND of this range's bits (a
-    // neighbour's own bits are never cleared, whatever the order).  (The
-    // words' writes cost ~55 us on cfg2 wherever they go -- fill kernel,
-    // apply kernel -- here they overlap the pass's loads.)
+    // neighbour's own bits are never cleared, whatever the order).
     const uint64_t sa = s_rng[0], sb = s_rng[1];
     const uint64_t wa = (sa + 31) >> 5, wb = sb >> 5;
     for (uint64_t w = wa + threadIdx.x; w < wb; w += kPrepThreads) P.sbits[w] = 0ull;
@@ -1093,15 +1205,7 @@ __global__ void __launch_bounds__(kPrepThreads, kStore ? 1 : 5) bqsr_prep_kernel
     const int64_t r = rt + i;
     const PrepRec x2 = i + 2 * kPrepThreads < kPrepChunk ? prep_rec(P, r + 2 * kPrepThreads) : PrepRec{};
     const PrepCols k1 = i + kPrepThreads < kPrepChunk ? prep_cols(P, x1) : PrepCols{};
-    uint64_t acc[kAccWords] = {0, 0, 0, 0, 0};
-    const bool todo = r < n && !prep_fast<kStore>(P, r, x0, k0, acc);
-    if (kStore) {
-      if (todo) {
-#pragma unroll
-        for (int k = 0; k < kAccWords; ++k) acc[k] = 0;
-      }
-      prep_store_words(P, r, x0, acc);
-    }
+    const bool todo = r < n && !prep_fast<kForm>(P, r, x0, k0);
     x0 = x1;
     x1 = x2;
     k0 = k1;
@@ -1117,29 +1221,26 @@ __global__ void __launch_bounds__(kPrepThreads, kStore ? 1 : 5) bqsr_prep_kernel
   const uint32_t k = cnt;
   if (!kStore) {
     for (uint32_t i = threadIdx.x; i < k; i += kPrepThreads)
-      if (!prep_long(P, (int64_t)list[i]))
-        prep_one(P, (int64_t)list[i], &s_cig[threadIdx.x * kPrepCigStride], &s_md[threadIdx.x * kPrepMdStride]);
+      if (!prep_long<kW32>(P, (int64_t)list[i]))
+        prep_one<kW32>(P, (int64_t)list[i], &s_cig[threadIdx.x * kPrepCigStride], &s_md[threadIdx.x * kPrepMdStride]);
     return;
   }
   for (uint32_t i = threadIdx.x; i < k; i += kPrepThreads) P.work[c0 + i] = list[i];
   if (threadIdx.x == 0) P.n_work[blockIdx.x] = k;
 }
 
-// Pass 2 (word stores only): workgroup w takes the reads pass 1's workgroup w
-// listed, one thread per read, the full per-read path (prep_one).
+// Pass 2 (kPrepStore only): workgroup w takes the reads pass 1's workgroup w
+// listed and wrote no word of, one thread per read: the long form, else the
+// full per-read path (prep_one).
 extern "C" __global__ void __launch_bounds__(kComplexThreads) bqsr_prep_complex(PrepParams P) {
   __shared__ uint32_t s_cig[kComplexThreads * kPrepCigStride];
   __shared__ uint32_t s_md[kComplexThreads * kPrepMdStride];
   const uint32_t k = P.n_work[blockIdx.x];
   const int64_t c0 = (int64_t)blockIdx.x * kPrepChunk;
-  if (P.store_words && threadIdx.x < kPrepChunk / 64) {  // pass 1's wavefront-boundary shares
-    const int64_t g = (c0 >> 6) + threadIdx.x;
-    if (g * 64 < P.rd.n_reads && P.bnd[2 * g])
-      atomicOr((unsigned long long*)&P.sbits[P.bnd[2 * g + 1]], (unsigned long long)P.bnd[2 * g]);
-  }
   for (uint32_t i = threadIdx.x; i < k; i += kComplexThreads)
-    if (!prep_long(P, (int64_t)P.work[c0 + i]))
-      prep_one(P, (int64_t)P.work[c0 + i], &s_cig[threadIdx.x * kPrepCigStride], &s_md[threadIdx.x * kPrepMdStride]);
+    if (!prep_long<true>(P, (int64_t)P.work[c0 + i]))
+      prep_one<true>(P, (int64_t)P.work[c0 + i], &s_cig[threadIdx.x * kPrepCigStride],
+                     &s_md[threadIdx.x * kPrepMdStride]);
 }
 
 // ------------------------------------------------------- lane-per-read ----
@@ -1321,18 +1422,6 @@ __device__ __forceinline__ void sub_bits(const uint64_t* w, uint32_t b0, int i, 
   }
   masked = __builtin_amdgcn_alignbit((uint32_t)hi, (uint32_t)lo, sh);
   mism = __builtin_amdgcn_alignbit((uint32_t)(hi >> 32), (uint32_t)(lo >> 32), sh);
-}
-
-// The same bits when the step's first slot sits at bit 16 h of w[0] (h = 0
-// or 1: 16-aligned slots, ReadsDev::slots_aligned): chunk i's bits are one
-// half of word (h + i) >> 1 -- a select for odd i instead of a scan.
-template <int NW>
-__device__ __forceinline__ void sub_bits16(const uint64_t* w, uint32_t h, int i, uint32_t& masked, uint32_t& mism) {
-  const int a = i >> 1, b = (i + 1) >> 1 < NW ? (i + 1) >> 1 : NW - 1;
-  const uint64_t v = (i & 1) ? (h ? w[b] : w[a]) : w[a];
-  const uint32_t sh = 16u * ((h + (uint32_t)i) & 1u);
-  masked = (uint32_t)v >> sh;
-  mism = (uint32_t)(v >> 32) >> sh;
 }
 
 // the read's first visited offset k has context 0 (slot 4): its predecessor
@@ -1587,7 +1676,8 @@ __device__ __forceinline__ void lds_add(uint32_t addr, uint32_t v) {
 // bqsr_observe_lean's slab layout, then the walk's kMkWords markers.
 struct ObsChunkLoads {
   uint4 qs, cr;
-  uint64_t bw0, bw1;  // sbits words of the chunk's first slot and the next
+  uint64_t bw0, bw1;  // u64 sbits words of the chunk's first slot and the next; aligned slots: the chunk's u32
+                      // word as a u64 one (masked bits 0..15, mismatch bits 32..47)
 };
 
 __device__ __forceinline__ ObsChunkLoads observe_load(const ObserveParams& P, const LaneRead& x, int j, bool on) {
@@ -1598,9 +1688,14 @@ __device__ __forceinline__ ObsChunkLoads observe_load(const ObserveParams& P, co
   if (x.fl & kInfoObs) {
     v.cr = chunk_raw(P.rd, chunk_n0(x, o0));
     const uint64_t s0 = x.oslot + (uint64_t)o0;
-    if (!(x.fl & kInfoNoBits)) {  // (a read without bits: nothing to load)
-      v.bw0 = P.sbits[s0 >> 5];
-      if ((s0 & 31) > 16) v.bw1 = P.sbits[(s0 >> 5) + 1];  // an unaligned layout's chunk across two words
+    if (!(x.fl & kInfoNoBits)) {  // (a read without bits: nothing to load, and nothing written there)
+      if (P.rd.slots_aligned) {  // u32 words, one per chunk
+        const uint32_t w = ((const uint32_t*)P.sbits)[s0 >> 4];
+        v.bw0 = (uint64_t)(w & 0xFFFFu) | ((uint64_t)(w >> 16) << 32);
+      } else {
+        v.bw0 = P.sbits[s0 >> 5];
+        if ((s0 & 31) > 16) v.bw1 = P.sbits[(s0 >> 5) + 1];  // the chunk across two words
+      }
     }
   }
   return v;
@@ -1623,7 +1718,7 @@ __device__ __forceinline__ void observe_chunk(const ObserveParams& P, const ObsP
   uint32_t bm = 0, bx = 0;
   uint32_t xo[4] = {4u, 4u, 4u, 4u};
   if (full) {
-    const uint32_t sb = (uint32_t)((x.oslot + (uint64_t)o0) & 31);
+    const uint32_t sb = P.rd.slots_aligned ? 0u : (uint32_t)((x.oslot + (uint64_t)o0) & 31);
     bm = __builtin_amdgcn_alignbit((uint32_t)ld.bw1, (uint32_t)ld.bw0, sb);
     bx = __builtin_amdgcn_alignbit((uint32_t)(ld.bw1 >> 32), (uint32_t)(ld.bw0 >> 32), sb);
     chunk_ctx(P.rd, x.fl & kInfoNeg, chunk_n0(x, o0), ld.cr, j, pc.tb, xo);

@@ -99,7 +99,10 @@ __device__ __forceinline__ void lean_clean(const uint32_t q[4], const uint32_t x
 // Prep ran before: ReadInfo and the slot bitmap.  (A form with the common
 // read's prep done in the observing lane -- the "fused prep" -- measured 2.15
 // against 2.06 ms a cfg2 job and was removed in round 6; git history holds it.)
-template <bool kIdent>
+// kW32 = ReadsDev::slots_aligned: the bitmap's u32 words, one per chunk (a
+// step's eight are two 16-B loads, dword-aligned, reaching up to seven words
+// past the read's own: the column's padding); else its u64 words.
+template <bool kIdent, bool kW32>
 __global__ void __launch_bounds__(kBlockThreads) bqsr_observe_lean(ObserveParams P) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int qw = P.w.qw, cells = P.g.cells, C = P.g.C, L = P.g.L;
@@ -157,13 +160,14 @@ __global__ void __launch_bounds__(kBlockThreads) bqsr_observe_lean(ObserveParams
     const bool rev = x.dir < 0;
     const uint32_t u1lo = neg ? kT2clo : kT1lo, u2lo = neg ? kT1clo : kT2lo;
     const uint32_t sel_q = rev ? kPermRev : kPermId, sel_x = sec ? kPermRev : kPermId;
-    const int jb = P.rd.slots_aligned ? -(x.st & 15) : 0;
+    const int jb = kW32 ? -(x.st & 15) : 0;
     const uint8_t* qp = P.rd.qual + x.slot;
     for (int j0 = jb; __builtin_amdgcn_ballot_w64(j0 < n); j0 += kSup) {
       if (j0 >= n) continue;
       uint4 qs[kLeanSub];
       uint3 cr[kLeanSub];
-      uint64_t bw[NW];
+      uint64_t bw[kW32 ? 1 : NW];
+      uint4 cw0 = make_uint4(0, 0, 0, 0), cw1 = cw0;  // kW32: the words of chunks 0..3 and 4..7
       const uint64_t s0 = x.slot + (uint64_t)(x.st + j0);
 #pragma unroll
       for (int i = 0; i < kLeanSub; ++i) {
@@ -173,9 +177,17 @@ __global__ void __launch_bounds__(kBlockThreads) bqsr_observe_lean(ObserveParams
         const int64_t n0 = chunk_n0(x, o0);
         cr[i] = (lv && full && n0 >= 0) ? *(const uint3*)(P.rd.bases + ((n0 >> 3) << 2)) : make_uint3(0, 0, 0);
       }
+      if constexpr (kW32) {
+        if (full && !(x.fl & kInfoNoBits)) {  // (a read without bits wrote no word)
+          const uint32_t* cwp = (const uint32_t*)P.sbits + (s0 >> 4);
+          cw0 = *(const uint4*)cwp;
+          if (4 * kChunk < n - j0) cw1 = *(const uint4*)(cwp + 4);
+        }
+      } else {
 #pragma unroll
-      for (int w = 0; w < NW; ++w)
-        bw[w] = !(full && !(x.fl & kInfoNoBits) && (w == 0 || 32 * w - 32 < n - j0)) ? 0ull : P.sbits[(s0 >> 5) + w];
+        for (int w = 0; w < NW; ++w)
+          bw[w] = !(full && !(x.fl & kInfoNoBits) && (w == 0 || 32 * w - 32 < n - j0)) ? 0ull : P.sbits[(s0 >> 5) + w];
+      }
 #pragma clang loop unroll(full)
       for (int i = 0; i < kLeanSub; ++i) {
         const int j = j0 + kChunk * i;
@@ -187,10 +199,13 @@ __global__ void __launch_bounds__(kBlockThreads) bqsr_observe_lean(ObserveParams
         uint32_t bm = 0, bx = 0;
         uint32_t h[4] = {0x10101010u, 0x10101010u, 0x10101010u, 0x10101010u};  // slot 4
         if (full) {
-          if (P.rd.slots_aligned)
-            sub_bits16<NW>(bw, (uint32_t)(s0 >> 4) & 1u, i, bm, bx);
-          else
+          if constexpr (kW32) {
+            const uint32_t cwv[kLeanSub] = {cw0.x, cw0.y, cw0.z, cw0.w, cw1.x, cw1.y, cw1.z, cw1.w};
+            bm = cwv[i] & 0xFFFFu;
+            bx = cwv[i] >> 16;
+          } else {
             sub_bits<NW>(bw, (uint32_t)(s0 & 31), i, bm, bx);
+          }
           const int64_t n0 = chunk_n0(x, o0);
           uint64_t clo;
           uint32_t chi;
@@ -348,6 +363,7 @@ __global__ void __launch_bounds__(kBlockThreads) bqsr_observe_lean(ObserveParams
     for (int k = tid; k < kQBins; k += blockDim.x) P.hq_block[(int64_t)blockIdx.x * kQBins + k] = blk_hist[k];
 }
 
-template __global__ void bqsr_observe_lean<true>(ObserveParams);
+template __global__ void bqsr_observe_lean<true, false>(ObserveParams);
+template __global__ void bqsr_observe_lean<true, true>(ObserveParams);
 
 }  // namespace bqsr
