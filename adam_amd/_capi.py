@@ -40,6 +40,8 @@ EXPORTS = [
     "bqsr_bgzf_inflate", "bqsr_sam_bam_form",
     "bqsr_sam_pileup_prepare", "bqsr_sam_pileup_columns", "bqsr_arrow_pileup_prepare", "bqsr_arrow_pileup_columns",
     "bqsr_pileup_kernel_times",
+    "bqsr_pileup_agg_create", "bqsr_pileup_agg_destroy", "bqsr_pileup_agg_add_host", "bqsr_sam_pileup_agg_add",
+    "bqsr_arrow_pileup_agg_add", "bqsr_pileup_agg_run", "bqsr_pileup_agg_fetch", "bqsr_pileup_agg_kernel_times",
     "bqsr_sam_bam_prepare", "bqsr_sam_bam_records", "bqsr_sam_bam_header", "bqsr_bgzf_compress",
     "bqsr_bam_kernel_times",
     "bqsr_compare_create", "bqsr_compare_destroy", "bqsr_compare_check_terms", "bqsr_compare_sam", "bqsr_compare_sides",

@@ -2183,6 +2183,7 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
 #include "sam_batch.hip"
 #include "arrow_ingest.hip"
 #include "pileup.hip"
+#include "pileup_agg.hip"
 #include "compare.hip"
 #include "tags.hip"
 #include "parquet_gzip.cpp"

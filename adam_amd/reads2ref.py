@@ -276,13 +276,11 @@ def _arrow_read_level(table, r0: int, n: int) -> _ReadLevel:
     return _ReadLevel(col("readName", pa.string()), coded)
 
 
-def arrow_pileups(reads, r0: int = 0, n: Optional[int] = None, stream=None):
-    """The ADAMPileup table of reads [r0, r0 + n) of a parquet.ArrowReads
-    (its table as given: apply :func:`locus_filter` before the upload)."""
+def _arrow_prepare(reads, r0: int, n: int, stream=None) -> PileupSizes:
+    """bqsr_arrow_pileup_prepare over reads [r0, r0 + n) of a parquet.ArrowReads"""
     import pyarrow as pa
     L = _lib()
     table = reads.table
-    n = reads.n_reads - r0 if n is None else n
     sz = PileupSizes()
     if not getattr(reads, "_mapq_sent", False):
         # mapq is not among bqsr_arrow_chunk's columns: handed over here, once per handle
@@ -311,6 +309,16 @@ def arrow_pileups(reads, r0: int = 0, n: Optional[int] = None, stream=None):
     else:
         check(L.bqsr_arrow_pileup_prepare(reads.ctx.handle, reads.h, r0, n, None, None, None, 0, stream,
                                           ctypes.byref(sz)))
+    return sz
+
+
+def arrow_pileups(reads, r0: int = 0, n: Optional[int] = None, stream=None):
+    """The ADAMPileup table of reads [r0, r0 + n) of a parquet.ArrowReads
+    (its table as given: apply :func:`locus_filter` before the upload)."""
+    L = _lib()
+    table = reads.table
+    n = reads.n_reads - r0 if n is None else n
+    sz = _arrow_prepare(reads, r0, n, stream)
     if sz.n_rows == 0:
         return _table(0, {}, None)
     H, arrays = _host_columns(sz.n_rows)

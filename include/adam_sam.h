@@ -656,6 +656,163 @@ bqsr_status bqsr_arrow_pileup_columns(bqsr_context* ctx, bqsr_arrow* a, const bq
  * columns call, in milliseconds (tools/bench_adam.py --reads2ref). */
 bqsr_status bqsr_pileup_kernel_times(double* count_ms, double* emit_ms);
 
+/* `adam aggregate_pileups` and what `reads2ref -aggregate` would compute
+ * (adam-cli/.../cli/PileupAggregator.scala:27-57 over PileupAggregator.
+ * aggregate, adam-core/.../rdd/PileupAggregator.scala:25-219): ADAMPileup rows
+ * grouped by (referenceId, position) and, within a position, by (readBase,
+ * rangeOffset, recordGroupSample); every group folded into one row.  Each of
+ * the three inner components is nullable and null is a value of its own (a null
+ * rangeOffset is not 0, a null sample is not "").
+ * The reference leaves two orders to Spark's shuffle and to a hash map; this
+ * interface DECLARES them:
+ *   fold order    rows fold in input row order: the order of the add calls,
+ *                 then the row order within an add.
+ *   output order  groups ascend by (referenceId, position, readBase ordinal,
+ *                 rangeOffset, sample code), integers signed, nulls first in
+ *                 every component.  The caller gives samples as int32 codes;
+ *                 codes that rank the distinct sample strings in byte order
+ *                 make this the byte order of the strings.
+ * A group of one row passes through, except mapQuality = mapQuality /
+ * countAtPosition and sangerQuality = sangerQuality / countAtPosition (so
+ * aggregating an aggregated file divides again, as in the reference).  A group
+ * of n >= 2 rows is the reference's reduce, a left fold whose accumulator is a
+ * built record: C = c_1, M = m_1, S = s_1, then for k = 2..n
+ *   M = M * C + m_k * c_k;  S = S * C + s_k * c_k;  C = C + c_k
+ * (M and S use the old C: the accumulator's quality is multiplied by its
+ * accumulated count -- the reference's quirk, order-dependent and factorial in
+ * depth), all in Java int arithmetic, wrapping mod 2^32; at the end mapQuality
+ * = M / C, sangerQuality = S / C, countAtPosition = C, the division truncating
+ * toward zero and Int.MinValue / -1 = Int.MinValue.  numSoftClipped and
+ * numReverseStrand are wrapping int sums, readStart the min, readEnd the max;
+ * referenceId, position, rangeOffset, rangeLength, referenceBase and readBase
+ * are the group's first row's.  The string columns are the caller's: fetch
+ * returns every group's rows in fold order (offsets into order) for them.
+ * Errors (bqsr_last_error_read = the row, counted over all adds; no result).
+ * The reference groups every row before it folds any, and so does the order
+ * declared here: first what throws while grouping, then what the folds throw,
+ * and within either the LOWEST offending input row decides (on one row
+ * NULL_FIELD before PILEUP).
+ *   grouping  BQSR_ERR_NULL_FIELD  a null referenceId or position
+ *             (ReferencePosition.apply unboxes them)
+ *             BQSR_ERR_UNSUPPORTED a sample code outside [0, 2^22 - 2] (and,
+ *             from the add calls, more than 2^31 - 1 rows in one handle)
+ *   folds     BQSR_ERR_NULL_FIELD  in any row a null mapQuality, sangerQuality
+ *             or countAtPosition; in a row of a group of two or more a null
+ *             numSoftClipped, numReverseStrand, readStart or readEnd (a lone
+ *             row with those nulls passes through)
+ *             BQSR_ERR_PILEUP      a group whose C is 0 (Java's
+ *             ArithmeticException), reported at the group's first row
+ * The handle keeps every added row on the device (about 70 bytes a row; run
+ * needs some 30 bytes a row more, plus the sort's scratch, while it runs).
+ * add_host: n_rows rows from host columns.  A NULL value column is a column of
+ *   nulls (rg_code is required); a *_valid pointer is an Arrow validity bitmap
+ *   of the add's rows (ceil(n_rows / 8) bytes, NULL: all valid).  Base columns
+ *   hold the enum ordinal.  rg_code: any int32 that is equal for rows whose ten
+ *   recordGroup* fields are equal; it only feeds uniform_rg.  name_code: the
+ *   caller's code of the row's readName, handed back by fetch (NULL: the
+ *   row's index in the handle).
+ * bqsr_sam_pileup_agg_add / bqsr_arrow_pileup_agg_add: the rows of the last
+ *   *_pileup_prepare on that parse, written by the emit pass straight into the
+ *   handle's columns (no host copy).  sample_code and rg_code: host arrays, one
+ *   entry per read of the prepared range (a negative sample code: null sample).
+ *   referenceId is the parse's (SAM / BAM: the @SQ index, null for "*"; a
+ *   bqsr_arrow handle: its referenceId column, loaded as for MarkDuplicates, a
+ *   negative one reading as null); countAtPosition is 1; a row's name code is
+ *   name_base + its read's index in the prepared range (the caller's ordinal
+ *   of the read; below 2^31).
+ * run: keys, sort, heads, the two scans, emit (adam_amd/csrc/pileup_agg.hip).
+ *   Adding rows afterwards discards the result; run may be called again.
+ * fetch: the result of the last successful run into host buffers (NULL skips
+ *   one): the group columns [n_groups]; validity words [bitmap_words] (bits at
+ *   and beyond n_groups clear; slots of null entries hold 0; the columns
+ *   without a word are never null); first_row = the group's first input row;
+ *   offsets [n_groups + 1] into order [n_rows], the input rows sorted by group,
+ *   a group's rows in fold order; names [n_rows]: the name codes of the rows of
+ *   order; uniform_rg: bit set where every row of the
+ *   group has one rg_code. */
+typedef struct bqsr_pileup_agg bqsr_pileup_agg;
+typedef struct bqsr_pileup_agg_rows {
+  int64_t n_rows;
+  const int32_t* reference_id;
+  const int64_t* position;
+  const int32_t* range_offset;
+  const int32_t* range_length;
+  const uint8_t* reference_base;
+  const uint8_t* read_base;
+  const int32_t* sanger_quality;
+  const int32_t* map_quality;
+  const int32_t* num_soft_clipped;
+  const int32_t* num_reverse_strand;
+  const int32_t* count_at_position;
+  const int64_t* read_start;
+  const int64_t* read_end;
+  const int32_t* sample_code;
+  const int32_t* rg_code;
+  const int32_t* name_code;
+  const uint8_t* reference_id_valid;
+  const uint8_t* position_valid;
+  const uint8_t* range_offset_valid;
+  const uint8_t* range_length_valid;
+  const uint8_t* reference_base_valid;
+  const uint8_t* read_base_valid;
+  const uint8_t* sanger_quality_valid;
+  const uint8_t* map_quality_valid;
+  const uint8_t* num_soft_clipped_valid;
+  const uint8_t* num_reverse_strand_valid;
+  const uint8_t* count_at_position_valid;
+  const uint8_t* read_start_valid;
+  const uint8_t* read_end_valid;
+  const uint8_t* sample_code_valid;
+} bqsr_pileup_agg_rows;
+typedef struct bqsr_pileup_agg_sizes {
+  int64_t n_rows;
+  int64_t n_groups;
+  int64_t bitmap_words; /* ceil(n_groups / 64) u64 words per bitmap */
+} bqsr_pileup_agg_sizes;
+typedef struct bqsr_pileup_agg_host {
+  int32_t* reference_id;
+  int64_t* position;
+  int32_t* range_offset;
+  int32_t* range_length;
+  uint8_t* reference_base;
+  uint8_t* read_base;
+  int32_t* sanger_quality;
+  int32_t* map_quality;
+  int32_t* num_soft_clipped;
+  int32_t* num_reverse_strand;
+  int32_t* count_at_position;
+  int64_t* read_start;
+  int64_t* read_end;
+  uint32_t* first_row;
+  uint32_t* offsets;
+  uint32_t* order;
+  int32_t* names;
+  uint64_t* range_offset_valid;
+  uint64_t* range_length_valid;
+  uint64_t* reference_base_valid;
+  uint64_t* read_base_valid;
+  uint64_t* num_soft_clipped_valid;
+  uint64_t* num_reverse_strand_valid;
+  uint64_t* read_start_valid;
+  uint64_t* read_end_valid;
+  uint64_t* uniform_rg;
+} bqsr_pileup_agg_host;
+bqsr_status bqsr_pileup_agg_create(bqsr_context* ctx, bqsr_pileup_agg** out);
+void bqsr_pileup_agg_destroy(bqsr_pileup_agg* agg);
+bqsr_status bqsr_pileup_agg_add_host(bqsr_pileup_agg* agg, const bqsr_pileup_agg_rows* rows, void* stream);
+bqsr_status bqsr_sam_pileup_agg_add(bqsr_context* ctx, bqsr_sam* s, bqsr_pileup_agg* agg, const int32_t* sample_code,
+                                    const int32_t* rg_code, int64_t name_base, void* stream);
+bqsr_status bqsr_arrow_pileup_agg_add(bqsr_context* ctx, bqsr_arrow* a, bqsr_pileup_agg* agg,
+                                      const int32_t* sample_code, const int32_t* rg_code, int64_t name_base,
+                                      void* stream);
+bqsr_status bqsr_pileup_agg_run(bqsr_pileup_agg* agg, void* stream, bqsr_pileup_agg_sizes* out);
+bqsr_status bqsr_pileup_agg_fetch(bqsr_pileup_agg* agg, const bqsr_pileup_agg_host* dst, void* stream);
+/* MEASUREMENT ONLY, not part of the stable interface: device-event times of
+ * the calling thread's last run, in ms: the keys kernel; the sort (key
+ * gathers and radix passes, and the host's look at the error word before
+ * them); heads and the two scans; emit (tools/bench_adam.py --aggregate). */
+bqsr_status bqsr_pileup_agg_kernel_times(double* keys_ms, double* sort_ms, double* scans_ms, double* emit_ms);
+
 /* MarkDuplicates across the partitions of one input (the reference's
  * groupBy spans every partition of the RDD, MarkDuplicates.scala:43-58).
  * add: one partition's parse (partitions in input order, each parsed with

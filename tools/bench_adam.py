@@ -32,6 +32,18 @@ summed; `close` is the wait for them at the end).  The two kernels' times are
 device events; the emit kernel's bytes written per second stand beside the
 copy rate DESIGN.md uses.  One JSON line.
 
+    python tools/bench_adam.py --aggregate [--reads 2000000] [--restatement-reads 200000]
+
+--aggregate measures `adam aggregate_pileups` (adam_amd/aggregate_pileups.py)
+over the same synthetic reads as --reads2ref, read input (the rows never leave
+the device), next to the unaggregated `reads2ref` job on the same file: both
+legs in this process, each run once after a warm-up run of its own.  Per leg
+the end-to-end seconds, rows in and out and the phase split (host clock); for
+the aggregation the device-event ms of its keys, sort, scans and emit stages;
+and the single-threaded Python restatement (tests/_pileup_ref.py,
+tests/_pileup_agg_ref.py) on the first --restatement-reads reads, whose result
+the command's on the same reads must equal.  One JSON line.
+
     python tools/bench_adam.py --bam-out [--reads 2000000] [--bam-level 6]
 
 --bam-out measures `transform IN.sam OUT.bam` (transform._BamOut) next to
@@ -532,6 +544,84 @@ def bench_reads2ref(a):
     print(json.dumps(res))
 
 
+def bench_aggregate(a):
+    """the --aggregate measurements (see the module doc)"""
+    import torch
+    from adam_amd import aggregate_pileups as AP
+    from adam_amd import reads2ref as R
+    t0 = time.perf_counter()
+    sam = synthetic_sam(a.reads, a.len)
+    log("generated %d bytes of SAM in %.1f s" % (len(sam), time.perf_counter() - t0))
+    torch.zeros(1, device="cuda")
+    work = a.dir or tempfile.mkdtemp(prefix="bench_aggregate_")
+    os.makedirs(work, exist_ok=True)
+    src, small = os.path.join(work, "in.sam"), os.path.join(work, "small.sam")
+    part_reads = a.part_reads if a.part_reads != 1 << 19 else R.DEFAULT_PART_READS
+
+    def timed(f):
+        t = time.perf_counter()
+        st = f()
+        return time.perf_counter() - t, st
+
+    try:
+        with open(src, "wb") as fh:
+            fh.write(sam)
+        n_small = min(a.reads, a.restatement_reads)
+        cut = 0
+        while sam[cut:cut + 1] == b"@":
+            cut = sam.index(b"\n", cut) + 1
+        for _ in range(n_small):
+            cut = sam.index(b"\n", cut) + 1
+        with open(small, "wb") as fh:
+            fh.write(sam[:cut])
+        del sam
+        out_r, out_a, out_s = (os.path.join(work, n) for n in ("r2r.adam", "agg.adam", "small.adam"))
+        r2r = lambda: R._reads2ref(src, out_r, a.compression, part_reads, a.partition_bytes, True, 0)
+        agg = lambda o=out_a, i=src: AP.aggregate_pileups(i, o, a.compression, partition_bytes=a.partition_bytes,
+                                                          overwrite=True, part_reads=part_reads)
+        log("warm-up runs")
+        r2r()
+        agg()
+        log("timed runs")
+        s_r, st_r = timed(r2r)
+        s_a, st_a = timed(agg)
+        size = lambda d: sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
+        res = {"metric": "adam aggregate_pileups SAM -> aggregated ADAMPileup Parquet next to adam reads2ref on the "
+                         "same reads: end-to-end seconds and phase split (host clock), the aggregation's stages by "
+                         "device events",
+               "reads": a.reads, "read_len": a.len, "compression": a.compression, "part_reads": part_reads,
+               "reads2ref": {"seconds": s_r, "rows": st_r["pileups"], "output_bytes": size(out_r),
+                             "phases_s": st_r["phases"]},
+               "aggregate_pileups": {"seconds": s_a, "rows_in": st_a["rows_in"], "rows_out": st_a["rows_out"],
+                                     "output_bytes": size(out_a), "phases_s": st_a["phases"],
+                                     "kernels_ms": st_a["kernel_ms"], "parts": st_a["parts"]},
+               "aggregate_over_reads2ref": s_a / s_r}
+        # the restatement, single-threaded, on the first reads; the command on the same reads must agree
+        if n_small:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import glob
+            import pyarrow as pa
+            import pyarrow.parquet as pq
+            from _adam_ref import convert_sam
+            from _pileup_agg_ref import aggregate
+            from _pileup_gen import assert_rows, run_date
+            from _pileup_ref import reads_to_pileups
+            with open(small, "rb") as fh:
+                text = fh.read()
+            s_p, want = timed(lambda: aggregate(reads_to_pileups(convert_sam(text, run_date))))
+            s_s, _ = timed(lambda: agg(out_s, small))
+            got = pa.concat_tables([pq.read_table(f) for f in sorted(glob.glob(os.path.join(out_s, "part-r-*.parquet")))])
+            assert_rows(got, want)
+            res["python_restatement"] = {"reads": n_small, "seconds": s_p, "rows_out": len(want),
+                                         "aggregate_pileups_seconds_same_reads": s_s}
+        log("reads2ref %.2f s (%d rows), aggregate_pileups %.2f s (%d -> %d rows), kernels %s"
+            % (s_r, st_r["pileups"], s_a, st_a["rows_in"], st_a["rows_out"], st_a["kernel_ms"]))
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps(res))
+
+
 def bench_bam_out(a):
     t0 = time.perf_counter()
     data = synthetic_sam(a.reads, a.len, p_q2tail=0.0)
@@ -606,6 +696,10 @@ def main():
                     help="measure transform SAM -> BAM next to SAM -> SAM text instead of the ADAM transform")
     ap.add_argument("--bam-level", type=int, default=6, help="--bam-out: the BGZF members' DEFLATE level")
     ap.add_argument("--reads2ref", action="store_true", help="measure adam reads2ref instead of the transform")
+    ap.add_argument("--aggregate", action="store_true",
+                    help="measure adam aggregate_pileups next to adam reads2ref instead of the transform")
+    ap.add_argument("--restatement-reads", type=int, default=200_000,
+                    help="--aggregate: reads the Python restatement is timed on (0: skip it)")
     ap.add_argument("--flagstat", action="store_true", help="measure adam flagstat instead of the transform")
     ap.add_argument("--print-tags", action="store_true", help="measure adam print_tags instead of the transform")
     ap.add_argument("--variant-lib", default=None,
@@ -631,6 +725,8 @@ def main():
         return bench_print_tags(a)
     if a.reads2ref:
         return bench_reads2ref(a)
+    if a.aggregate:
+        return bench_aggregate(a)
     if a.bam_out:
         return bench_bam_out(a)
     t0 = time.perf_counter()
