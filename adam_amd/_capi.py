@@ -44,6 +44,8 @@ EXPORTS = [
     "bqsr_arrow_pileup_agg_add", "bqsr_pileup_agg_run", "bqsr_pileup_agg_fetch", "bqsr_pileup_agg_kernel_times",
     "bqsr_sam_bam_prepare", "bqsr_sam_bam_records", "bqsr_sam_bam_header", "bqsr_bgzf_compress",
     "bqsr_bam_kernel_times",
+    "bqsr_bgzf_deflate", "bqsr_bgzf_deflate_host", "bqsr_sam_bam_members", "bqsr_deflate_code_lengths",
+    "bqsr_bgzf_deflate_times",
     "bqsr_compare_create", "bqsr_compare_destroy", "bqsr_compare_check_terms", "bqsr_compare_sam", "bqsr_compare_sides",
     "bqsr_compare_values", "bqsr_compare_baseqs", "bqsr_compare_rows", "bqsr_compare_kernel_times",
     "bqsr_sam_tag_counts", "bqsr_arrow_tag_counts", "bqsr_sam_tag_values", "bqsr_arrow_tag_values",

@@ -283,7 +283,7 @@ __device__ __forceinline__ int table_decode(Bits& b, const uint16_t* t) {
 constexpr uint32_t kCrcPoly = 0xEDB88320u;
 
 // a * b mod P, bit-reflected (bit 31 is x^0)
-__device__ __forceinline__ uint32_t crc_mult(uint32_t a, uint32_t b) {
+__host__ __device__ __forceinline__ uint32_t crc_mult(uint32_t a, uint32_t b) {
   uint32_t p = 0;
   for (uint32_t m = 1u << 31; m; m >>= 1) {
     if (a & m) p ^= b;
@@ -292,7 +292,7 @@ __device__ __forceinline__ uint32_t crc_mult(uint32_t a, uint32_t b) {
   return p;
 }
 // x^(8 n) mod P: squarings of x^8 (x2n[k] = x^(8 * 2^k))
-__device__ __forceinline__ uint32_t crc_x8n(const uint32_t* x2n, uint32_t n) {
+__host__ __device__ __forceinline__ uint32_t crc_x8n(const uint32_t* x2n, uint32_t n) {
   uint32_t p = 1u << 31;
   for (int k = 0; n; n >>= 1, ++k)
     if (n & 1u) p = crc_mult(x2n[k], p);

@@ -2178,6 +2178,7 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
 #include "mark_duplicates.cpp"
 #include "adam_out.hip"
 #include "bam_out.hip"
+#include "bgzf_deflate.hip"
 #include "sam_sort.hip"
 #include "flagstat.hip"
 #include "sam_batch.hip"

@@ -12,7 +12,9 @@ fields (the output path, core/rdd/AdamRDDFunctions.scala:37-56, as SAM text);
 ``.flagstat()`` counts the records as `adam flagstat` does (flagstat.py);
 ``.pileups()`` converts them to ADAMPileup records (reads2ref.py);
 ``.bam_header()`` / ``.bam_records()`` encode them as BAM on the device
-(bam_out.hip) and ``bgzf_compress`` cuts such a stream into BGZF members.
+(bam_out.hip) and ``bgzf_compress`` cuts such a stream into BGZF members on
+host threads; ``.bam_members()`` / ``bgzf_deflate`` do that on the device
+(bgzf_deflate.hip).
 """
 from __future__ import annotations
 
@@ -89,6 +91,12 @@ def _lib():
                                                      ctypes.POINTER(ctypes.c_double)]),
             "bqsr_bgzf_inflate": (ctypes.c_int, [vp, ctypes.c_char_p, i64, vp, vp, i64, ctypes.POINTER(i64), vp, i64,
                                                  ctypes.POINTER(i64)]),
+            "bqsr_bgzf_deflate": (ctypes.c_int, [vp, vp, i64, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+            "bqsr_bgzf_deflate_host": (ctypes.c_int, [vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+            "bqsr_sam_bam_members": (ctypes.c_int, [vp, vp, vp, vp, i64, ctypes.POINTER(i64)]),
+            "bqsr_deflate_code_lengths": (ctypes.c_int, [vp, i32, i32, vp]),
+            "bqsr_bgzf_deflate_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double),
+                                                       ctypes.POINTER(ctypes.c_double)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -255,6 +263,24 @@ class SamText:
         check(self.L.bqsr_sam_bam_records(self.ctx.handle, self.h, out.ctypes.data, stream))
         return out[:sz.bytes]
 
+    def bam_members(self, r0: int = 0, n: Optional[int] = None, stream=None) -> bytes:
+        """Records [r0, r0 + n) as BGZF members deflated on the device
+        (bqsr_sam_bam_prepare / _members: the encoded stream never leaves the
+        device, only the packed members come back).  They inflate to
+        ``bam_records(r0, n)``; zero records give zero bytes; no EOF member."""
+        if n is None:
+            n = self.counts().n_reads - r0
+        sz = BamSizes()
+        check(self.L.bqsr_sam_bam_prepare(self.ctx.handle, self.h, int(r0), int(n), stream, ctypes.byref(sz)))
+        return self._members(sz.bytes, stream)
+
+    def _members(self, stream_bytes: int, stream=None) -> bytes:
+        cap = stream_bytes + 64 * (stream_bytes // 65280 + 1)
+        out = np.empty(cap, np.uint8)
+        got = ctypes.c_int64()
+        check(self.L.bqsr_sam_bam_members(self.ctx.handle, self.h, stream, out.ctypes.data, cap, ctypes.byref(got)))
+        return out[:got.value].tobytes()
+
     def text(self) -> bytes:
         n = self.counts().text_bytes
         buf = ctypes.create_string_buffer(max(1, n))
@@ -302,6 +328,57 @@ def bgzf_compress(data, level: int = 6) -> bytes:
     got = ctypes.c_int64()
     check(L.bqsr_bgzf_compress(a.ctypes.data if n else None, n, int(level), out.ctypes.data, cap, ctypes.byref(got)))
     return out[:got.value].tobytes()
+
+
+def _bytes_array(data):
+    return np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+
+
+def bgzf_deflate(data, ctx: Optional[bqsr.Context] = None, stream=None) -> bytes:
+    """BGZF members of a byte stream, deflated on the device
+    (bqsr_bgzf_deflate): cut as ``bgzf_compress`` cuts it, one level, the
+    bytes a function of the input alone.  No EOF member."""
+    L = _lib()
+    ctx = ctx or bqsr.Context.get(0)
+    a = _bytes_array(data)
+    n = int(a.size)
+    cap = n + 64 * (n // 65280 + 1)
+    out = np.empty(cap, np.uint8)
+    got = ctypes.c_int64()
+    check(L.bqsr_bgzf_deflate(ctx.handle, a.ctypes.data if n else None, n, stream, out.ctypes.data, cap,
+                              ctypes.byref(got), None))
+    return out[:got.value].tobytes()
+
+
+def bgzf_deflate_host(data) -> bytes:
+    """``bgzf_deflate``'s bytes from the member routine compiled for the host
+    (bqsr_bgzf_deflate_host: no device; for tests, slow)."""
+    L = _lib()
+    a = _bytes_array(data)
+    n = int(a.size)
+    cap = n + 64 * (n // 65280 + 1)
+    out = np.empty(cap, np.uint8)
+    got = ctypes.c_int64()
+    check(L.bqsr_bgzf_deflate_host(a.ctypes.data if n else None, n, out.ctypes.data, cap, ctypes.byref(got), None))
+    return out[:got.value].tobytes()
+
+
+def deflate_code_lengths(freq, max_bits: int) -> np.ndarray:
+    """The code lengths the device encoder gives a histogram
+    (bqsr_deflate_code_lengths; host only): a uint8 array, 0 for an unused
+    symbol.  More than 2^max_bits symbols raise BQSRError (INVALID_ARG)."""
+    L = _lib()
+    f = np.ascontiguousarray(freq, np.uint32)
+    out = np.zeros(max(1, f.size), np.uint8)
+    check(L.bqsr_deflate_code_lengths(f.ctypes.data if f.size else None, int(f.size), int(max_bits), out.ctypes.data))
+    return out[:f.size]
+
+
+def bgzf_deflate_times():
+    """(member kernel ms, pack kernel ms) of this thread's last device deflate (measurement only)"""
+    a, b = ctypes.c_double(), ctypes.c_double()
+    check(_lib().bqsr_bgzf_deflate_times(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
 
 
 def bam_kernel_times():

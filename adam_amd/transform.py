@@ -4,12 +4,14 @@
     python -m adam_amd.transform INPUT.sam OUTPUT.sam [-mark_duplicate_reads]
         [-recalibrate_base_qualities] [-dbsnp_sites SITES.vcf]
     python -m adam_amd.transform INPUT.{adam,parquet,sam} OUTPUT.{adam,parquet} [...]
-    python -m adam_amd.transform INPUT.{sam,bam} OUTPUT.bam [-bam_compression_level N] [...]
+    python -m adam_amd.transform INPUT.{sam,bam} OUTPUT.bam [-bam_compression_level N]
+        [-bam_compressor {host,device}] [...]
 
 SAM or BAM in goes through the device path described below, out as SAM text,
 as BAM (an output name ending in .bam: the records encoded on the device,
 sam.SamText.bam_records, cut into BGZF members compressed by host threads,
-sam.bgzf_compress; see _BamOut) or as ADAMRecord Parquet part files (adamSave,
+sam.bgzf_compress, or with -bam_compressor device deflated on the device,
+sam.SamText.bam_members; see _BamOut) or as ADAMRecord Parquet part files (adamSave,
 adam_save.py).  BAM holds what the SAM spec allows: a record it cannot hold
 -- the reference's trimmed recalibrated QUAL strings and its chars above
 0x7F among them, which the SAM text sink writes as they are -- fails the job
@@ -415,31 +417,49 @@ class _SamOut:
 BAM_PIECE_READS = 1 << 19
 
 
+BAM_COMPRESSORS = ("host", "device")
+DEVICE_LEVEL_REFUSAL = ("-bam_compressor device has one level: it cannot be combined with an explicit "
+                        "-bam_compression_level")
+
+
 class _BamOut:
     """BAM output with _SamOut's contract (records appended partition by
     partition; the file appears when the job succeeds): the header once,
     then per emit the records in pieces of `piece_reads`, each encoded on the
     device (SamText.bam_records) and compressed into BGZF members by host
-    threads (sam.bgzf_compress) while the next piece is encoded and
-    downloaded; the EOF marker at close(ok=True).  A piece ends in a short
-    member."""
+    threads (sam.bgzf_compress, `level`: None is 6) while the next piece is
+    encoded and downloaded; the EOF marker at close(ok=True).  A piece ends in
+    a short member.  compressor="device": each piece's members come deflated
+    from the device (SamText.bam_members: the record stream is not downloaded)
+    and are written as they arrive, no compressor thread; the header member
+    stays on the host path; the device form has one level, so `level` must be
+    None."""
 
-    def __init__(self, path: str, level: int = 6, piece_reads: int = BAM_PIECE_READS, overwrite: bool = False):
+    def __init__(self, path: str, level: Optional[int] = None, piece_reads: int = BAM_PIECE_READS,
+                 overwrite: bool = False, compressor: str = "host"):
         from concurrent.futures import ThreadPoolExecutor
+        if compressor not in BAM_COMPRESSORS:
+            raise ValueError("-bam_compressor must be one of %s" % ", ".join(BAM_COMPRESSORS))
+        if compressor == "device" and level is not None:
+            raise ValueError(DEVICE_LEVEL_REFUSAL)
+        level = 6 if level is None else level
         if not 0 <= int(level) <= 9:
             raise ValueError("-bam_compression_level must be 0..9")
         _check_out(path, overwrite, False)
         self.path = path
         self.tmp = path + ".partial"
         self.level = int(level)
+        self.compressor = compressor
         self.piece_reads = max(1, int(piece_reads))
         self.fh = open(self.tmp, "wb")
         self.first = True
-        self.pool = ThreadPoolExecutor(1)
+        self.pool = ThreadPoolExecutor(1)  # (the header member, and the host compressor's pieces)
         self.pending = None
         # measured: the two kernels' device-event ms, stream / file bytes, seconds inside the compressor
+        # (device: inside bam_members, pass 2 and the download included), the deflate kernels' ms, bytes downloaded
         self.stats = {"len_ms": 0.0, "write_ms": 0.0, "record_bytes": 0, "text_bytes": 0, "file_bytes": 0,
-                      "compress_s": 0.0}
+                      "compress_s": 0.0, "compressor": compressor, "deflate_ms": 0.0, "pack_ms": 0.0,
+                      "downloaded_bytes": 0}
 
     def _compress(self, data):
         from .sam import bgzf_compress
@@ -473,12 +493,37 @@ class _BamOut:
         c = sam.counts()
         self.stats["text_bytes"] += c.text_bytes
         for r0 in range(0, c.n_reads, self.piece_reads):
-            rec = sam.bam_records(r0, min(self.piece_reads, c.n_reads - r0))
+            n = min(self.piece_reads, c.n_reads - r0)
+            if self.compressor == "device":
+                self._emit_device(sam, r0, n)
+                continue
+            rec = sam.bam_records(r0, n)
             a, b = bam_kernel_times()
             self.stats["len_ms"] += a
             self.stats["write_ms"] += b
             self.stats["record_bytes"] += int(rec.size)
+            self.stats["downloaded_bytes"] += int(rec.size)
             self._submit(rec)
+
+    def _emit_device(self, sam, r0: int, n: int):
+        """a piece deflated on the device (SamText.bam_members) and written as it arrives"""
+        from .sam import BamSizes, bam_kernel_times, bgzf_deflate_times
+        sz = BamSizes()
+        check(sam.L.bqsr_sam_bam_prepare(sam.ctx.handle, sam.h, int(r0), int(n), None, ctypes.byref(sz)))
+        t0 = time.perf_counter()
+        out = sam._members(sz.bytes)
+        self.stats["compress_s"] += time.perf_counter() - t0
+        a, b = bam_kernel_times()
+        d, p = bgzf_deflate_times()
+        self.stats["len_ms"] += a
+        self.stats["write_ms"] += b
+        self.stats["deflate_ms"] += d
+        self.stats["pack_ms"] += p
+        self.stats["record_bytes"] += int(sz.bytes)
+        self.stats["downloaded_bytes"] += len(out)
+        self._drain()  # (the header member goes first)
+        self.fh.write(out)
+        self.stats["file_bytes"] += len(out)
 
     def close(self, ok: bool = True):
         from .sam import BGZF_EOF
@@ -551,17 +596,25 @@ def is_bam(data) -> bool:
 def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bool = False,
               dbsnp: Optional[str] = None, device: int = 0, partition_bytes: int = DEFAULT_PARTITION_BYTES,
               compression: str = "gzip", part_reads: int = 1 << 19, overwrite: bool = False,
-              sort_reads: bool = False, bam_level: int = 6,
-              bam_piece_reads: int = BAM_PIECE_READS) -> Dict[str, float]:
+              sort_reads: bool = False, bam_level: Optional[int] = None,
+              bam_piece_reads: int = BAM_PIECE_READS, bam_compressor: Optional[str] = None) -> Dict[str, float]:
     """Transform.run (cli/Transform.scala:62-97) over SAM or BAM input: the
     records parsed on the device (a BAM's records become SAM lines there),
     MarkDuplicates, BQSR, then adamSave (OUT.adam / .parquet / a directory:
     ADAMRecord Parquet part files, adam_save.py), BAM (OUT.bam, _BamOut:
-    bam_level 0-9, records per encoded piece bam_piece_reads) or SAM text.
+    bam_level 0-9 (None: 6), records per encoded piece bam_piece_reads,
+    bam_compressor "host" (None) or "device": the BGZF members deflated on
+    the device, one level) or SAM text.
     ADAM Parquet input goes through transform_parquet (Arrow reads it on the
     host).  sort_reads: the records sorted on the device before the save (see
     the module doc); the input must be one partition."""
     bam_out = out.endswith(".bam")
+    if bam_compressor is not None and not bam_out:  # before anything is read
+        raise ValueError("-bam_compressor applies to BAM output only (an output name ending in .bam)")
+    if bam_compressor is not None and bam_compressor not in BAM_COMPRESSORS:
+        raise ValueError("-bam_compressor must be one of %s" % ", ".join(BAM_COMPRESSORS))
+    if bam_compressor == "device" and bam_level is not None:
+        raise ValueError(DEVICE_LEVEL_REFUSAL)
     if bam_out and is_parquet(inp):  # before anything is read
         raise ValueError("ADAM Parquet input cannot be written as BAM (no SAM lines to encode): "
                          "use a .adam / .parquet output, or SAM / BAM input")
@@ -580,7 +633,7 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
     # because `out` is some existing directory: the sinks refuse that)
     from .adam_save import is_adam_output
     adam_out = not bam_out and (out.endswith((".adam", ".parquet")) or is_adam_output(out))
-    sink = (_BamOut(out, bam_level, bam_piece_reads, overwrite) if bam_out
+    sink = (_BamOut(out, bam_level, bam_piece_reads, overwrite, bam_compressor or "host") if bam_out
             else _AdamOut(out, compression, part_reads, overwrite) if adam_out else _SamOut(out, overwrite))
     try:
         ctx = bqsr.Context.get(device)
@@ -670,17 +723,25 @@ def main(argv=None) -> int:
     ap.add_argument("-parquet_compression", default="gzip", choices=("gzip", "snappy", "zstd", "none"),
                     help="ADAM output: the part files' codec (adamSave's default: GZIP)")
     ap.add_argument("-part_reads", type=int, default=1 << 19, help="ADAM output: records per part file")
-    ap.add_argument("-bam_compression_level", type=int, default=6, choices=range(10), metavar="N",
+    ap.add_argument("-bam_compression_level", type=int, default=None, choices=range(10), metavar="N",
                     help="BAM output (OUTPUT.bam): the BGZF members' DEFLATE level, 0-9 (0: stored; default 6, "
-                         "zlib's and samtools')")
+                         "zlib's and samtools'); the host compressor's")
+    ap.add_argument("-bam_compressor", default=None, choices=BAM_COMPRESSORS,
+                    help="BAM output: who deflates the BGZF members: host threads (default) or the device "
+                         "(one level: not together with -bam_compression_level)")
     ap.add_argument("-overwrite", action="store_true",
                     help="replace an existing output (a file, or a directory of ADAM part files only)")
     a = ap.parse_args(argv)
     if a.realignIndels or a.coalesce != -1:
         ap.error("-coalesce / -realignIndels are outside this build")
+    if a.bam_compressor is not None and not a.output.endswith(".bam"):
+        ap.error("-bam_compressor applies to BAM output only (an output name ending in .bam)")
+    if a.bam_compressor == "device" and a.bam_compression_level is not None:
+        ap.error(DEVICE_LEVEL_REFUSAL)
     st = transform(a.input, a.output, a.mark_duplicate_reads, a.recalibrate_base_qualities, a.dbsnp_sites,
                    partition_bytes=a.partition_bytes, compression=a.parquet_compression, part_reads=a.part_reads,
-                   overwrite=a.overwrite, sort_reads=a.sort_reads, bam_level=a.bam_compression_level)
+                   overwrite=a.overwrite, sort_reads=a.sort_reads, bam_level=a.bam_compression_level,
+                   bam_compressor=a.bam_compressor)
     print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
     return 0
 

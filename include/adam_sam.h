@@ -322,6 +322,49 @@ bqsr_status bqsr_bgzf_compress(const uint8_t* in, int64_t n, int32_t level, uint
  * bqsr_sam_bam_records (pass 2) kernels, in milliseconds
  * (tools/bench_adam.py --bam-out). */
 bqsr_status bqsr_bam_kernel_times(double* len_ms, double* write_ms);
+/* BGZF members deflated on the device (bgzf_deflate.hip), the inverse of
+ * bqsr_bgzf_inflate: `in` (host memory) is uploaded, cut as bqsr_bgzf_compress
+ * cuts it (members of 65280 bytes, the last one short, none for n == 0, no
+ * EOF member) and every member compressed by one workgroup: LZ77 matches
+ * within the member only (distance <= 32768, length 3..258, runs included),
+ * a greedy parse, and the smallest of one dynamic-Huffman block, one
+ * fixed-Huffman block and one stored block (a member DEFLATE would not shrink
+ * is stored: 31 bytes more than its data); BSIZE in the BC field, CRC32 and
+ * ISIZE computed on the device.  The members are packed there and only the
+ * packed bytes come back.  The bytes are a function of the input alone (no
+ * level, no dependence on timing).  *out_len: the size, also when it exceeds
+ * cap (BQSR_ERR_INVALID_ARG then); n + 64 * (n / 65280 + 1) bytes always
+ * suffice.  *n_members (may be NULL): the members written. */
+bqsr_status bqsr_bgzf_deflate(bqsr_context* ctx, const uint8_t* in, int64_t n, void* stream, uint8_t* out, int64_t cap,
+                              int64_t* out_len, int64_t* n_members);
+/* The same member routine compiled for the host, a lane at a time: the bytes
+ * bqsr_bgzf_deflate gives, without a device call.  For tests on a machine
+ * without a GPU; far slower than bqsr_bgzf_compress. */
+bqsr_status bqsr_bgzf_deflate_host(const uint8_t* in, int64_t n, uint8_t* out, int64_t cap, int64_t* out_len,
+                                   int64_t* n_members);
+/* After bqsr_sam_bam_prepare, in place of bqsr_sam_bam_records: pass 2 into
+ * the device buffer, the float tags' values converted on the host as there
+ * (only the patch list and the texts are downloaded) and scattered into the
+ * device stream, then that stream deflated as bqsr_bgzf_deflate does it.  dst
+ * receives the members, which inflate to exactly the bytes
+ * bqsr_sam_bam_records hands out.  *out_len also when it exceeds cap
+ * (BQSR_ERR_INVALID_ARG); sizes.bytes + 64 * (sizes.bytes / 65280 + 1) bytes
+ * always suffice.  BQSR_ERR_INVALID_ARG when the text changed since the
+ * prepare. */
+bqsr_status bqsr_sam_bam_members(bqsr_context* ctx, bqsr_sam* s, void* stream, uint8_t* dst, int64_t cap,
+                                 int64_t* out_len);
+/* Host only, no device call: the code lengths the encoder gives a histogram
+ * (deflate_codes.h, the routine the kernel runs).  len_out[i]: 0 for
+ * freq[i] == 0, otherwise 1..max_bits; a single used symbol gets 1; with two
+ * or more the lengths form a complete code (Kraft sum 1), and where the plain
+ * Huffman code fits max_bits their cost is Huffman's.  BQSR_ERR_INVALID_ARG
+ * when n_syms > 2^max_bits or max_bits is outside 1..15. */
+bqsr_status bqsr_deflate_code_lengths(const uint32_t* freq, int32_t n_syms, int32_t max_bits, uint8_t* len_out);
+/* MEASUREMENT ONLY, not part of the stable interface: the device-event times
+ * of the calling thread's last device deflate (bqsr_bgzf_deflate or
+ * bqsr_sam_bam_members): the member kernel and the pack kernel, in
+ * milliseconds. */
+bqsr_status bqsr_bgzf_deflate_times(double* deflate_ms, double* pack_ms);
 
 /* MarkDuplicates (§8 f3): adam-core/.../rdd/MarkDuplicates.scala:24-111 over
  * SingleReadBucket (models/SingleReadBucket.scala:27-37: reads grouped by

@@ -54,7 +54,12 @@ strings; should a recalibrated char still leave '!'..'~' the refusal is
 reported and both legs rerun without BQSR).  Reads/s and the phase split of
 both legs, the two encoder kernels by device events with the bytes they move
 (pass 1 reads the record text; pass 2 reads it again and writes the records)
-as a fraction of 8 TB/s, and the compressor's MB/s of stream.  One JSON line.
+as a fraction of 8 TB/s, and the compressor's MB/s of stream.  Then, in the
+same run, the BAM leg again with the host compressor at level 1 and with the
+device compressor (-bam_compressor device: the deflate and pack kernels'
+device-event ms, GB/s of stream, the bytes downloaded, the file's size);
+every leg's --reps timed runs are all reported (seconds_all) with their
+spread.  One JSON line.
 
     python tools/bench_adam.py --print-tags [--reads 2000000] [--variant-lib LIB.so]
 
@@ -639,55 +644,76 @@ def bench_bam_out(a):
     del data
 
     def leg(out, recal, **kw):
-        best = None
+        best, times = None, []
         for i in range(1 + max(1, a.reps)):  # the first run warms
-            log("%s transform -> %s" % ("warm-up" if i == 0 else "timed", os.path.basename(out)))
+            log("%s transform -> %s %s" % ("warm-up" if i == 0 else "timed", os.path.basename(out), kw or ""))
             t = time.perf_counter()
             st = T.transform(src, out, mark_duplicates=not a.no_markdup, recalibrate=recal,
                              partition_bytes=a.partition_bytes, overwrite=True, **kw)
             dt = time.perf_counter() - t
-            if i and (best is None or dt < best[0]):
-                best = (dt, st)
+            if i:
+                times.append(dt)
+                if best is None or dt < best[0]:
+                    best = (dt, st)
         if best[1]["reads"] != a.reads:
             raise SystemExit("transformed %d reads, expected %d" % (best[1]["reads"], a.reads))
-        return best
+        return best[0], best[1], times
+
+    peak = 8e12
+
+    def bam_result(dt, st, times, path, what):
+        b = st["bam"]
+        k1 = b["text_bytes"] / (b["len_ms"] * 1e-3) if b["len_ms"] else None
+        moved2 = b["text_bytes"] + b["record_bytes"]
+        k2 = moved2 / (b["write_ms"] * 1e-3) if b["write_ms"] else None
+        ph = st.get("phases") or {}
+        r = {"seconds": dt, "seconds_all": times, "seconds_spread": max(times) - min(times),
+             "reads_per_s": a.reads / dt, "output_bytes": os.path.getsize(path), "compressor": what,
+             "phases_s": ph, "emit_s": ph.get("emit"), "close_s": ph.get("close"),
+             "record_bytes": b["record_bytes"], "downloaded_bytes": b["downloaded_bytes"],
+             "compress_s": b["compress_s"],
+             "compress_MB_per_s": b["record_bytes"] / b["compress_s"] / 1e6 if b["compress_s"] else None,
+             "kernels": {"len_ms": b["len_ms"], "len_bytes_read": b["text_bytes"], "len_bytes_per_s": k1,
+                         "len_share_of_8TBps": k1 / peak if k1 else None,
+                         "write_ms": b["write_ms"], "write_bytes_moved": moved2, "write_bytes_per_s": k2,
+                         "write_share_of_8TBps": k2 / peak if k2 else None}}
+        if b["compressor"] == "device":
+            ms = b["deflate_ms"] + b["pack_ms"]
+            r["kernels"].update({"deflate_ms": b["deflate_ms"], "pack_ms": b["pack_ms"],
+                                 "deflate_GB_per_s_of_stream": b["record_bytes"] / (ms * 1e-3) / 1e9 if ms else None})
+        return r
 
     try:
         recal, refused = True, None
+        out_bam = os.path.join(work, "out.bam")
         try:
-            bdt, bst = leg(os.path.join(work, "out.bam"), True, bam_level=a.bam_level)
+            bdt, bst, bts = leg(out_bam, True, bam_level=a.bam_level)
         except _capi.BQSRError as e:
             if e.status != _capi.UNSUPPORTED:
                 raise
             recal, refused = False, str(e)
-            log("BAM refused the recalibrated records (%s): both legs without BQSR" % e)
-            bdt, bst = leg(os.path.join(work, "out.bam"), False, bam_level=a.bam_level)
-        sdt, sst = leg(os.path.join(work, "out.sam"), recal)
-        bam_bytes = os.path.getsize(os.path.join(work, "out.bam"))
+            log("BAM refused the recalibrated records (%s): every leg without BQSR" % e)
+            bdt, bst, bts = leg(out_bam, False, bam_level=a.bam_level)
+        bam = bam_result(bdt, bst, bts, out_bam, "host threads, level %d" % a.bam_level)
+        bam["level"] = a.bam_level
+        sdt, sst, sts = leg(os.path.join(work, "out.sam"), recal)
         sam_bytes = os.path.getsize(os.path.join(work, "out.sam"))
+        # the host compressor at level 1 and the device compressor: the same run, the same input
+        l1 = bam_result(*leg(out_bam, recal, bam_level=1), out_bam, "host threads, level 1")
+        l1["level"] = 1
+        dev = bam_result(*leg(out_bam, recal, bam_compressor="device"), out_bam, "device")
     finally:
         if not a.dir:
             shutil.rmtree(work, ignore_errors=True)
-    b = bst["bam"]
-    peak = 8e12
-    k1 = b["text_bytes"] / (b["len_ms"] * 1e-3) if b["len_ms"] else None
-    moved2 = b["text_bytes"] + b["record_bytes"]
-    k2 = moved2 / (b["write_ms"] * 1e-3) if b["write_ms"] else None
     print(json.dumps({
-        "metric": "transform SAM -> BAM (records encoded on the device, BGZF members by host threads) next to "
-                  "SAM -> SAM text, same input, same run; %sMarkDuplicates%s" % (
+        "metric": "transform SAM -> BAM (records encoded on the device; BGZF members by host threads at two levels "
+                  "and by the device) next to SAM -> SAM text, same input, same run; %sMarkDuplicates%s" % (
                       "" if not a.no_markdup else "no ", ", BQSR" if recal else ", no BQSR"),
         "reads": a.reads, "read_len": a.len, "input_bytes": n_bytes, "recalibrate": recal, "refused": refused,
-        "bam": {"seconds": bdt, "reads_per_s": a.reads / bdt, "output_bytes": bam_bytes, "level": a.bam_level,
-                "phases_s": bst.get("phases"), "record_bytes": b["record_bytes"],
-                "compress_s": b["compress_s"],
-                "compress_MB_per_s": b["record_bytes"] / b["compress_s"] / 1e6 if b["compress_s"] else None,
-                "kernels": {"len_ms": b["len_ms"], "len_bytes_read": b["text_bytes"], "len_bytes_per_s": k1,
-                            "len_share_of_8TBps": k1 / peak if k1 else None,
-                            "write_ms": b["write_ms"], "write_bytes_moved": moved2, "write_bytes_per_s": k2,
-                            "write_share_of_8TBps": k2 / peak if k2 else None}},
-        "sam": {"seconds": sdt, "reads_per_s": a.reads / sdt, "output_bytes": sam_bytes,
-                "phases_s": sst.get("phases")}}))
+        "reps": max(1, a.reps),
+        "bam": bam, "bam_level1": l1, "bam_device": dev,
+        "sam": {"seconds": sdt, "seconds_all": sts, "seconds_spread": max(sts) - min(sts),
+                "reads_per_s": a.reads / sdt, "output_bytes": sam_bytes, "phases_s": sst.get("phases")}}))
 
 
 def main():
