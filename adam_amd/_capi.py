@@ -37,7 +37,7 @@ EXPORTS = [
     "bqsr_copy_dyn_async", "bqsr_compact_outputs_async", "bqsr_batch_exception_count_ptr",
     "bqsr_sort_order", "bqsr_sam_sort",  # include/adam_sam.h
     "bqsr_sam_flagstat", "bqsr_flagstat_arrow", "bqsr_flagstat_arrow_device",
-    "bqsr_bgzf_inflate", "bqsr_sam_bam_form",
+    "bqsr_bgzf_inflate", "bqsr_sam_bam_form", "bqsr_sam_markdup_path",
     "bqsr_sam_pileup_prepare", "bqsr_sam_pileup_columns", "bqsr_arrow_pileup_prepare", "bqsr_arrow_pileup_columns",
     "bqsr_pileup_kernel_times",
     "bqsr_pileup_agg_create", "bqsr_pileup_agg_destroy", "bqsr_pileup_agg_add_host", "bqsr_sam_pileup_agg_add",

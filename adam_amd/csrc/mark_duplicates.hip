@@ -289,31 +289,40 @@ bool markdup_host_forced() {
   }();
   return v;
 }
-bqsr_status mark_duplicates_device(bqsr_sam* s, int64_t* n_duplicates, std::vector<void*>& tmp, bool* fallback);
+bqsr_status mark_duplicates_device(bqsr_sam* s, int64_t* n_duplicates, std::vector<void*>& tmp, int* bad_word);
 }  // namespace
 
 // device path; a hash collision or a field beyond the packed keys falls back
-// to the host path (same rules, same order)
+// to the host path (same rules, same order); s->markdup_path says which ran
 bqsr_status bqsr_sam_mark_duplicates(bqsr_sam* s, int64_t* n_duplicates) {
   if (!s) return fail(BQSR_ERR_INVALID_ARG, "null");
   HIP_TRY(hipSetDevice(s->ctx->device));
+  s->markdup_path = -1;
   if (s->n_reads == 0) {
     s->dup_marked = true;
     s->flag_text_current = false;
+    s->markdup_path = 0;
     if (n_duplicates) *n_duplicates = 0;
     return ok();
   }
-  if (markdup_host_forced() || s->n_reads >= (1ll << 31) - 1) return mark_duplicates_host(s, n_duplicates);
+  if (markdup_host_forced() || s->n_reads >= (1ll << 31) - 1) {
+    const bqsr_status st = mark_duplicates_host(s, n_duplicates);
+    if (st == BQSR_OK) s->markdup_path = 8;
+    return st;
+  }
   std::vector<void*> tmp;
-  bool fallback = false;
-  const bqsr_status st = mark_duplicates_device(s, n_duplicates, tmp, &fallback);
+  int bad_word = 0;
+  bqsr_status st = mark_duplicates_device(s, n_duplicates, tmp, &bad_word);
   for (void* p : tmp) (void)hipFree(p);
-  if (st == BQSR_OK && fallback) return mark_duplicates_host(s, n_duplicates);
+  if (st == BQSR_OK && bad_word) st = mark_duplicates_host(s, n_duplicates);
+  if (st == BQSR_OK) s->markdup_path = bad_word & 7;
   return st;
 }
 
+int bqsr_sam_markdup_path(const bqsr_sam* s) { return s ? s->markdup_path : -1; }
+
 namespace {
-bqsr_status mark_duplicates_device(bqsr_sam* s, int64_t* n_duplicates, std::vector<void*>& tmp, bool* fallback) {
+bqsr_status mark_duplicates_device(bqsr_sam* s, int64_t* n_duplicates, std::vector<void*>& tmp, int* bad_word) {
   using namespace mdupd;
   const int64_t n = s->n_reads;
   // library ranks: LB strings of the read groups, sorted (1 + rank; 0 = no LB)
@@ -395,7 +404,7 @@ bqsr_status mark_duplicates_device(bqsr_sam* s, int64_t* n_duplicates, std::vect
   HIP_TRY(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (hbad) {  // a hash collision, or a position / library beyond the packed keys
-    *fallback = true;
+    *bad_word = hbad;
     return ok();
   }
   hipLaunchKernelGGL(mdup_mark, dim3(g), dim3(kThreads), 0, st, (const uint32_t*)idx2, (const uint32_t*)incl, n,

@@ -891,6 +891,7 @@ struct bqsr_sam {
   uint64_t* qual_span = nullptr;
   bool dup_marked = false;  // bqsr_sam_mark_duplicates ran: FLAG 0x400 rewritten on output
   bool flag_text_current = false;  // the text's FLAG fields carry MarkDuplicates' bits (rewritten since it ran)
+  int32_t markdup_path = -1;  // bqsr_sam_markdup_path: -1 not run, 0 the device, else why the host did it
   bool from_bam = false;    // bqsr_bam_parse: d_text holds the records converted to SAM text on the device
   int32_t bam_form = 0;     // bqsr_sam_bam_form: 1 the BGZF blocks inflated by host threads, 2 on the device
   samk::NameTable sq_tab{}, rg_tab{};  // @SQ / @RG name tables on the device (ADAM columns)

@@ -74,6 +74,7 @@ def _lib():
             "bqsr_sam_text_download": (ctypes.c_int, [vp, ctypes.c_char_p]),
             "bqsr_mark_duplicates": (ctypes.c_int, [ctypes.POINTER(DupReads), vp]),
             "bqsr_sam_mark_duplicates": (ctypes.c_int, [vp, ctypes.POINTER(i64)]),
+            "bqsr_sam_markdup_path": (ctypes.c_int, [vp]),
             "bqsr_sam_batch_create": (ctypes.c_int, [vp, vp, vp, i32, vp, pp]),
             "bqsr_dup_set_create": (ctypes.c_int, [vp, i64, pp]),
             "bqsr_dup_set_add": (ctypes.c_int, [vp, vp]),
@@ -182,6 +183,13 @@ class SamText:
         n = ctypes.c_int64()
         check(self.L.bqsr_sam_mark_duplicates(self.h, ctypes.byref(n)))
         return int(n.value)
+
+    def markdup_path(self) -> int:
+        """Which path served the last ``mark_duplicates()``
+        (bqsr_sam_markdup_path): -1 not run, 0 the device, otherwise the bits
+        of why the host form did it (1 hash collision, 2 contig or position
+        beyond the packed key, 4 library rank >= 4096, 8 forced)."""
+        return int(self.L.bqsr_sam_markdup_path(self.h))
 
     def rewrite(self, job=None) -> None:
         """The output text: every record's QUAL field replaced by the

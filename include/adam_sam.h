@@ -395,8 +395,20 @@ bqsr_status bqsr_mark_duplicates(const bqsr_dup_reads* reads, uint8_t* dup);
 /* The same over a parse (readName = QNAME, referenceId = the @SQ index,
  * mateMapped from FLAG 0x8, library = the read group's LB); the parse's
  * flags column gets BQSR_F_DUPLICATE set or cleared accordingly, as
- * `transform -mark_duplicate_reads` does before BQSR. */
+ * `transform -mark_duplicate_reads` does before BQSR.
+ * Runs on the device.  Its packed keys hold 32767 contigs (referenceId, the
+ * @SQ index, 0..32766) and 4095 distinct LB values among the header's read
+ * groups: a primary mapped read on a later contig, or a bucket whose library
+ * is the 4096th or later in sorted order, makes this call redo the work with
+ * the host form (the same result, slower); so does a 64-bit collision of the
+ * bucket hash.  bqsr_sam_markdup_path tells which ran. */
 bqsr_status bqsr_sam_mark_duplicates(bqsr_sam* s, int64_t* n_duplicates);
+/* Which path served the last bqsr_sam_mark_duplicates on this parse: -1 not
+ * run (or it failed), 0 the device, otherwise a bit mask of why the host form
+ * did it: 1 a hash collision between two buckets, 2 a contig or a position
+ * beyond the packed key, 4 a library rank of 4096 or more, 8 forced
+ * (ADAM_BQSR_MARKDUP=host, or 2^31 - 1 reads or more). */
+int bqsr_sam_markdup_path(const bqsr_sam* s);
 
 /* Sort by reference position (`transform -sort_reads`):
  * adamSortReadsByReferencePosition (adam-core/.../rdd/AdamRDDFunctions.scala:63-93)
@@ -870,7 +882,12 @@ bqsr_status bqsr_pileup_agg_kernel_times(double* keys_ms, double* sort_ms, doubl
  * hashes agree (names are not compared across partitions: a 128-bit
  * collision would merge two buckets).  BQSR_ERR_UNSUPPORTED for more than
  * 2^32 - 1 reads or positions / libraries beyond the packed keys;
- * BQSR_ERR_INVALID_ARG for partitions whose headers name other libraries. */
+ * BQSR_ERR_INVALID_ARG for partitions whose headers name other libraries.
+ * The packed keys' limits are bqsr_sam_mark_duplicates': 32767 contigs
+ * (referenceId 0..32766) and 4095 distinct LB values.  There is no host form
+ * here: when any read added is a primary mapped read on a later contig, or
+ * carries a library of rank 4096 or more, bqsr_dup_set_finish fails with
+ * BQSR_ERR_UNSUPPORTED and no read is marked. */
 typedef struct bqsr_dup_set bqsr_dup_set;
 bqsr_status bqsr_dup_set_create(bqsr_context* ctx, int64_t reads_hint, bqsr_dup_set** out);
 bqsr_status bqsr_dup_set_add(bqsr_dup_set* d, const bqsr_sam* s);

@@ -58,10 +58,15 @@ def score(r) -> int:
     return s
 
 
-def mark_duplicates(reads: List[dict], ties: Optional[list] = None) -> List[bool]:
+def mark_duplicates(reads: List[dict], ties: Optional[list] = None, stats: Optional[dict] = None) -> List[bool]:
     """MarkDuplicates.apply (:100-111).  `ties`, when a list, receives per
     scoreAndMarkReads call whose best score is shared the primary-read index
-    lists of the tied best buckets (the first of them kept here)."""
+    lists of the tied best buckets (the first of them kept here).  `stats`,
+    when a dict, receives what the input exercised: cross_contig_pairs
+    (buckets whose two positions lie on different contigs),
+    fragment_dups_in_paired_groups (primary reads of fragment buckets marked
+    because their group has pairs) and multi_right_groups (groups with two or
+    more distinct right positions)."""
     dup = [False] * len(reads)
     # SingleReadBucket.apply: groupBy (recordGroupId, readName); partition mapped / primary
     buckets: Dict[tuple, dict] = {}
@@ -84,6 +89,8 @@ def mark_duplicates(reads: List[dict], ties: Optional[list] = None) -> List[bool
                 left, right = (p1, p2) if p1 < p2 else (p2, p1)
             else:
                 left = p1
+        if stats is not None and right is not None and left[0] != right[0]:
+            stats["cross_contig_pairs"] = stats.get("cross_contig_pairs", 0) + 1
         first = (b["prim"] + b["sec"] + b["unm"])[0]
         keyed.append((left, right, reads[first]["library"], b))
 
@@ -119,9 +126,14 @@ def mark_duplicates(reads: List[dict], ties: Optional[list] = None) -> List[bool
             by_right.setdefault(right, []).append(b)
         fragments = by_right.get(None)
         has_pairs = any(k is not None for k in by_right)
+        if stats is not None and sum(k is not None for k in by_right) > 1:
+            stats["multi_right_groups"] = stats.get("multi_right_groups", 0) + 1
         if has_pairs:
             for b in fragments or []:
                 mark(b, True)
+                if stats is not None:
+                    stats["fragment_dups_in_paired_groups"] = (stats.get("fragment_dups_in_paired_groups", 0) +
+                                                               len(b["prim"]))
             for k, bs in by_right.items():
                 if k is not None:
                     score_and_mark(bs)

@@ -408,6 +408,7 @@ def test_mark_duplicates_device_equals_host(n_reads, contig_len):
     s = SamText(text)
     try:
         nd = s.mark_duplicates()
+        assert s.markdup_path() == 0  # the device did it: no fallback to the host form compared with
         got = (s.batch().flags & R.F_DUPLICATE) != 0
     finally:
         s.close()
