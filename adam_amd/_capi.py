@@ -21,6 +21,9 @@ STATUS_NAMES = ["OK", "NULL_RG", "MD_PARSE", "CIGAR_SHORT", "BAD_REVCOMP_BASE", 
                 "SAM_PARSE", "PILEUP", "ATTRIBUTE"]
 (NULL_RG, MD_PARSE, CIGAR_SHORT, BAD_REVCOMP_BASE, EMPTY_TABLE, MISSING_KEY, QUAL_RANGE, NULL_FIELD, SEQ_SHORT,
  CIGAR_INVALID, INVALID_ARG, DEVICE, UNSUPPORTED, SAM_PARSE, PILEUP, ATTRIBUTE) = range(1, 17)
+# the statuses `adam mpileup` added (include/adam_bqsr.h), numbered on from STATUS_NAMES
+MPILEUP_STATUS_NAMES = ["UNSORTED", "REFERENCE_CONFLICT"]
+UNSORTED, REFERENCE_CONFLICT = 17, 18
 
 # every symbol include/adam_bqsr.h declares
 EXPORTS = [
@@ -40,6 +43,8 @@ EXPORTS = [
     "bqsr_bgzf_inflate", "bqsr_sam_bam_form", "bqsr_sam_markdup_path",
     "bqsr_sam_pileup_prepare", "bqsr_sam_pileup_columns", "bqsr_arrow_pileup_prepare", "bqsr_arrow_pileup_columns",
     "bqsr_pileup_kernel_times",
+    "bqsr_sam_mpileup_prepare", "bqsr_sam_mpileup_text", "bqsr_arrow_mpileup_prepare", "bqsr_arrow_mpileup_text",
+    "bqsr_mpileup_kernel_times",
     "bqsr_pileup_agg_create", "bqsr_pileup_agg_destroy", "bqsr_pileup_agg_add_host", "bqsr_sam_pileup_agg_add",
     "bqsr_arrow_pileup_agg_add", "bqsr_pileup_agg_run", "bqsr_pileup_agg_fetch", "bqsr_pileup_agg_kernel_times",
     "bqsr_sam_bam_prepare", "bqsr_sam_bam_records", "bqsr_sam_bam_header", "bqsr_bgzf_compress",
@@ -61,7 +66,8 @@ class BQSRError(RuntimeError):
     """A status the C ABI returned; ``.status`` mirrors the JVM exception class."""
 
     def __init__(self, status: int, message: str = "", read: int = -1):
-        name = STATUS_NAMES[status] if 0 <= status < len(STATUS_NAMES) else str(status)
+        names = STATUS_NAMES + MPILEUP_STATUS_NAMES
+        name = names[status] if 0 <= status < len(names) else str(status)
         super().__init__("%s: %s" % (name, message))
         self.status = status
         self.name = name

@@ -58,7 +58,7 @@ class Context:
         """Set layout knobs (order: -1 auto / 0 read / 1 read-group buckets;
         fronts: -1 auto / 0 none / f; key_major: 1 / 0; bgzf: 1 device / 0 host
         inflate of BAM input; flagstat_grid: 0 auto / at most g workgroups for
-        the flagstat kernels; pileup_grid: the same for the reads2ref kernels);
+        the flagstat kernels; pileup_grid: the same for the reads2ref and mpileup kernels);
         returns the settings they replace."""
         cur = getattr(self, "_tuned", dict(self._DEFAULTS))
         prev = {}

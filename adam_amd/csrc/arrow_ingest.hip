@@ -309,6 +309,7 @@ struct bqsr_arrow {
   uint8_t* q_valid = nullptr;
   int64_t q_bytes = -1;
   std::shared_ptr<void> pileup;  // pileup scratch and columns (pileup.hip)
+  std::shared_ptr<void> mpileup, mpileup_names;  // mpileup's events and lines, its reference names (mpileup.hip)
   std::vector<void*> allocs;
   ~bqsr_arrow() {
     for (void* p : allocs) (void)hipFree(p);

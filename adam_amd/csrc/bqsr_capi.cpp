@@ -62,7 +62,7 @@ hipStream_t S(void* s) { return s ? (hipStream_t)s : hipStreamPerThread; }
 const char* kStatusNames[] = {"OK",          "NULL_RG",      "MD_PARSE",       "CIGAR_SHORT", "BAD_REVCOMP_BASE",
                               "EMPTY_TABLE", "MISSING_KEY",  "QUAL_RANGE",     "NULL_FIELD",  "SEQ_SHORT",
                               "CIGAR_INVALID", "INVALID_ARG", "DEVICE",        "UNSUPPORTED", "SAM_PARSE",
-                              "PILEUP",      "ATTRIBUTE"};
+                              "PILEUP",      "ATTRIBUTE",    "UNSORTED",       "REFERENCE_CONFLICT"};
 
 // map a device error key to (status, read) and record the message
 bqsr_status from_err_key(unsigned long long k, int64_t read_base) {
@@ -479,7 +479,7 @@ int bqsr_abi_version(void) { return BQSR_ABI_VERSION; }
 const char* bqsr_last_error(void) { return g_err.c_str(); }
 int64_t bqsr_last_error_read(void) { return g_err_read; }
 const char* bqsr_status_name(bqsr_status s) {
-  if ((int)s < 0 || (int)s > 16) return "UNKNOWN";
+  if ((int)s < 0 || (int)s > 18) return "UNKNOWN";
   return kStatusNames[(int)s];
 }
 
@@ -2184,6 +2184,7 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
 #include "sam_batch.hip"
 #include "arrow_ingest.hip"
 #include "pileup.hip"
+#include "mpileup.hip"
 #include "pileup_agg.hip"
 #include "compare.hip"
 #include "tags.hip"

@@ -249,6 +249,31 @@ __device__ int walk_read(const CountParams& P, int64_t i, int64_t r, uint64_t* r
   return 0;
 }
 
+// mapq of read r (SAMRecordConverter.scala:46-54: only with a reference, and
+// not 255; Arrow: the column's entry); false: null
+__device__ __forceinline__ bool read_mapq(const Reads& R, int64_t r, int32_t* out) {
+  int32_t q = 0;
+  bool has = false;
+  if (R.text) {
+    const int64_t e = (int64_t)R.line_span[2 * r + 1];
+    int64_t p = (int64_t)R.line_span[2 * r], a4 = 0, b4 = 0;
+    for (int k = 0; k < 5; ++k) {  // MAPQ is field 5 of the line (the parse saw 11 fields)
+      const int64_t fa = p;
+      while (p < e && R.text[p] != '\t') ++p;
+      if (k == 4) a4 = fa, b4 = p;
+      if (p < e) ++p;
+    }
+    int64_t v;
+    has = adamk::mapq_field(R.text, a4, b4, R.sq_id[r], &v);
+    q = has ? (int32_t)v : 0;
+  } else if (R.in_mapq_ok && R.in_mapq_ok[r]) {
+    has = true;
+    q = R.in_mapq[r];
+  }
+  *out = q;
+  return has;
+}
+
 extern "C" __global__ void __launch_bounds__(kThreads) pileup_count(CountParams P) {
   const Reads& R = P.R;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < P.n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -257,25 +282,8 @@ extern "C" __global__ void __launch_bounds__(kThreads) pileup_count(CountParams 
     const int st = walk_read(P, i, r, &rows);
     P.X.cnt[i] = st ? 0 : rows;
     if (st) atomicMin(P.err, ((unsigned long long)i << 8) | (unsigned long long)st);
-    // mapq (SAMRecordConverter.scala:46-54: only with a reference, and not 255)
-    int32_t q = 0;
-    bool has = false;
-    if (R.text) {
-      const int64_t e = (int64_t)R.line_span[2 * r + 1];
-      int64_t p = (int64_t)R.line_span[2 * r], a4 = 0, b4 = 0;
-      for (int k = 0; k < 5; ++k) {  // MAPQ is field 5 of the line (the parse saw 11 fields)
-        const int64_t fa = p;
-        while (p < e && R.text[p] != '\t') ++p;
-        if (k == 4) a4 = fa, b4 = p;
-        if (p < e) ++p;
-      }
-      int64_t v;
-      has = adamk::mapq_field(R.text, a4, b4, R.sq_id[r], &v);
-      q = has ? (int32_t)v : 0;
-    } else if (R.in_mapq_ok && R.in_mapq_ok[r]) {
-      has = true;
-      q = R.in_mapq[r];
-    }
+    int32_t q;
+    const bool has = read_mapq(R, r, &q);
     P.X.mapq[i] = q;
     P.X.mapq_ok[i] = has;
   }
@@ -648,6 +656,46 @@ PileupView pileup_view(const bqsr_arrow* a, const PileupState& A) {
   return V;
 }
 
+// the mapq column of an Arrow handle's reads (per chunk, host memory) onto the
+// device, replacing an earlier one
+bqsr_status pileup_arrow_mapq(bqsr_context* ctx, bqsr_arrow* a, PileupState& A, const int64_t* chunk_reads,
+                              const int32_t* const* mapq, const uint8_t* const* mapq_validity, int32_t n_chunks,
+                              hipStream_t s, const char* who) {
+  int64_t tot = 0;
+  for (int32_t c = 0; c < n_chunks; ++c) {
+    if (chunk_reads[c] < 0) return fail(BQSR_ERR_INVALID_ARG, std::string(who) + ": negative chunk length");
+    tot += chunk_reads[c];
+  }
+  if (tot != a->n) return fail(BQSR_ERR_INVALID_ARG, std::string(who) + ": the mapq chunks do not cover the reads");
+  A.a_loaded = false;
+  const size_t N = (size_t)std::max<int64_t>(a->n, 1);
+  if (!A.a_mapq) HIP_TRY(hipMalloc((void**)&A.a_mapq, N * 4));
+  if (!A.a_mapq_ok) HIP_TRY(hipMalloc((void**)&A.a_mapq_ok, N));
+  HIP_TRY(hipMemsetAsync(A.a_mapq_ok, 0, N, s));
+  SortTmp T;
+  int64_t base = 0;
+  bqsr_status e;
+  for (int32_t c = 0; c < n_chunks; ++c) {
+    const int64_t m = chunk_reads[c];
+    if (m && mapq[c]) {  // (a NULL column: every mapq of the chunk null)
+      HIP_TRY(hipMemcpyAsync(A.a_mapq + base, mapq[c], (size_t)m * 4, hipMemcpyHostToDevice, s));
+      uint8_t* dv = nullptr;
+      if (mapq_validity[c]) {
+        if ((e = sam_alloc(T.v, &dv, (size_t)(m + 7) / 8)) != BQSR_OK) return e;
+        HIP_TRY(hipMemcpyAsync(dv, mapq_validity[c], (size_t)(m + 7) / 8, hipMemcpyHostToDevice, s));
+      }
+      hipLaunchKernelGGL(pilk::pileup_mapq_chunk, dim3(sam_grid(m, pilk::kThreads, ctx->n_cu * 8)),
+                         dim3(pilk::kThreads), 0, s, (const int32_t*)(A.a_mapq + base), (const uint8_t*)dv, m,
+                         A.a_mapq + base, A.a_mapq_ok + base);
+      HIP_TRY(hipGetLastError());
+    }
+    base += m;
+  }
+  HIP_TRY(hipStreamSynchronize(s));  // (the staging bitmaps are freed with T)
+  A.a_loaded = true;
+  return BQSR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -677,39 +725,9 @@ bqsr_status bqsr_arrow_pileup_prepare(bqsr_context* ctx, bqsr_arrow* a, int64_t 
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
   PileupState& A = *pileup_state(a->pileup);
-  if (n_chunks) {  // the mapq column of the handle's reads, replacing an earlier one
-    int64_t tot = 0;
-    for (int32_t c = 0; c < n_chunks; ++c) {
-      if (chunk_reads[c] < 0) return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_prepare: negative chunk length");
-      tot += chunk_reads[c];
-    }
-    if (tot != a->n) return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_prepare: the mapq chunks do not cover the reads");
-    A.a_loaded = false;
-    const size_t N = (size_t)std::max<int64_t>(a->n, 1);
-    if (!A.a_mapq) HIP_TRY(hipMalloc((void**)&A.a_mapq, N * 4));
-    if (!A.a_mapq_ok) HIP_TRY(hipMalloc((void**)&A.a_mapq_ok, N));
-    HIP_TRY(hipMemsetAsync(A.a_mapq_ok, 0, N, s));
-    SortTmp T;
-    int64_t base = 0;
-    bqsr_status e;
-    for (int32_t c = 0; c < n_chunks; ++c) {
-      const int64_t m = chunk_reads[c];
-      if (m && mapq[c]) {  // (a NULL column: every mapq of the chunk null)
-        HIP_TRY(hipMemcpyAsync(A.a_mapq + base, mapq[c], (size_t)m * 4, hipMemcpyHostToDevice, s));
-        uint8_t* dv = nullptr;
-        if (mapq_validity[c]) {
-          if ((e = sam_alloc(T.v, &dv, (size_t)(m + 7) / 8)) != BQSR_OK) return e;
-          HIP_TRY(hipMemcpyAsync(dv, mapq_validity[c], (size_t)(m + 7) / 8, hipMemcpyHostToDevice, s));
-        }
-        hipLaunchKernelGGL(pilk::pileup_mapq_chunk, dim3(sam_grid(m, pilk::kThreads, ctx->n_cu * 8)),
-                           dim3(pilk::kThreads), 0, s, (const int32_t*)(A.a_mapq + base), (const uint8_t*)dv, m,
-                           A.a_mapq + base, A.a_mapq_ok + base);
-        HIP_TRY(hipGetLastError());
-      }
-      base += m;
-    }
-    HIP_TRY(hipStreamSynchronize(s));  // (the staging bitmaps are freed with T)
-    A.a_loaded = true;
+  if (n_chunks) {
+    const bqsr_status e = pileup_arrow_mapq(ctx, a, A, chunk_reads, mapq, mapq_validity, n_chunks, s, "bqsr_arrow_pileup_prepare");
+    if (e != BQSR_OK) return e;
   }
   return pileup_prepare(ctx, A, pileup_view(a, A), r0, n, s, out, "reads2ref");
 }

@@ -315,6 +315,7 @@ class ArrowReads:
         del keep
         self.n_reads = n
         self.table = table  # (pileups: mapq and the read-level columns come from it)
+        self.markdup = markdup
 
     def device_batch(self, contigs: Optional[Sequence[str]] = None, stream=None) -> ctypes.c_void_p:
         """A BQSR batch of the reads (the caller owns it)."""
@@ -373,6 +374,14 @@ class ArrowReads:
         table is taken as loaded: reads2ref.locus_filter is the caller's."""
         from .reads2ref import arrow_pileups
         return arrow_pileups(self, r0, n, stream)
+
+    def mpileup(self, window_bytes: Optional[int] = None, stream=None):
+        """`adam mpileup` over the reads (bqsr_arrow_mpileup_*), as
+        ``SamText.mpileup``: an iterator over text windows.  Needs a load with
+        markdup=True (readName and referenceId); failedVendorQualityChecks is
+        not on the device: reads2ref.locus_filter is the caller's."""
+        from . import mpileup as M
+        return M.arrow_mpileup(self, M.DEFAULT_WINDOW_BYTES if window_bytes is None else window_bytes, stream)
 
     def close(self):
         if self.h:

@@ -249,6 +249,17 @@ class SamText:
         from .reads2ref import sam_pileups
         return sam_pileups(self, r0, n, stream=stream)
 
+    def mpileup(self, window_bytes: Optional[int] = None, stream=None):
+        """`adam mpileup` over the reads (bqsr_sam_mpileup_*,
+        core/util/PileupTraversable.scala:83-281): the pileup text, as an
+        iterator over windows of whole lines (bytes) of at most window_bytes
+        (mpileup.DEFAULT_WINDOW_BYTES).  LocusPredicate is applied to the
+        records; a read the reference throws on, a start that decreases
+        inside a run of one reference and a position whose events disagree
+        on the reference base raise BQSRError before the first window."""
+        from . import mpileup as M
+        return M.sam_mpileup(self, M.DEFAULT_WINDOW_BYTES if window_bytes is None else window_bytes, stream)
+
     def bam_header(self) -> bytes:
         """The BAM header of the parse (bqsr_sam_bam_header): magic, the
         header text unchanged, the @SQ lines as the reference list."""

@@ -62,7 +62,9 @@ typedef enum bqsr_status {
   BQSR_ERR_UNSUPPORTED = 13,     /* input outside what the device path handles          */
   BQSR_ERR_SAM_PARSE = 14,       /* malformed SAM text where read_sam / SAMRecordConverter throws (adam_sam.h) */
   BQSR_ERR_PILEUP = 15,          /* reads2ref: an exception inside Reads2PileupProcessor's CIGAR walk (adam_sam.h) */
-  BQSR_ERR_ATTRIBUTE = 16        /* print_tags: what AttributeUtils.parseAttribute throws at (adam_sam.h)    */
+  BQSR_ERR_ATTRIBUTE = 16,       /* print_tags: what AttributeUtils.parseAttribute throws at (adam_sam.h)    */
+  BQSR_ERR_UNSORTED = 17,        /* mpileup: a read starts before the kept read in front of it, same reference (adam_sam.h) */
+  BQSR_ERR_REFERENCE_CONFLICT = 18 /* mpileup: AssertionError, one position's events disagree on the reference base (adam_sam.h) */
 } bqsr_status;
 
 /* ADAMRecord boolean fields (adam-format/.../adam.avdl:28-38) and null-ness
@@ -160,7 +162,8 @@ void bqsr_context_destroy(bqsr_context* ctx);
  *                        so that a small input runs every wavefront through
  *                        many passes of its grid-stride loop (tests)
  *   BQSR_TUNE_PILEUP_GRID 0 auto, g > 0: at most g workgroups for the two
- *                        pileup kernels (adam_sam.h bqsr_sam_pileup_*), as
+ *                        pileup kernels (adam_sam.h bqsr_sam_pileup_*) and for
+ *                        every mpileup kernel (bqsr_sam_mpileup_*), as
  *                        BQSR_TUNE_FLAGSTAT_GRID */
 enum {
   BQSR_TUNE_ORDER = 1,

@@ -711,6 +711,96 @@ bqsr_status bqsr_arrow_pileup_columns(bqsr_context* ctx, bqsr_arrow* a, const bq
  * columns call, in milliseconds (tools/bench_adam.py --reads2ref). */
 bqsr_status bqsr_pileup_kernel_times(double* count_ms, double* emit_ms);
 
+/* `adam mpileup` (adam-cli/.../cli/MpileupCommand.scala:37-82 over
+ * PileupTraversable, adam-core/.../util/PileupTraversable.scala:83-281, with
+ * MdTag.scala:38-98, 247-269 and predicates/LocusPredicate.scala): the reads of
+ * a parse as pileup text, one line per (run of one referenceId, position).
+ *   Reads.  LocusPredicate is applied here, to SAM / BAM input as well, on the
+ *   record SAMRecordConverter produces: readMapped, primaryAlignment,
+ *   !duplicateRead from the flags column as it stands (bqsr_sam_mark_duplicates
+ *   changes duplicateRead), !failedVendorQualityChecks from FLAG 0x200; a
+ *   FLAG-0 record has every boolean false (quirk Q2) and is dropped.  A
+ *   bqsr_arrow handle carries no failedVendorQualityChecks: filter its table
+ *   before the upload (adam_amd/reads2ref.py locus_filter).  The kept reads, in
+ *   input order, are the job's reads; `read` in errors is the index in the
+ *   handle.
+ *   Events of a kept read (readToPileups).  Without CIGAR or MD: none.  Else
+ *   MdTag(md, start), referencePos = start, readPos = 0, and per element
+ *     M  per base a match where the MD says match (reference base = the read's
+ *        base), else a mismatch where the MD has a mismatch base (reference
+ *        base = the MD's, printed character = the read's base);
+ *     D  per base a delete, reference base = the MD's deleted base;
+ *     I  ONE insertion per element at the unchanged referencePos, no reference
+ *        base, carrying the read's whole sequence;
+ *     S N H P = X  nothing; both positions advance as the operator consumes
+ *        (after an N the MD is looked up in the wrong place, as in reads2ref).
+ *   Base is the five-value enum A C T G N: any other character in the sequence
+ *   (not upper-cased) or the MD (upper-cased) throws.
+ *   Segments.  A kept read whose referenceId differs from the kept read before
+ *   it starts a new segment (a reference that comes back is a new segment).
+ *   A line merges a position's events of one segment: matches, mismatches,
+ *   deletes, insertions, each in read order.
+ *   The line: name ' ' position(0-based) ' ' base-or-'?' ' ' numReads ' ', per
+ *   match '.' (',' reverse strand), per mismatch the read's base (lower case
+ *   on the reverse strand), per delete "-1" + the reference base, per insertion
+ *   '+' + the read sequence's length + the whole sequence, '\n'.  The name is
+ *   the referenceName of the position's first event.
+ * Declared where the reference is loose:
+ *   BQSR_ERR_UNSORTED            inside a segment a kept read's start is below
+ *     the start of the kept read before it (the reference asserts only against
+ *     the segment's first start, and prints positions twice otherwise);
+ *     bqsr_last_error_read = the read.
+ *   BQSR_ERR_REFERENCE_CONFLICT  a position's events disagree on the reference
+ *     base (the reference's AssertionError); the message names the reference
+ *     and the position, bqsr_last_error_read = the position.
+ *   On any failure there is no text.  A read-level exception wins (the first
+ *   such read in input order, that read's first exception in the reference's
+ *   evaluation order), then the lowest unsorted read, then the lowest
+ *   conflicting (segment, position).
+ * Read-level statuses: BQSR_ERR_NULL_FIELD for a NullPointerException (a kept
+ * read's null referenceId or start; a null readName, mapq -- a SAM MAPQ of 255
+ * --, qual, sequence or referenceName reached by an event); BQSR_ERR_MD_PARSE
+ * where MdTag.apply rejects the tag; BQSR_ERR_PILEUP for everything thrown
+ * inside the CIGAR walk (a character outside A C T G N, a sequence shorter than
+ * the walk, an M base the MD has as a delete or not at all, a D base without an
+ * MD delete).  BQSR_ERR_UNSUPPORTED: the per-read limits of reads2ref, a start
+ * below 0, more than 2^31 - 1 reads or events in one job, a key of segment,
+ * position and class beyond 64 bits, or an input whose events do not fit the
+ * device: one input stays resident per job (the message names the allocation).
+ * prepare: everything up to every line's byte offset (walk, scan, event emit,
+ * a stable radix sort by (segment, position, class), grouping); sizes out.
+ * text: the largest run of whole lines from line0 within `budget` bytes,
+ * formatted on the device and copied to dst (host memory, budget bytes);
+ * *n_lines and *n_bytes say what was written, both 0 at line0 = n_lines.  A
+ * first line longer than the budget is BQSR_ERR_INVALID_ARG, the message gives
+ * its size.  Device: adam_amd/csrc/mpileup.hip. */
+typedef struct bqsr_mpileup_sizes {
+  int64_t n_reads;    /* reads LocusPredicate keeps */
+  int64_t n_events;
+  int64_t n_lines;
+  int64_t text_bytes; /* of all lines */
+} bqsr_mpileup_sizes;
+bqsr_status bqsr_sam_mpileup_prepare(bqsr_context* ctx, bqsr_sam* s, void* stream, bqsr_mpileup_sizes* out);
+bqsr_status bqsr_sam_mpileup_text(bqsr_context* ctx, bqsr_sam* s, int64_t line0, int64_t budget, char* dst,
+                                  void* stream, int64_t* n_lines, int64_t* n_bytes);
+/* The same over a bqsr_arrow handle loaded with MarkDuplicates' columns
+ * (readName's validity and referenceId come with them; without them every
+ * readName is null and referenceId is the referenceName index).  mapq as
+ * bqsr_arrow_pileup_prepare takes it (kept with the handle, shared with it).
+ * ref_names: the strings the handle's referenceName indices
+ * (bqsr_arrow_chunk.reference) stand for.  A null boolean reads as false. */
+bqsr_status bqsr_arrow_mpileup_prepare(bqsr_context* ctx, bqsr_arrow* a, const int64_t* chunk_reads,
+                                       const int32_t* const* mapq, const uint8_t* const* mapq_validity,
+                                       int32_t n_chunks, const char* const* ref_names, int32_t n_ref_names,
+                                       void* stream, bqsr_mpileup_sizes* out);
+bqsr_status bqsr_arrow_mpileup_text(bqsr_context* ctx, bqsr_arrow* a, int64_t line0, int64_t budget, char* dst,
+                                    void* stream, int64_t* n_lines, int64_t* n_bytes);
+/* MEASUREMENT ONLY, not part of the stable interface: device-event times, in
+ * milliseconds, of the calling thread's last prepare (ms5[0] keep / compact /
+ * walk, [1] event emit, [2] sort, [3] grouping) and last text call ([4] the
+ * text kernel) (tools/bench_adam.py --mpileup). */
+bqsr_status bqsr_mpileup_kernel_times(double* ms5);
+
 /* `adam aggregate_pileups` and what `reads2ref -aggregate` would compute
  * (adam-cli/.../cli/PileupAggregator.scala:27-57 over PileupAggregator.
  * aggregate, adam-core/.../rdd/PileupAggregator.scala:25-219): ADAMPileup rows

@@ -63,6 +63,19 @@ spread.  One JSON line.
 
     python tools/bench_adam.py --print-tags [--reads 2000000] [--variant-lib LIB.so]
 
+--mpileup measures `adam mpileup` (adam_amd/mpileup.py) over the same
+synthetic reads after `transform -sort_reads`.  The generator draws every
+read's bases and MD on its own, so overlapping reads disagree on the reference
+base, which mpileup refuses as the reference asserts: of the reads
+LocusPredicate keeps, those that overlap the kept read before them are left
+out.  Once each after a warm-up, in this process: mpileup and reads2ref on
+that file (end-to-end seconds, phase split, mpileup's stages by device
+events), then the single-threaded Python restatement (tests/_mpileup_ref.py)
+on the first --restatement-reads reads, whose text the command must equal.
+One JSON line.
+
+    python tools/bench_adam.py --mpileup [--reads 2000000]
+
 --print-tags measures `adam print_tags` (adam_amd/print_tags.py) over the same
 synthetic reads as SAM text with aligner-like fields appended to every line
 (NM:i, AS:i, XS:i, and XA:Z on about 5 % of the lines; samgen alone writes MD
@@ -549,6 +562,121 @@ def bench_reads2ref(a):
     print(json.dumps(res))
 
 
+def _thin_to_one_reference(sam: bytes):
+    """(text, kept): the sorted SAM text without the reads LocusPredicate would
+    keep that overlap the read kept before them.  The generator draws every
+    read's bases and MD on its own, so two reads over one position disagree on
+    the reference base there -- which `adam mpileup` refuses
+    (REFERENCE_CONFLICT), as the reference asserts."""
+    import re
+    el = re.compile(rb"([0-9]+)([MIDNSHP=X])")
+    out, kept, last_ref, last_end = [], 0, None, -1
+    for line in sam.split(b"\n"):
+        if not line:
+            continue
+        if line.startswith(b"@"):
+            out.append(line)
+            continue
+        f = line.split(b"\t", 6)
+        flag = int(f[1])
+        if flag == 0 or flag & (0x4 | 0x100 | 0x200 | 0x400):  # LocusPredicate drops it anyway
+            out.append(line)
+            continue
+        start = int(f[3]) - 1
+        end = start + sum(int(n) for n, op in el.findall(f[5]) if op in b"MDN=X")
+        if f[2] == last_ref and start < last_end:
+            continue
+        last_ref, last_end = f[2], end
+        kept += 1
+        out.append(line)
+    return b"\n".join(out) + b"\n", kept
+
+
+def bench_mpileup(a):
+    """the --mpileup measurements (see the module doc)"""
+    import torch
+    from adam_amd import mpileup as M
+    from adam_amd import reads2ref as R
+    from adam_amd.transform import transform
+    t0 = time.perf_counter()
+    sam = synthetic_sam(a.reads, a.len)
+    log("generated %d bytes of SAM in %.1f s" % (len(sam), time.perf_counter() - t0))
+    torch.zeros(1, device="cuda")
+    work = a.dir or tempfile.mkdtemp(prefix="bench_mpileup_")
+    os.makedirs(work, exist_ok=True)
+    raw, srt, src, small = (os.path.join(work, n) for n in ("raw.sam", "sorted.sam", "in.sam", "small.sam"))
+    part_reads = a.part_reads if a.part_reads != 1 << 19 else R.DEFAULT_PART_READS
+
+    def timed(f):
+        t = time.perf_counter()
+        st = f()
+        return time.perf_counter() - t, st
+
+    try:
+        with open(raw, "wb") as fh:
+            fh.write(sam)
+        del sam
+        s_sort, _ = timed(lambda: transform(raw, srt, sort_reads=True, partition_bytes=a.partition_bytes,
+                                            overwrite=True))
+        with open(srt, "rb") as fh:
+            text, kept = _thin_to_one_reference(fh.read())
+        n_lines = text.count(b"\n") - sum(1 for l in text.split(b"\n", 64)[:64] if l.startswith(b"@"))
+        log("sorted in %.1f s; %d reads left, %d of them kept by LocusPredicate" % (s_sort, n_lines, kept))
+        with open(src, "wb") as fh:
+            fh.write(text)
+        n_small = min(n_lines, a.restatement_reads)
+        cut = 0
+        while text[cut:cut + 1] == b"@":
+            cut = text.index(b"\n", cut) + 1
+        for _ in range(n_small):
+            cut = text.index(b"\n", cut) + 1
+        small_text = text[:cut]
+        with open(small, "wb") as fh:
+            fh.write(small_text)
+        del text
+        out_m, out_r, out_s = (os.path.join(work, n) for n in ("mpileup.txt", "r2r.adam", "small.txt"))
+        mp = lambda i=src, o=out_m: M.mpileup(i, o)
+        r2r = lambda: R._reads2ref(src, out_r, a.compression, part_reads, a.partition_bytes, True, 0)
+        log("warm-up runs")
+        mp()
+        r2r()
+        log("timed runs")
+        s_m, st_m = timed(mp)
+        s_r, st_r = timed(r2r)
+        size = lambda d: sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
+        res = {"metric": "adam mpileup SAM -> pileup text next to adam reads2ref on the same reads, one run each after "
+                         "a warm-up in one process: end-to-end seconds and phase split (host clock), mpileup's stages "
+                         "by device events",
+               "input": "%d synthetic reads of %d bases, transform -sort_reads, then without the LocusPredicate-kept "
+                        "reads that overlap the kept read before them (the generator's reads do not share a "
+                        "reference: overlapping ones are a REFERENCE_CONFLICT)" % (a.reads, a.len),
+               "reads": n_lines, "read_len": a.len, "input_bytes": os.path.getsize(src),
+               "mpileup": {"seconds": s_m, "kept_reads": st_m["kept"], "events": st_m["events"],
+                           "lines": st_m["lines"], "text_bytes": st_m["bytes"], "phases_s": st_m["phases"],
+                           "kernels_ms": st_m["kernel_ms"], "window_bytes": M.DEFAULT_WINDOW_BYTES,
+                           "events_per_s": st_m["events"] / s_m if s_m else None},
+               "reads2ref": {"seconds": s_r, "rows": st_r["pileups"], "output_bytes": size(out_r),
+                             "compression": a.compression, "phases_s": st_r["phases"]},
+               "mpileup_over_reads2ref": s_m / s_r}
+        # the restatement, single-threaded, on the first reads; the command on the same reads must agree
+        if n_small:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            from _adam_ref import convert_sam
+            from _mpileup_ref import mpileup as restated
+            s_p, want = timed(lambda: restated(convert_sam(small_text)).encode("latin-1"))
+            s_s, _ = timed(lambda: mp(small, out_s))
+            with open(out_s, "rb") as fh:
+                assert fh.read() == want, "the command and the restatement differ"
+            res["python_restatement"] = {"reads": n_small, "seconds": s_p, "text_bytes": len(want),
+                                         "mpileup_seconds_same_reads": s_s}
+        log("mpileup %.2f s (%d events, %d lines), reads2ref %.2f s (%d rows), kernels %s"
+            % (s_m, st_m["events"], st_m["lines"], s_r, st_r["pileups"], st_m["kernel_ms"]))
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps(res))
+
+
 def bench_aggregate(a):
     """the --aggregate measurements (see the module doc)"""
     import torch
@@ -724,6 +852,8 @@ def main():
     ap.add_argument("--reads2ref", action="store_true", help="measure adam reads2ref instead of the transform")
     ap.add_argument("--aggregate", action="store_true",
                     help="measure adam aggregate_pileups next to adam reads2ref instead of the transform")
+    ap.add_argument("--mpileup", action="store_true",
+                    help="measure adam mpileup next to adam reads2ref instead of the transform")
     ap.add_argument("--restatement-reads", type=int, default=200_000,
                     help="--aggregate: reads the Python restatement is timed on (0: skip it)")
     ap.add_argument("--flagstat", action="store_true", help="measure adam flagstat instead of the transform")
@@ -749,6 +879,8 @@ def main():
         return bench_flagstat(a)
     if a.print_tags:
         return bench_print_tags(a)
+    if a.mpileup:
+        return bench_mpileup(a)
     if a.reads2ref:
         return bench_reads2ref(a)
     if a.aggregate:
