@@ -45,6 +45,8 @@ EXPORTS = [
     "bqsr_pileup_kernel_times",
     "bqsr_sam_mpileup_prepare", "bqsr_sam_mpileup_text", "bqsr_arrow_mpileup_prepare", "bqsr_arrow_mpileup_text",
     "bqsr_mpileup_kernel_times",
+    "bqsr_sam_realign_targets_prepare", "bqsr_sam_realign_targets_fetch", "bqsr_arrow_realign_targets_prepare",
+    "bqsr_arrow_realign_targets_fetch", "bqsr_realign_targets_kernel_times",
     "bqsr_pileup_agg_create", "bqsr_pileup_agg_destroy", "bqsr_pileup_agg_add_host", "bqsr_sam_pileup_agg_add",
     "bqsr_arrow_pileup_agg_add", "bqsr_pileup_agg_run", "bqsr_pileup_agg_fetch", "bqsr_pileup_agg_kernel_times",
     "bqsr_sam_bam_prepare", "bqsr_sam_bam_records", "bqsr_sam_bam_header", "bqsr_bgzf_compress",

@@ -310,6 +310,7 @@ struct bqsr_arrow {
   int64_t q_bytes = -1;
   std::shared_ptr<void> pileup;  // pileup scratch and columns (pileup.hip)
   std::shared_ptr<void> mpileup, mpileup_names;  // mpileup's events and lines, its reference names (mpileup.hip)
+  std::shared_ptr<void> realign_targets;  // realignment targets' rows, events and results (realign_targets.hip)
   std::vector<void*> allocs;
   ~bqsr_arrow() {
     for (void* p : allocs) (void)hipFree(p);

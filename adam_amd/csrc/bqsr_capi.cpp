@@ -2185,6 +2185,7 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
 #include "arrow_ingest.hip"
 #include "pileup.hip"
 #include "mpileup.hip"
+#include "realign_targets.hip"
 #include "pileup_agg.hip"
 #include "compare.hip"
 #include "tags.hip"

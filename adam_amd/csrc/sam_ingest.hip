@@ -899,6 +899,7 @@ struct bqsr_sam {
   void* adam = nullptr;     // ADAM column buffers (adam_out.hip), freed with the handle
   std::shared_ptr<void> pileup;  // pileup scratch and columns (pileup.hip)
   std::shared_ptr<void> mpileup; // mpileup's events and lines (mpileup.hip)
+  std::shared_ptr<void> realign_targets;  // realignment targets' rows, events and results (realign_targets.hip)
   std::shared_ptr<void> bam;     // BAM record buffers (bam_out.hip)
   std::vector<void*> allocs;
   ~bqsr_sam();

@@ -383,6 +383,13 @@ class ArrowReads:
         from . import mpileup as M
         return M.arrow_mpileup(self, M.DEFAULT_WINDOW_BYTES if window_bytes is None else window_bytes, stream)
 
+    def realignment_targets(self, stream=None):
+        """RealignmentTargetFinder over the reads
+        (bqsr_arrow_realign_targets_*), as ``SamText.realignment_targets``;
+        the table as given, no LocusPredicate."""
+        from . import realignment_targets as RT
+        return RT.arrow_targets(self, stream)
+
     def close(self):
         if self.h:
             self.L.bqsr_arrow_destroy(self.h)

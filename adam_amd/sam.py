@@ -260,6 +260,15 @@ class SamText:
         from . import mpileup as M
         return M.sam_mpileup(self, M.DEFAULT_WINDOW_BYTES if window_bytes is None else window_bytes, stream)
 
+    def realignment_targets(self, stream=None):
+        """RealignmentTargetFinder over the reads (bqsr_sam_realign_targets_*,
+        core/algorithms/realignmenttarget/RealignmentTargetFinder.scala:54-101):
+        the indel realignment targets as a dict of int64 arrays
+        (realignment_targets.COLUMNS).  No LocusPredicate; a read the pileup
+        walk throws on raises BQSRError."""
+        from . import realignment_targets as RT
+        return RT.sam_targets(self, stream)
+
     def bam_header(self) -> bytes:
         """The BAM header of the parse (bqsr_sam_bam_header): magic, the
         header text unchanged, the @SQ lines as the reference list."""

@@ -801,6 +801,98 @@ bqsr_status bqsr_arrow_mpileup_text(bqsr_context* ctx, bqsr_arrow* a, int64_t li
  * text kernel) (tools/bench_adam.py --mpileup). */
 bqsr_status bqsr_mpileup_kernel_times(double* ms5);
 
+/* Indel realignment targets: stage 1 of RealignIndels.realignIndels,
+ * RealignmentTargetFinder(reads) (adam-core/.../algorithms/realignmenttarget/
+ * RealignmentTargetFinder.scala:54-101 over IndelRealignmentTarget.scala:41-101,
+ * 126-165, 194-231, 251-437).  One job over all reads of a handle.
+ *   Rows.  reads.adamRecords2Pileup(): exactly the ADAMPileup rows of
+ *   bqsr_sam_pileup_* over all reads, with the same exceptions in the same
+ *   order.  No LocusPredicate, for any input: an unmapped or FLAG-0 read (quirk
+ *   Q2) that has a CIGAR and an MD fails the job with BQSR_ERR_PILEUP.
+ *   Rods.  Rows are grouped by position ALONE (groupBy(_.getPosition)): equal
+ *   positions on two references share a rod, as in the reference.
+ *   Per rod (IndelRealignmentTarget.apply).  indels: the rows with a
+ *   rangeOffset (I, D and S rows: soft clips count).  matches / mismatches: the
+ *   rows without one and numSoftClipped == 0, readBase == / != referenceBase.
+ *   matchQuality, mismatchQuality: sums of sangerQuality as Java Ints (they
+ *   wrap at 32 bits; empty: 0).  The mismatches are SNP evidence iff
+ *   matchQuality == 0 || (double)mismatchQuality / (double)matchQuality >= 0.15
+ *   (IEEE double; a negative ratio is below).  Every indel row gives
+ *   IndelRange(indelRange, readRange): readRange = [readStart, readEnd - 1];
+ *   indelRange = [position - rangeOffset, position + rangeLength - rangeOffset
+ *   - 1] for a delete (readBase null), [position, position] otherwise.  Every
+ *   mismatch row of a rod that keeps SNP evidence gives SNPRange(position,
+ *   readRange).  Both are sets: equal tuples collapse (the rows of one
+ *   multi-base insertion are one range).  A rod with both sets empty is
+ *   dropped; the others are candidates, their range the hull of their
+ *   elements' read ranges.
+ *   The fold (joinTargets over singletons), left to right over the candidates
+ *   in DECLARED order, ascending by (range start, position) -- the reference
+ *   sorts by start and leaves ties to Spark, and the result depends on them.
+ *   With a the last target so far and b the candidate: if
+ *   TargetOrdering.overlap(a, b) -- its four clauses as written; a partial
+ *   overlap is none: [1,20] then [10,30] stay two -- a = a.merge(b), else b is
+ *   a new target.  merge unites the SNP sets, and sorts the united indel set
+ *   and collapses runs of equal indelRange into one range with the hull of
+ *   their read ranges.  A target from a single rod never went through merge
+ *   and keeps two ranges with equal indelRange and different read ranges.
+ *   DECLARED element order (the reference has hash sets): targets ascend by
+ *   start (the fold gives that); a target's indel ranges by (indel_start,
+ *   indel_end, indel_read_start, indel_read_end); its SNP ranges by (snp_site,
+ *   snp_read_start, snp_read_end).
+ * Read-level statuses are those of bqsr_sam_pileup_prepare (NULL_FIELD,
+ * MD_PARSE, PILEUP, UNSUPPORTED): the first throwing read in input order
+ * decides and bqsr_last_error_read names it.  BQSR_ERR_UNSUPPORTED also: a read
+ * with rows and start < 0 (positions are sort-key bits) or 2^31 or more CIGAR
+ * elements; more than 2^31 - 1 reads or rows (hence candidates or events) in a
+ * job; an input that does not fit the device -- one input stays resident per
+ * job, at 36 bytes of HBM per row and 80 per event beside the scan / sort
+ * workspace; the message names the allocation.  On any failure there is no
+ * output.  An input that yields no target is no error: zero targets.
+ * prepare computes everything and keeps the results on the device; only the
+ * candidates' (start, end) pairs visit the host, where the serial fold runs.
+ * fetch copies the columns asked for (a NULL pointer skips one): per target
+ * start and end; indel_offset / snp_offset with n_targets + 1 entries each
+ * (always at least the one 0); n_indels indel and n_snps SNP ranges.  Device:
+ * adam_amd/csrc/realign_targets.hip. */
+typedef struct bqsr_realign_targets_sizes {
+  int64_t n_reads;
+  int64_t n_rows;       /* ADAMPileup rows */
+  int64_t n_candidates; /* rods with evidence */
+  int64_t n_targets;
+  int64_t n_indels;     /* indel ranges of all targets */
+  int64_t n_snps;       /* SNP ranges of all targets */
+} bqsr_realign_targets_sizes;
+typedef struct bqsr_realign_targets_host {
+  int64_t* target_start;
+  int64_t* target_end;
+  int64_t* indel_offset;
+  int64_t* snp_offset;
+  int64_t* indel_start;
+  int64_t* indel_end;
+  int64_t* indel_read_start;
+  int64_t* indel_read_end;
+  int64_t* snp_site;
+  int64_t* snp_read_start;
+  int64_t* snp_read_end;
+} bqsr_realign_targets_host;
+bqsr_status bqsr_sam_realign_targets_prepare(bqsr_context* ctx, bqsr_sam* s, void* stream,
+                                             bqsr_realign_targets_sizes* out);
+bqsr_status bqsr_sam_realign_targets_fetch(bqsr_context* ctx, bqsr_sam* s, const bqsr_realign_targets_host* dst,
+                                           void* stream);
+/* The same over a bqsr_arrow handle; mapq is no part of a target and is not
+ * needed.  A null boolean reads as false. */
+bqsr_status bqsr_arrow_realign_targets_prepare(bqsr_context* ctx, bqsr_arrow* a, void* stream,
+                                               bqsr_realign_targets_sizes* out);
+bqsr_status bqsr_arrow_realign_targets_fetch(bqsr_context* ctx, bqsr_arrow* a, const bqsr_realign_targets_host* dst,
+                                             void* stream);
+/* MEASUREMENT ONLY, not part of the stable interface: times, in milliseconds,
+ * of the calling thread's last prepare: by device events ms7[0] the count
+ * kernel, [1] row scan and emit, [2] the row sort, [3] rods and events, [4]
+ * candidates (hulls and their sort), [6] the targets' sets; by the host clock
+ * [5] the fold (tools/bench_adam.py --realign-targets). */
+bqsr_status bqsr_realign_targets_kernel_times(double* ms7);
+
 /* `adam aggregate_pileups` and what `reads2ref -aggregate` would compute
  * (adam-cli/.../cli/PileupAggregator.scala:27-57 over PileupAggregator.
  * aggregate, adam-core/.../rdd/PileupAggregator.scala:25-219): ADAMPileup rows

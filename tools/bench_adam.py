@@ -76,6 +76,19 @@ One JSON line.
 
     python tools/bench_adam.py --mpileup [--reads 2000000]
 
+--realign-targets measures the indel realignment targets
+(adam_amd/realignment_targets.py) over the same synthetic reads as SAM text, as
+generated (no sort, no filter: the finder takes every read).  Once after a
+warm-up, in this process: the command end to end (phase split by the host
+clock, the stages by device events, the fold by the host clock), then, on the
+same file, reads2ref's prepare (the pileup walk alone) and `adam mpileup`
+(which refuses unsorted reads or reads that disagree on the reference base:
+its seconds or its refusal is reported), then the single-threaded Python
+restatement (tests/_realign_targets_ref.py) on the first --restatement-reads
+reads, whose arrays the device must equal.  One JSON line.
+
+    python tools/bench_adam.py --realign-targets [--reads 2000000] [--restatement-reads 20000]
+
 --print-tags measures `adam print_tags` (adam_amd/print_tags.py) over the same
 synthetic reads as SAM text with aligner-like fields appended to every line
 (NM:i, AS:i, XS:i, and XA:Z on about 5 % of the lines; samgen alone writes MD
@@ -677,6 +690,102 @@ def bench_mpileup(a):
     print(json.dumps(res))
 
 
+def bench_realign_targets(a):
+    """the --realign-targets measurements (see the module doc)"""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from adam_amd import _capi
+    from adam_amd import mpileup as M
+    from adam_amd import reads2ref as R
+    from adam_amd import realignment_targets as RT
+    from adam_amd.sam import SamText
+    t0 = time.perf_counter()
+    sam = synthetic_sam(a.reads, a.len)
+    log("generated %d bytes of SAM in %.1f s" % (len(sam), time.perf_counter() - t0))
+    torch.zeros(1, device="cuda")
+    work = a.dir or tempfile.mkdtemp(prefix="bench_realign_targets_")
+    os.makedirs(work, exist_ok=True)
+    src, small = os.path.join(work, "in.sam"), os.path.join(work, "small.sam")
+
+    def timed(f):
+        t = time.perf_counter()
+        st = f()
+        return time.perf_counter() - t, st
+
+    def targets(path):
+        st = {}
+        out = RT.realignment_targets(path, stats=st)
+        return st, out
+
+    try:
+        with open(src, "wb") as fh:
+            fh.write(sam)
+        n_small = min(a.reads, a.restatement_reads)
+        cut = 0
+        while sam[cut:cut + 1] == b"@":
+            cut = sam.index(b"\n", cut) + 1
+        for _ in range(n_small):
+            cut = sam.index(b"\n", cut) + 1
+        small_text = sam[:cut]
+        with open(small, "wb") as fh:
+            fh.write(small_text)
+        log("warm-up run")
+        targets(src)
+        log("timed run")
+        s_t, (st, out) = timed(lambda: targets(src))
+        ts, te = out["target_start"], out["target_end"]
+        n_ind = np.diff(out["indel_offset"])
+        res = {"metric": "indel realignment targets (RealignmentTargetFinder) of SAM text, one run after a warm-up in "
+                         "one process: end-to-end seconds and phase split (host clock), the stages by device events "
+                         "(fold_host: the serial fold, host clock)",
+               "input": "%d synthetic reads of %d bases as generated, unsorted, every read taken" % (a.reads, a.len),
+               "reads": st["reads"], "read_len": a.len, "input_bytes": os.path.getsize(src),
+               "realign_targets": {"seconds": s_t, "rows": st["rows"], "candidates": st["candidates"],
+                                   "targets": st["targets"], "indel_ranges": st["indels"], "snp_ranges": st["snps"],
+                                   "phases_s": st["phases"], "kernels_ms": st["kernel_ms"],
+                                   "rows_per_s": st["rows"] / s_t if s_t else None,
+                                   "targets_with_indels": int((n_ind > 0).sum()),
+                                   "longest_target": int((te - ts + 1).max()) if len(ts) else 0,
+                                   "candidates_per_target": st["candidates"] / st["targets"] if st["targets"] else None}}
+        # the pileup walk alone (reads2ref's prepare over all reads) and mpileup, on the same file
+        with open(src, "rb") as fh:
+            data = fh.read()
+        s = SamText(data)
+        try:
+            L = R._lib()
+            sz = R.PileupSizes()
+            prep = lambda: _capi.check(L.bqsr_sam_pileup_prepare(s.ctx.handle, s.h, 0, s.counts().n_reads, None,
+                                                                 ctypes.byref(sz)))
+            prep()
+            s_p, _ = timed(prep)
+            res["reads2ref_prepare"] = {"seconds": s_p, "rows": sz.n_rows, "count_kernel_ms": R.kernel_times()[0]}
+        finally:
+            s.close()
+        del data
+        try:
+            s_m, st_m = timed(lambda: M.mpileup(src, os.path.join(work, "mpileup.txt")))
+            res["mpileup"] = {"seconds": s_m, "events": st_m["events"], "lines": st_m["lines"]}
+        except _capi.BQSRError as e:
+            res["mpileup"] = {"refused": e.name, "message": str(e)[:200]}
+        if n_small:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            from _adam_ref import convert_sam
+            import _realign_targets_ref as ref
+            s_r, want = timed(lambda: ref.as_arrays(ref.find_targets(convert_sam(small_text))))
+            s_s, (st_s, got) = timed(lambda: targets(small))
+            assert all(np.array_equal(got[k], want[k]) for k in RT.COLUMNS), "the device and the restatement differ"
+            res["python_restatement"] = {"reads": n_small, "seconds": s_r, "targets": st_s["targets"],
+                                         "realign_targets_seconds_same_reads": s_s}
+        log("realign targets %.2f s (%d rows, %d candidates, %d targets), kernels %s"
+            % (s_t, st["rows"], st["candidates"], st["targets"], st["kernel_ms"]))
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps(res))
+
+
 def bench_aggregate(a):
     """the --aggregate measurements (see the module doc)"""
     import torch
@@ -854,6 +963,8 @@ def main():
                     help="measure adam aggregate_pileups next to adam reads2ref instead of the transform")
     ap.add_argument("--mpileup", action="store_true",
                     help="measure adam mpileup next to adam reads2ref instead of the transform")
+    ap.add_argument("--realign-targets", action="store_true",
+                    help="measure the indel realignment targets instead of the transform")
     ap.add_argument("--restatement-reads", type=int, default=200_000,
                     help="--aggregate: reads the Python restatement is timed on (0: skip it)")
     ap.add_argument("--flagstat", action="store_true", help="measure adam flagstat instead of the transform")
@@ -881,6 +992,8 @@ def main():
         return bench_print_tags(a)
     if a.mpileup:
         return bench_mpileup(a)
+    if a.realign_targets:
+        return bench_realign_targets(a)
     if a.reads2ref:
         return bench_reads2ref(a)
     if a.aggregate:
