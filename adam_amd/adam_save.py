@@ -345,6 +345,19 @@ def is_adam_output(path: str) -> bool:
     return True
 
 
+def check_out(path: str, overwrite: bool, adam: bool) -> None:
+    """The output path must not exist (adamSave's FileOutputFormat refuses an
+    existing one); with overwrite, only a regular file, or (ADAM output) a
+    directory of nothing but part files, may be replaced."""
+    for p in (path, path + ".partial"):
+        if not os.path.lexists(p):
+            continue
+        if not overwrite:
+            raise FileExistsError("output path %s already exists" % p)
+        if os.path.isdir(p) and not (adam and is_adam_output(p)):
+            raise FileExistsError("refusing to replace directory %s" % p)
+
+
 class AdamWriter:
     """adamSave's output: a directory of part files, written by host threads
     as the tables arrive (``OUT.partial`` renamed to ``OUT`` on ``close``)."""

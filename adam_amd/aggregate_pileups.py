@@ -55,8 +55,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import mmap
-import os
 import sys
 import time
 from typing import Dict, List, Optional, Sequence
@@ -66,8 +64,9 @@ import numpy as np
 from . import _capi, bqsr
 from . import reads2ref as R
 from ._capi import check
-from .adam_save import (BASES, PILEUP_DICT_COLS, PILEUP_FIELDS, PILEUP_STATS_COLS, RG_TAGS, AdamWriter, header_info,
-                        pileup_schema)
+from .adam_save import (BASES, PILEUP_DICT_COLS, PILEUP_FIELDS, PILEUP_STATS_COLS, RG_TAGS, AdamWriter, check_out,
+                        header_info, pileup_schema)
+from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
 
 DEFAULT_PART_ROWS = 1 << 20  # aggregated rows per part file (their joined read names stay far below 2 GB)
 WORKGROUP = 256              # rows per scan tile (pileup_agg.hip kThreads): the size the boundary tests straddle
@@ -501,11 +500,10 @@ def aggregate_pileups(inp: str, out: str, compression: str = "gzip", part_rows: 
     part file; partition_bytes: SAM text per streamed partition; part_reads:
     reads per expansion call.  Returns the job's statistics."""
     from . import parquet as P
-    from .transform import DEFAULT_PARTITION_BYTES, _Phases, _check_out, _host_bytes, is_bam, is_parquet, sam_partitions
     partition_bytes = DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes
-    _check_out(out, overwrite, True)
+    check_out(out, overwrite, True)
     ctx = bqsr.Context.get(device)
-    ph = _Phases()
+    ph = Phases()
     part_rows, part_reads = max(1, int(part_rows)), max(1, int(part_reads))
     stats: Dict[str, object] = {}
     U = Units()
@@ -540,44 +538,27 @@ def aggregate_pileups(inp: str, out: str, compression: str = "gzip", part_rows: 
                 stats["input"] = "reads"
                 stats["reads"] = table.num_rows
         else:
-            from .sam import SamText
             n_reads = 0
-            with open(inp, "rb") as fh:
-                data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if os.path.getsize(inp) else b""
-                try:
-                    bam = is_bam(data)
-                    makes = [lambda: _host_bytes(data)]
-                    if not bam and len(data):
-                        header, ranges = sam_partitions(data, partition_bytes)
-                        if len(ranges) > 1:
-                            makes = [lambda a=a, b=b: header + bytes(data[a:b]) for a, b in ranges]
-                    for make in makes:
-                        with ph("parse"):
-                            sam = SamText(make(), ctx, bam=bam)
-                        try:
-                            hdr = header_info(sam)
-                            ranks = _sam_units(U, hdr)
-                            n = sam.counts().n_reads
-                            with ph("add"):
-                                for r0 in range(0, n, part_reads):
-                                    m = min(part_reads, n - r0)
-                                    sz = R.PileupSizes()
-                                    try:
-                                        check(L.bqsr_sam_pileup_prepare(ctx.handle, sam.h, r0, m, None, ctypes.byref(sz)))
-                                    except _capi.BQSRError as e:
-                                        raise R._rebased(e, n_reads) from None
-                                    rl = R._sam_read_level(sam, r0, m, hdr)
-                                    ref, ref_ok, _ = rl.coded["referenceId"]
-                                    rg, rg_ok, _ = rl.coded["recordGroupSample"]
-                                    code = np.where(rg_ok, rg + 1, 0).astype(np.int32)
-                                    agg.add_sam(sam, sz.n_rows, ranks[code], code, n_reads + r0)
-                                    U.add(rl.read_name, np.where(ref_ok, ref, -1), code)
-                            n_reads += n
-                        finally:
-                            sam.close()
-                finally:
-                    if isinstance(data, mmap.mmap):
-                        data.close()
+            with SamInput(inp, ctx, ph, partition_bytes) as src:
+                for sam, base in src:
+                    hdr = header_info(sam)
+                    ranks = _sam_units(U, hdr)
+                    n = sam.counts().n_reads
+                    with ph("add"):
+                        for r0 in range(0, n, part_reads):
+                            m = min(part_reads, n - r0)
+                            sz = R.PileupSizes()
+                            try:
+                                check(L.bqsr_sam_pileup_prepare(ctx.handle, sam.h, r0, m, None, ctypes.byref(sz)))
+                            except _capi.BQSRError as e:
+                                raise rebased(e, base) from None
+                            rl = R._sam_read_level(sam, r0, m, hdr)
+                            ref, ref_ok, _ = rl.coded["referenceId"]
+                            rg, rg_ok, _ = rl.coded["recordGroupSample"]
+                            code = np.where(rg_ok, rg + 1, 0).astype(np.int32)
+                            agg.add_sam(sam, sz.n_rows, ranks[code], code, base + r0)
+                            U.add(rl.read_name, np.where(ref_ok, ref, -1), code)
+                    n_reads = base + n
             stats["input"] = "reads"
             stats["reads"] = n_reads
         with ph("aggregate"):
@@ -622,7 +603,6 @@ def aggregate_pileups(inp: str, out: str, compression: str = "gzip", part_rows: 
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    from .transform import DEFAULT_PARTITION_BYTES
     ap = argparse.ArgumentParser(prog="adam_amd.aggregate_pileups", description=__doc__.split("\n\n")[0])
     ap.add_argument("input")
     ap.add_argument("output")
@@ -634,8 +614,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     a = ap.parse_args(argv)
     t0 = time.perf_counter()
     st = aggregate_pileups(a.input, a.output, a.parquet_compression, a.part_rows, a.partition_bytes, a.overwrite)
-    st["seconds"] = time.perf_counter() - t0
-    print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
+    report(st, t0)
     return 0
 
 

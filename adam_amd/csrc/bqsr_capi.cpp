@@ -2172,6 +2172,7 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
 }  // extern "C"
 
 // ---- SAM ingest / output (include/adam_sam.h) ----
+#include "device_job.h"
 #include "sam_ingest.hip"
 #include "bgzf_inflate.hip"
 #include "bam_ingest.hip"

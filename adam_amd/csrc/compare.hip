@@ -762,17 +762,6 @@ struct CompareSide {
   bool collision = false;
 };
 
-template <class F>
-bqsr_status with_temp(std::vector<void*>& keep, F&& call) {
-  size_t bytes = 0;
-  HIP_TRY(call((void*)nullptr, bytes));
-  uint8_t* temp = nullptr;
-  const bqsr_status e = sam_alloc(keep, &temp, bytes);
-  if (e != BQSR_OK) return e;
-  HIP_TRY(call((void*)temp, bytes));
-  return BQSR_OK;
-}
-
 // the Arrow side's firstOfPair and mapq chunks -> per-read columns (cat, mapq, mapq_ok)
 bqsr_status compare_arrow_columns(bqsr_compare* c, const bqsr_compare_side* in, SortTmp& T, hipStream_t st,
                                   uint8_t* cat, int32_t* mapq, uint8_t* ok) {

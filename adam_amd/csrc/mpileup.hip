@@ -512,17 +512,8 @@ extern "C" __global__ void __launch_bounds__(kThreads) mp_text(TextParams P) {
 
 namespace {
 
-// a device buffer that only grows
-struct MpBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~MpBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 struct MpState {
-  MpBuf keep, kpos, kidx, evpre, readpre, refpre, mdent, cnt, es, md_n, segflag, segid1, key_a, key_b, val_a, val_b, head,
+  DevBuf keep, kpos, kidx, evpre, readpre, refpre, mdent, cnt, es, md_n, segflag, segid1, key_a, key_b, val_a, val_b, head,
       line1, len, evoff, mask, first, linemask, hdrlen, linebase, linelen, lineoff, temp, names, name_off, out, small;
   uint64_t *key = nullptr, *val = nullptr;  // the sorted ones
   int64_t nk = 0, n_ev = 0, n_lines = 0, text_bytes = 0;
@@ -537,56 +528,6 @@ struct MpState {
 
 // walk, emit, sort, group, text: the calling thread's last prepare / text calls
 thread_local double g_mpileup_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-
-MpState* mp_state(std::shared_ptr<void>& slot) {
-  if (!slot) slot = std::shared_ptr<void>(new MpState, [](void* p) { delete (MpState*)p; });
-  return (MpState*)slot.get();
-}
-
-// the job keeps its whole input's events on the device: what does not fit is refused
-template <class T>
-bqsr_status mp_need(MpBuf& b, T** p, size_t count, const char* what) {
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  if (b.cap < bytes) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      b.p = nullptr;
-      return fail(BQSR_ERR_UNSUPPORTED, std::string("mpileup: one input stays resident on the device and this one does "
-                                                    "not fit: ") + std::to_string(bytes) + " bytes for its " + what);
-    }
-    b.cap = bytes;
-  }
-  *p = (T*)b.p;
-  return BQSR_OK;
-}
-
-template <class F>
-bqsr_status mp_prim(MpState& A, F&& call) {
-  size_t tb = 0;
-  HIP_TRY(call((void*)nullptr, tb));
-  uint8_t* temp;
-  const bqsr_status e = mp_need(A.temp, &temp, tb, "scan and sort workspace");
-  if (e != BQSR_OK) return e;
-  HIP_TRY(call((void*)temp, tb));
-  return BQSR_OK;
-}
-
-// (BQSR_TUNE_PILEUP_GRID caps these grids as it does reads2ref's: tests run every loop through many passes)
-unsigned mp_grid(const bqsr_context* ctx, int64_t n) {
-  return sam_grid(n, mpk::kThreads, ctx->tune_pileup_grid > 0 ? ctx->tune_pileup_grid : ctx->n_cu * 8);
-}
-
-int mp_bits(uint64_t v) {
-  int b = 0;
-  while (v) {
-    ++b;
-    v >>= 1;
-  }
-  return b;
-}
 
 struct MpView {
   mpk::Reads A;
@@ -628,6 +569,11 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
     return ok();
   }
   bqsr_status e;
+  auto need = [](DevBuf& b, auto** p, size_t count, const char* what) {
+    return dev_need(b, p, count, "mpileup", what);
+  };
+  auto prim = [&](auto&& call) { return dev_prim(A.temp, "mpileup", call); };
+  auto grid = [&](int64_t items) { return pileup_job_grid(ctx, items, kThreads); };
   // ---- the name table ----
   {
     std::vector<uint8_t> blob;
@@ -638,7 +584,7 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
     }
     uint8_t* dn;
     uint64_t* doff;
-    if ((e = mp_need(A.names, &dn, blob.size(), "reference names")) || (e = mp_need(A.name_off, &doff, off.size(), "reference names")))
+    if ((e = need(A.names, &dn, blob.size(), "reference names")) || (e = need(A.name_off, &doff, off.size(), "reference names")))
       return e;
     if (!blob.empty()) HIP_TRY(hipMemcpyAsync(dn, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(doff, off.data(), off.size() * 8, hipMemcpyHostToDevice, s));
@@ -648,19 +594,19 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
   uint32_t *keep, *kpos;
   int64_t* kidx;
   unsigned long long* small;  // err, unsorted, maxpos, conflict, then mp_window's six words
-  if ((e = mp_need(A.keep, &keep, (size_t)n + 1, "reads")) || (e = mp_need(A.kpos, &kpos, (size_t)n + 1, "reads")) ||
-      (e = mp_need(A.kidx, &kidx, (size_t)n, "reads")) || (e = mp_need(A.small, &small, 16, "status words")))
+  if ((e = need(A.keep, &keep, (size_t)n + 1, "reads")) || (e = need(A.kpos, &kpos, (size_t)n + 1, "reads")) ||
+      (e = need(A.kidx, &kidx, (size_t)n, "reads")) || (e = need(A.small, &small, 16, "status words")))
     return e;
   HIP_TRY(hipMemsetAsync(small, 0xFF, 16 * 8, s));
   HIP_TRY(hipMemsetAsync(small + 2, 0, 8, s));
   HIP_TRY(hipEventRecord(A.ev[0], s));
-  hipLaunchKernelGGL(mp_keep, dim3(mp_grid(ctx, n)), dim3(kThreads), 0, s, V.A, n, keep);
+  hipLaunchKernelGGL(mp_keep, dim3(grid(n)), dim3(kThreads), 0, s, V.A, n, keep);
   HIP_TRY(hipGetLastError());
-  if ((e = mp_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, keep, kpos, (uint32_t)0, (size_t)n + 1, rocprim::plus<uint32_t>(), s);
        })))
     return e;
-  hipLaunchKernelGGL(mp_compact, dim3(mp_grid(ctx, n)), dim3(kThreads), 0, s, (const uint32_t*)keep,
+  hipLaunchKernelGGL(mp_compact, dim3(grid(n)), dim3(kThreads), 0, s, (const uint32_t*)keep,
                      (const uint32_t*)kpos, n, kidx);
   HIP_TRY(hipGetLastError());
   uint32_t nk32 = 0;
@@ -678,21 +624,21 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
   uint64_t* es;
   uint32_t* segid1;
   const size_t nc = (size_t)V.cig_ops, nm = (size_t)V.md_bytes, K = (size_t)nk;
-  if ((e = mp_need(A.evpre, &X.evpre, nc, "CIGAR elements")) || (e = mp_need(A.readpre, &X.readpre, nc, "CIGAR elements")) ||
-      (e = mp_need(A.refpre, &X.refpre, nc, "CIGAR elements")) || (e = mp_need(A.mdent, &X.mdent, nm, "MD entries")) ||
-      (e = mp_need(A.cnt, &X.cnt, K + 1, "kept reads")) || (e = mp_need(A.es, &es, K + 1, "kept reads")) ||
-      (e = mp_need(A.md_n, &X.md_n, K, "kept reads")) || (e = mp_need(A.segflag, &X.segflag, K, "kept reads")) ||
-      (e = mp_need(A.segid1, &segid1, K, "kept reads")))
+  if ((e = need(A.evpre, &X.evpre, nc, "CIGAR elements")) || (e = need(A.readpre, &X.readpre, nc, "CIGAR elements")) ||
+      (e = need(A.refpre, &X.refpre, nc, "CIGAR elements")) || (e = need(A.mdent, &X.mdent, nm, "MD entries")) ||
+      (e = need(A.cnt, &X.cnt, K + 1, "kept reads")) || (e = need(A.es, &es, K + 1, "kept reads")) ||
+      (e = need(A.md_n, &X.md_n, K, "kept reads")) || (e = need(A.segflag, &X.segflag, K, "kept reads")) ||
+      (e = need(A.segid1, &segid1, K, "kept reads")))
     return e;
   HIP_TRY(hipMemsetAsync(X.cnt + nk, 0, 8, s));
   WalkParams W{V.A, X, kidx, nk, small, small + 1, small + 2};
-  hipLaunchKernelGGL(mp_walk, dim3(mp_grid(ctx, nk)), dim3(kThreads), 0, s, W);
+  hipLaunchKernelGGL(mp_walk, dim3(grid(nk)), dim3(kThreads), 0, s, W);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(A.ev[1], s));
-  if ((e = mp_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, X.cnt, es, (uint64_t)0, K + 1, rocprim::plus<uint64_t>(), s);
        })) ||
-      (e = mp_prim(A, [&](void* t, size_t& b) {
+      (e = prim([&](void* t, size_t& b) {
          return rocprim::inclusive_scan(t, b, X.segflag, segid1, K, rocprim::plus<uint32_t>(), s);
        })))
     return e;
@@ -724,8 +670,8 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
     A.prepared = true;
     return ok();
   }
-  const int pos_bits = std::max(1, mp_bits((uint64_t)st3[2]));
-  const int key_bits = 2 + pos_bits + mp_bits((uint64_t)n_seg - 1);
+  const int pos_bits = std::max(1, bits_of((uint64_t)st3[2]));
+  const int key_bits = 2 + pos_bits + bits_of((uint64_t)n_seg - 1);
   if (key_bits > 64)
     return fail(BQSR_ERR_UNSUPPORTED, "mpileup: segment, position and class need " + std::to_string(key_bits) +
                 " key bits, more than 64");
@@ -733,15 +679,15 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
   // ---- emit, sort ----
   const size_t M = (size_t)m;
   uint64_t *key_a, *key_b, *val_a, *val_b;
-  if ((e = mp_need(A.key_a, &key_a, M, "events")) || (e = mp_need(A.key_b, &key_b, M, "events")) ||
-      (e = mp_need(A.val_a, &val_a, M, "events")) || (e = mp_need(A.val_b, &val_b, M, "events")))
+  if ((e = need(A.key_a, &key_a, M, "events")) || (e = need(A.key_b, &key_b, M, "events")) ||
+      (e = need(A.val_a, &val_a, M, "events")) || (e = need(A.val_b, &val_b, M, "events")))
     return e;
   EmitParams E{V.A, X, kidx, es, segid1, nk, m, pos_bits, key_a, val_a};
   HIP_TRY(hipEventRecord(A.ev[2], s));
-  hipLaunchKernelGGL(mp_emit, dim3(mp_grid(ctx, m)), dim3(kThreads), 0, s, E);
+  hipLaunchKernelGGL(mp_emit, dim3(grid(m)), dim3(kThreads), 0, s, E);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(A.ev[3], s));
-  if ((e = mp_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::radix_sort_pairs(t, b, key_a, key_b, val_a, val_b, M, 0, (unsigned)key_bits, s);
        })))
     return e;
@@ -752,17 +698,17 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
   uint32_t *head, *line1, *mask, *first, *linemask, *hdrlen;
   uint64_t *len, *evoff, *linelen, *lineoff;
   uint8_t* linebase;
-  if ((e = mp_need(A.head, &head, M + 1, "events")) || (e = mp_need(A.line1, &line1, M, "events")) ||
-      (e = mp_need(A.len, &len, M + 1, "events")) || (e = mp_need(A.evoff, &evoff, M + 1, "events")) ||
-      (e = mp_need(A.mask, &mask, M, "events")) || (e = mp_need(A.first, &first, M + 1, "events")))
+  if ((e = need(A.head, &head, M + 1, "events")) || (e = need(A.line1, &line1, M, "events")) ||
+      (e = need(A.len, &len, M + 1, "events")) || (e = need(A.evoff, &evoff, M + 1, "events")) ||
+      (e = need(A.mask, &mask, M, "events")) || (e = need(A.first, &first, M + 1, "events")))
     return e;
   GroupParams G{V.A, kidx, key_b, val_b, m, head, len, mask};
-  hipLaunchKernelGGL(mp_heads, dim3(mp_grid(ctx, m)), dim3(kThreads), 0, s, G);
+  hipLaunchKernelGGL(mp_heads, dim3(grid(m)), dim3(kThreads), 0, s, G);
   HIP_TRY(hipGetLastError());
-  if ((e = mp_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::inclusive_scan(t, b, head, line1, M, rocprim::plus<uint32_t>(), s);
        })) ||
-      (e = mp_prim(A, [&](void* t, size_t& b) {
+      (e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, len, evoff, (uint64_t)0, M + 1, rocprim::plus<uint64_t>(), s);
        })))
     return e;
@@ -771,24 +717,24 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
   HIP_TRY(hipStreamSynchronize(s));
   const int64_t nl = nl32;
   const size_t NL = (size_t)nl;
-  if ((e = mp_need(A.linemask, &linemask, NL + 1, "lines")) || (e = mp_need(A.hdrlen, &hdrlen, NL, "lines")) ||
-      (e = mp_need(A.linebase, &linebase, NL, "lines")) || (e = mp_need(A.linelen, &linelen, NL + 1, "lines")) ||
-      (e = mp_need(A.lineoff, &lineoff, NL + 1, "lines")))
+  if ((e = need(A.linemask, &linemask, NL + 1, "lines")) || (e = need(A.hdrlen, &hdrlen, NL, "lines")) ||
+      (e = need(A.linebase, &linebase, NL, "lines")) || (e = need(A.linelen, &linelen, NL + 1, "lines")) ||
+      (e = need(A.lineoff, &lineoff, NL + 1, "lines")))
     return e;
-  hipLaunchKernelGGL(mp_first, dim3(mp_grid(ctx, m)), dim3(kThreads), 0, s, (const uint32_t*)head,
+  hipLaunchKernelGGL(mp_first, dim3(grid(m)), dim3(kThreads), 0, s, (const uint32_t*)head,
                      (const uint32_t*)line1, m, first);
   HIP_TRY(hipGetLastError());
   // per line the OR of its events' reference-base bits (head is free: the unique keys go there, the count after them)
-  if ((e = mp_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::reduce_by_key(t, b, line1, mask, M, head, linemask, linemask + nl, mpk::BitOr(),
                                        rocprim::equal_to<uint32_t>(), s);
        })))
     return e;
   LineParams LP{V.A, kidx, key_b, val_b, first, evoff, linemask, (const uint64_t*)A.name_off.p, nl, pos_bits,
                 hdrlen, linebase, linelen, small + 3};
-  hipLaunchKernelGGL(mp_lines, dim3(mp_grid(ctx, nl)), dim3(kThreads), 0, s, LP);
+  hipLaunchKernelGGL(mp_lines, dim3(grid(nl)), dim3(kThreads), 0, s, LP);
   HIP_TRY(hipGetLastError());
-  if ((e = mp_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, linelen, lineoff, (uint64_t)0, NL + 1, rocprim::plus<uint64_t>(), s);
        })))
     return e;
@@ -850,13 +796,13 @@ bqsr_status mp_text_call(bqsr_context* ctx, MpState& A, const MpView& V, int64_t
   if (!dst) return fail(BQSR_ERR_INVALID_ARG, std::string(who) + ": null destination");
   uint8_t* out;
   bqsr_status e;
-  if ((e = mp_need(A.out, &out, (size_t)nbytes + 64, "text window"))) return e;
+  if ((e = dev_need(A.out, &out, (size_t)nbytes + 64, "mpileup", "text window"))) return e;
   TextParams T{V.A, (const int64_t*)A.kidx.p, A.key, A.val, (const uint32_t*)A.line1.p, (const uint32_t*)A.first.p,
                (const uint64_t*)A.evoff.p, (const uint64_t*)A.lineoff.p, (const uint32_t*)A.hdrlen.p,
                (const uint8_t*)A.linebase.p, (const uint8_t*)A.names.p, (const uint64_t*)A.name_off.p,
                (int64_t)w[4], (int64_t)w[5], w[1], nbytes, A.pos_bits, out};
   HIP_TRY(hipEventRecord(A.ev[6], s));
-  hipLaunchKernelGGL(mp_text, dim3(mp_grid(ctx, T.e1 - T.e0)), dim3(kThreads), 0, s, T);
+  hipLaunchKernelGGL(mp_text, dim3(pileup_job_grid(ctx, T.e1 - T.e0, kThreads)), dim3(kThreads), 0, s, T);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(A.ev[7], s));
   HIP_TRY(hipMemcpyAsync(dst, out, (size_t)nbytes, hipMemcpyDeviceToHost, s));
@@ -899,7 +845,7 @@ extern "C" {
 bqsr_status bqsr_sam_mpileup_prepare(bqsr_context* ctx, bqsr_sam* s, void* stream, bqsr_mpileup_sizes* out) {
   if (!ctx || !s || !out) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_mpileup_prepare: bad arguments");
   HIP_TRY(hipSetDevice(ctx->device));
-  return mp_prepare(ctx, *mp_state(s->mpileup), mp_view(s), S(stream), out);
+  return mp_prepare(ctx, *job_state<MpState>(s->mpileup), mp_view(s), S(stream), out);
 }
 
 bqsr_status bqsr_sam_mpileup_text(bqsr_context* ctx, bqsr_sam* s, int64_t line0, int64_t budget, char* dst, void* stream,
@@ -907,7 +853,7 @@ bqsr_status bqsr_sam_mpileup_text(bqsr_context* ctx, bqsr_sam* s, int64_t line0,
   if (!ctx || !s || !n_lines || !n_bytes) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_mpileup_text: bad arguments");
   if (!s->mpileup) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_mpileup_text before bqsr_sam_mpileup_prepare");
   HIP_TRY(hipSetDevice(ctx->device));
-  return mp_text_call(ctx, *mp_state(s->mpileup), mp_view(s), line0, budget, dst, S(stream), n_lines, n_bytes,
+  return mp_text_call(ctx, *job_state<MpState>(s->mpileup), mp_view(s), line0, budget, dst, S(stream), n_lines, n_bytes,
                       "bqsr_sam_mpileup_text");
 }
 
@@ -922,7 +868,7 @@ bqsr_status bqsr_arrow_mpileup_prepare(bqsr_context* ctx, bqsr_arrow* a, const i
     if (!ref_names[i]) return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_mpileup_prepare: a null reference name");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
-  PileupState& P = *pileup_state(a->pileup);
+  PileupState& P = *job_state<PileupState>(a->pileup);
   if (n_chunks) {
     const bqsr_status e = pileup_arrow_mapq(ctx, a, P, chunk_reads, mapq, mapq_validity, n_chunks, s,
                                             "bqsr_arrow_mpileup_prepare");
@@ -931,7 +877,7 @@ bqsr_status bqsr_arrow_mpileup_prepare(bqsr_context* ctx, bqsr_arrow* a, const i
   if (!a->mpileup_names) a->mpileup_names = std::shared_ptr<void>(new MpArrowNames, [](void* p) { delete (MpArrowNames*)p; });
   MpArrowNames& N = *(MpArrowNames*)a->mpileup_names.get();
   N.names.assign(ref_names, ref_names + n_ref_names);
-  return mp_prepare(ctx, *mp_state(a->mpileup), mp_view(a, P, N.names), s, out);
+  return mp_prepare(ctx, *job_state<MpState>(a->mpileup), mp_view(a, P, N.names), s, out);
 }
 
 bqsr_status bqsr_arrow_mpileup_text(bqsr_context* ctx, bqsr_arrow* a, int64_t line0, int64_t budget, char* dst,
@@ -941,8 +887,8 @@ bqsr_status bqsr_arrow_mpileup_text(bqsr_context* ctx, bqsr_arrow* a, int64_t li
     return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_mpileup_text before bqsr_arrow_mpileup_prepare");
   HIP_TRY(hipSetDevice(ctx->device));
   MpArrowNames& N = *(MpArrowNames*)a->mpileup_names.get();
-  return mp_text_call(ctx, *mp_state(a->mpileup), mp_view(a, *pileup_state(a->pileup), N.names), line0, budget, dst,
-                      S(stream), n_lines, n_bytes, "bqsr_arrow_mpileup_text");
+  return mp_text_call(ctx, *job_state<MpState>(a->mpileup), mp_view(a, *job_state<PileupState>(a->pileup), N.names),
+                      line0, budget, dst, S(stream), n_lines, n_bytes, "bqsr_arrow_mpileup_text");
 }
 
 bqsr_status bqsr_mpileup_kernel_times(double* ms5) {

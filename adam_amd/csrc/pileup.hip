@@ -468,11 +468,6 @@ struct PileupView {
   int64_t n_reads, cig_ops, md_bytes;
 };
 
-PileupState* pileup_state(std::shared_ptr<void>& slot) {
-  if (!slot) slot = std::shared_ptr<void>(new PileupState, [](void* p) { delete (PileupState*)p; });
-  return (PileupState*)slot.get();
-}
-
 unsigned pileup_grid(const bqsr_context* ctx, int64_t blocks) {
   const int64_t cap = ctx->tune_pileup_grid > 0 ? ctx->tune_pileup_grid : (int64_t)ctx->n_cu * 8;
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, cap));
@@ -705,14 +700,15 @@ bqsr_status bqsr_sam_pileup_prepare(bqsr_context* ctx, bqsr_sam* s, int64_t r0, 
   if (!ctx || !s || !out || r0 < 0 || n < 0 || r0 + n > s->n_reads)
     return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_pileup_prepare: bad arguments");
   HIP_TRY(hipSetDevice(ctx->device));
-  return pileup_prepare(ctx, *pileup_state(s->pileup), pileup_view(s), r0, n, S(stream), out, "reads2ref");
+  return pileup_prepare(ctx, *job_state<PileupState>(s->pileup), pileup_view(s), r0, n, S(stream), out, "reads2ref");
 }
 
 bqsr_status bqsr_sam_pileup_columns(bqsr_context* ctx, bqsr_sam* s, const bqsr_pileup_host* dst, void* stream) {
   if (!ctx || !s || !dst) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_pileup_columns: bad arguments");
   if (!s->pileup) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_pileup_columns before bqsr_sam_pileup_prepare");
   HIP_TRY(hipSetDevice(ctx->device));
-  return pileup_columns(ctx, *pileup_state(s->pileup), pileup_view(s), dst, S(stream), "bqsr_sam_pileup_columns");
+  return pileup_columns(ctx, *job_state<PileupState>(s->pileup), pileup_view(s), dst, S(stream),
+                        "bqsr_sam_pileup_columns");
 }
 
 bqsr_status bqsr_arrow_pileup_prepare(bqsr_context* ctx, bqsr_arrow* a, int64_t r0, int64_t n,
@@ -724,7 +720,7 @@ bqsr_status bqsr_arrow_pileup_prepare(bqsr_context* ctx, bqsr_arrow* a, int64_t 
     return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_prepare: bad arguments");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
-  PileupState& A = *pileup_state(a->pileup);
+  PileupState& A = *job_state<PileupState>(a->pileup);
   if (n_chunks) {
     const bqsr_status e = pileup_arrow_mapq(ctx, a, A, chunk_reads, mapq, mapq_validity, n_chunks, s, "bqsr_arrow_pileup_prepare");
     if (e != BQSR_OK) return e;
@@ -736,7 +732,7 @@ bqsr_status bqsr_arrow_pileup_columns(bqsr_context* ctx, bqsr_arrow* a, const bq
   if (!ctx || !a || !dst) return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_columns: bad arguments");
   if (!a->pileup) return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_columns before bqsr_arrow_pileup_prepare");
   HIP_TRY(hipSetDevice(ctx->device));
-  PileupState& A = *pileup_state(a->pileup);
+  PileupState& A = *job_state<PileupState>(a->pileup);
   return pileup_columns(ctx, A, pileup_view(a, A), dst, S(stream), "bqsr_arrow_pileup_columns");
 }
 

@@ -704,9 +704,8 @@ bqsr_status bqsr_sam_pileup_agg_add(bqsr_context* ctx, bqsr_sam* sm, bqsr_pileup
     return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_pileup_agg_add: bad arguments");
   if (!sm->pileup) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_pileup_agg_add before bqsr_sam_pileup_prepare");
   HIP_TRY(hipSetDevice(ctx->device));
-  return agg_add_reads(ctx, agg, *pileup_state(sm->pileup), pileup_view(sm), sm->sq_id, sample_code, rg_code, name_base,
-                       S(stream),
-                       "bqsr_sam_pileup_agg_add");
+  return agg_add_reads(ctx, agg, *job_state<PileupState>(sm->pileup), pileup_view(sm), sm->sq_id, sample_code, rg_code,
+                       name_base, S(stream), "bqsr_sam_pileup_agg_add");
 }
 
 bqsr_status bqsr_arrow_pileup_agg_add(bqsr_context* ctx, bqsr_arrow* a, bqsr_pileup_agg* agg,
@@ -716,7 +715,7 @@ bqsr_status bqsr_arrow_pileup_agg_add(bqsr_context* ctx, bqsr_arrow* a, bqsr_pil
     return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_agg_add: bad arguments");
   if (!a->pileup) return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_agg_add before bqsr_arrow_pileup_prepare");
   HIP_TRY(hipSetDevice(ctx->device));
-  PileupState& A = *pileup_state(a->pileup);
+  PileupState& A = *job_state<PileupState>(a->pileup);
   return agg_add_reads(ctx, agg, A, pileup_view(a, A), a->sq, sample_code, rg_code, name_base, S(stream),
                        "bqsr_arrow_pileup_agg_add");
 }

@@ -54,8 +54,6 @@
 // HBM per row as built: 16 B key, 16 B payload (both double-buffered for the
 // sort; the spare halves then hold the heads, rod ids, quality words and event
 // flags) and 4 B event offset: 36 B, plus rocprim's workspace; 80 B per event.
-//
-// Included by bqsr_capi.cpp after mpileup.hip (MpBuf, mp_bits).
 
 namespace rtk {
 
@@ -305,7 +303,7 @@ extern "C" __global__ void __launch_bounds__(kThreads) rt_offsets(const Ev* out,
 namespace {
 
 struct RtState {
-  MpBuf rowpre, readpre, refpre, mdent, cnt, rs, md_n, rend, small, key_a, key_b, val_a, val_b, evoff, rodq, ev_a, ev_b,
+  DevBuf rowpre, readpre, refpre, mdent, cnt, rs, md_n, rend, small, key_a, key_b, val_a, val_b, evoff, rodq, ev_a, ev_b,
       candrod, hull, ckey_a, ckey_b, cval_a, cval_b, cend, tid, multi, rod2t, isi, islot, res, temp;
   rtk::Result D{};
   std::vector<int64_t> t_start, t_end;
@@ -320,47 +318,6 @@ struct RtState {
 
 // count, emit, sort, rods, candidates, fold (host), sets: the calling thread's last prepare
 thread_local double g_realign_ms[7] = {0, 0, 0, 0, 0, 0, 0};
-
-RtState* rt_state(std::shared_ptr<void>& slot) {
-  if (!slot) slot = std::shared_ptr<void>(new RtState, [](void* p) { delete (RtState*)p; });
-  return (RtState*)slot.get();
-}
-
-// the job keeps its whole input's rows on the device: what does not fit is refused
-template <class T>
-bqsr_status rt_need(MpBuf& b, T** p, size_t count, const char* what) {
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  if (b.cap < bytes) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      b.p = nullptr;
-      return fail(BQSR_ERR_UNSUPPORTED, std::string("realignment_targets: one input stays resident on the device and "
-                                                    "this one does not fit: ") + std::to_string(bytes) +
-                                            " bytes for its " + what);
-    }
-    b.cap = bytes;
-  }
-  *p = (T*)b.p;
-  return BQSR_OK;
-}
-
-template <class F>
-bqsr_status rt_prim(RtState& A, F&& call) {
-  size_t tb = 0;
-  HIP_TRY(call((void*)nullptr, tb));
-  uint8_t* temp;
-  const bqsr_status e = rt_need(A.temp, &temp, tb, "scan and sort workspace");
-  if (e != BQSR_OK) return e;
-  HIP_TRY(call((void*)temp, tb));
-  return BQSR_OK;
-}
-
-unsigned rt_grid(const bqsr_context* ctx, int64_t n) {
-  return sam_grid(n, rtk::kThreads, ctx->tune_pileup_grid > 0 ? ctx->tune_pileup_grid : ctx->n_cu * 8);
-}
 
 // joinTargets over singleton sets, left to right over the candidates in their
 // declared order: the running last target a = (as, ae), the next candidate b
@@ -413,26 +370,31 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   if (n == 0) return done();
   bqsr_status e;
   float ms = 0.f;
+  auto need = [](DevBuf& b, auto** p, size_t count, const char* what) {
+    return dev_need(b, p, count, "realignment_targets", what);
+  };
+  auto prim = [&](auto&& call) { return dev_prim(A.temp, "realignment_targets", call); };
+  auto grid = [&](int64_t items) { return pileup_job_grid(ctx, items, kThreads); };
   // ---- count ----
   pilk::Scratch X{};
   uint64_t* rs;
   unsigned long long* small;  // the error word, the largest readEnd
   const size_t nc = (size_t)V.cig_ops, nm = (size_t)V.md_bytes, N = (size_t)n;
-  if ((e = rt_need(A.rowpre, &X.rowpre, nc, "CIGAR elements")) || (e = rt_need(A.readpre, &X.readpre, nc, "CIGAR elements")) ||
-      (e = rt_need(A.refpre, &X.refpre, nc, "CIGAR elements")) || (e = rt_need(A.mdent, &X.mdent, nm, "MD entries")) ||
-      (e = rt_need(A.cnt, &X.cnt, N + 1, "reads")) || (e = rt_need(A.rs, &rs, N + 1, "reads")) ||
-      (e = rt_need(A.md_n, &X.md_n, N, "reads")) || (e = rt_need(A.rend, &X.rend, N, "reads")) ||
-      (e = rt_need(A.small, &small, 2, "status words")))
+  if ((e = need(A.rowpre, &X.rowpre, nc, "CIGAR elements")) || (e = need(A.readpre, &X.readpre, nc, "CIGAR elements")) ||
+      (e = need(A.refpre, &X.refpre, nc, "CIGAR elements")) || (e = need(A.mdent, &X.mdent, nm, "MD entries")) ||
+      (e = need(A.cnt, &X.cnt, N + 1, "reads")) || (e = need(A.rs, &rs, N + 1, "reads")) ||
+      (e = need(A.md_n, &X.md_n, N, "reads")) || (e = need(A.rend, &X.rend, N, "reads")) ||
+      (e = need(A.small, &small, 2, "status words")))
     return e;
   HIP_TRY(hipMemsetAsync(small, 0xFF, 8, s));
   HIP_TRY(hipMemsetAsync(small + 1, 0, 8, s));
   HIP_TRY(hipMemsetAsync(X.cnt + n, 0, 8, s));
   CountParams C{pilk::CountParams{V.R, X, 0, n, small}, small + 1};
   HIP_TRY(hipEventRecord(A.ev[0], s));
-  hipLaunchKernelGGL(rt_count, dim3(rt_grid(ctx, n)), dim3(kThreads), 0, s, C);
+  hipLaunchKernelGGL(rt_count, dim3(grid(n)), dim3(kThreads), 0, s, C);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(A.ev[1], s));
-  if ((e = rt_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, X.cnt, rs, (uint64_t)0, N + 1, rocprim::plus<uint64_t>(), s);
        })))
     return e;
@@ -457,18 +419,18 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   const int64_t m = (int64_t)total;
   A.sizes.n_rows = m;
   if (m == 0) return done();
-  const int pos_bits = std::max(1, mp_bits((uint64_t)st2[1]));
+  const int pos_bits = std::max(1, bits_of((uint64_t)st2[1]));
   // ---- emit, sort ----
   const size_t M = (size_t)m;
   uint64_t *key_a, *key_b, *val_a, *val_b;
-  if ((e = rt_need(A.key_a, &key_a, M + 2, "pileup rows")) || (e = rt_need(A.key_b, &key_b, M, "pileup rows")) ||
-      (e = rt_need(A.val_a, &val_a, M + 2, "pileup rows")) || (e = rt_need(A.val_b, &val_b, M, "pileup rows")))
+  if ((e = need(A.key_a, &key_a, M + 2, "pileup rows")) || (e = need(A.key_b, &key_b, M, "pileup rows")) ||
+      (e = need(A.val_a, &val_a, M + 2, "pileup rows")) || (e = need(A.val_b, &val_b, M, "pileup rows")))
     return e;
   EmitParams E{V.R, X, rs, n, m, key_a, val_a};
-  hipLaunchKernelGGL(rt_emit, dim3(rt_grid(ctx, m)), dim3(kThreads), 0, s, E);
+  hipLaunchKernelGGL(rt_emit, dim3(grid(m)), dim3(kThreads), 0, s, E);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(A.ev[2], s));
-  if ((e = rt_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::radix_sort_pairs(t, b, key_a, key_b, val_a, val_b, M, 0, (unsigned)pos_bits, s);
        })))
     return e;
@@ -478,11 +440,11 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   uint32_t* head = (uint32_t*)val_a;           // [M + 2]; later the event flags
   uint32_t* rod1 = (uint32_t*)val_a + (M + 2);  // [M + 2]
   uint32_t* evoff;
-  if ((e = rt_need(A.evoff, &evoff, M + 1, "pileup rows"))) return e;
-  hipLaunchKernelGGL(rt_heads, dim3(rt_grid(ctx, m)), dim3(kThreads), 0, s, (const uint64_t*)key_b,
+  if ((e = need(A.evoff, &evoff, M + 1, "pileup rows"))) return e;
+  hipLaunchKernelGGL(rt_heads, dim3(grid(m)), dim3(kThreads), 0, s, (const uint64_t*)key_b,
                      (const uint64_t*)val_b, m, head, q);
   HIP_TRY(hipGetLastError());
-  if ((e = rt_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::inclusive_scan(t, b, head, rod1, M, rocprim::plus<uint32_t>(), s);
        })))
     return e;
@@ -491,17 +453,17 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   HIP_TRY(hipStreamSynchronize(s));
   const size_t NR = n_rods32;
   uint64_t* rodq;
-  if ((e = rt_need(A.rodq, &rodq, NR + 1, "rods"))) return e;
+  if ((e = need(A.rodq, &rodq, NR + 1, "rods"))) return e;
   // (head is free: the unique keys go there, the count after the sums)
-  if ((e = rt_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::reduce_by_key(t, b, rod1, q, M, head, rodq, rodq + NR, QSum(), rocprim::equal_to<uint32_t>(), s);
        })))
     return e;
   uint32_t* isev = head;
-  hipLaunchKernelGGL(rt_evflag, dim3(rt_grid(ctx, m)), dim3(kThreads), 0, s, (const uint64_t*)val_b,
+  hipLaunchKernelGGL(rt_evflag, dim3(grid(m)), dim3(kThreads), 0, s, (const uint64_t*)val_b,
                      (const uint32_t*)rod1, (const uint64_t*)rodq, m, isev);
   HIP_TRY(hipGetLastError());
-  if ((e = rt_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, isev, evoff, (uint32_t)0, M + 1, rocprim::plus<uint32_t>(), s);
        })))
     return e;
@@ -520,15 +482,15 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   }
   Ev *ev_a, *ev_b, *hull;
   int64_t* candrod;
-  if ((e = rt_need(A.ev_a, &ev_a, NE, "events")) || (e = rt_need(A.ev_b, &ev_b, NE, "events")) ||
-      (e = rt_need(A.hull, &hull, NE, "events")) || (e = rt_need(A.candrod, &candrod, NE + 1, "events")))
+  if ((e = need(A.ev_a, &ev_a, NE, "events")) || (e = need(A.ev_b, &ev_b, NE, "events")) ||
+      (e = need(A.hull, &hull, NE, "events")) || (e = need(A.candrod, &candrod, NE + 1, "events")))
     return e;
   EventParams EP{V.R, X, key_b, val_b, rod1, isev, evoff, m, ev_a};
-  hipLaunchKernelGGL(rt_events, dim3(rt_grid(ctx, m)), dim3(kThreads), 0, s, EP);
+  hipLaunchKernelGGL(rt_events, dim3(grid(m)), dim3(kThreads), 0, s, EP);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(A.ev[4], s));
   // ---- candidates: the rods with events, their hulls, ascending by (start, position) ----
-  if ((e = rt_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::reduce_by_key(t, b, rocprim::make_transform_iterator((const Ev*)ev_a, RodOf()), (const Ev*)ev_a,
                                        NE, candrod, hull, candrod + NE, Hull(), rocprim::equal_to<int64_t>(), s);
        })))
@@ -541,19 +503,19 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   uint32_t *cval_a, *cval_b, *tid, *rod2t;
   int64_t* cend;
   uint8_t* multi;
-  if ((e = rt_need(A.ckey_a, &ckey_a, NC, "candidates")) || (e = rt_need(A.ckey_b, &ckey_b, NC, "candidates")) ||
-      (e = rt_need(A.cval_a, &cval_a, NC, "candidates")) || (e = rt_need(A.cval_b, &cval_b, NC, "candidates")) ||
-      (e = rt_need(A.cend, &cend, NC, "candidates")) || (e = rt_need(A.tid, &tid, NC, "candidates")) ||
-      (e = rt_need(A.multi, &multi, NC, "candidates")) || (e = rt_need(A.rod2t, &rod2t, NR, "rods")))
+  if ((e = need(A.ckey_a, &ckey_a, NC, "candidates")) || (e = need(A.ckey_b, &ckey_b, NC, "candidates")) ||
+      (e = need(A.cval_a, &cval_a, NC, "candidates")) || (e = need(A.cval_b, &cval_b, NC, "candidates")) ||
+      (e = need(A.cend, &cend, NC, "candidates")) || (e = need(A.tid, &tid, NC, "candidates")) ||
+      (e = need(A.multi, &multi, NC, "candidates")) || (e = need(A.rod2t, &rod2t, NR, "rods")))
     return e;
-  hipLaunchKernelGGL(rt_candkeys, dim3(rt_grid(ctx, n_cand)), dim3(kThreads), 0, s, (const Ev*)hull, n_cand, ckey_a,
+  hipLaunchKernelGGL(rt_candkeys, dim3(grid(n_cand)), dim3(kThreads), 0, s, (const Ev*)hull, n_cand, ckey_a,
                      cval_a);
   HIP_TRY(hipGetLastError());
-  if ((e = rt_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::radix_sort_pairs(t, b, ckey_a, ckey_b, cval_a, cval_b, NC, 0, (unsigned)pos_bits, s);
        })))
     return e;
-  hipLaunchKernelGGL(rt_gather, dim3(rt_grid(ctx, n_cand)), dim3(kThreads), 0, s, (const Ev*)hull,
+  hipLaunchKernelGGL(rt_gather, dim3(grid(n_cand)), dim3(kThreads), 0, s, (const Ev*)hull,
                      (const uint32_t*)cval_b, n_cand, cend);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(A.ev[5], s));
@@ -573,15 +535,15 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   HIP_TRY(hipMemcpyAsync(multi, h_multi.data(), (size_t)n_t, hipMemcpyHostToDevice, s));
   // ---- the sets of every target ----
   HIP_TRY(hipEventRecord(A.ev[6], s));
-  hipLaunchKernelGGL(rt_rod2t, dim3(rt_grid(ctx, n_cand)), dim3(kThreads), 0, s, (const int64_t*)candrod,
+  hipLaunchKernelGGL(rt_rod2t, dim3(grid(n_cand)), dim3(kThreads), 0, s, (const int64_t*)candrod,
                      (const uint32_t*)cval_b, (const uint32_t*)tid, n_cand, rod2t);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(rt_retarget, dim3(rt_grid(ctx, n_ev)), dim3(kThreads), 0, s, ev_a, n_ev, (const uint32_t*)rod2t);
+  hipLaunchKernelGGL(rt_retarget, dim3(grid(n_ev)), dim3(kThreads), 0, s, ev_a, n_ev, (const uint32_t*)rod2t);
   HIP_TRY(hipGetLastError());
-  if ((e = rt_prim(A, [&](void* t, size_t& b) { return rocprim::merge_sort(t, b, ev_a, ev_b, NE, EvLess(), s); })))
+  if ((e = prim([&](void* t, size_t& b) { return rocprim::merge_sort(t, b, ev_a, ev_b, NE, EvLess(), s); })))
     return e;
   // (ev_a is free: the unique keys go there; hull takes the survivors, candrod's last word their count)
-  if ((e = rt_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::reduce_by_key(t, b, (const Ev*)ev_b, (const Ev*)ev_b, NE, ev_a, hull, candrod + NE, Hull(),
                                        EvSame{multi}, s);
        })))
@@ -592,21 +554,21 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   const size_t NO = (size_t)n_out, NT = (size_t)n_t;
   uint32_t *isi, *islot;
   int64_t* res;
-  if ((e = rt_need(A.isi, &isi, NO + 1, "targets' ranges")) || (e = rt_need(A.islot, &islot, NO + 1, "targets' ranges")) ||
-      (e = rt_need(A.res, &res, 7 * NO + 2 * (NT + 1), "targets' ranges")))
+  if ((e = need(A.isi, &isi, NO + 1, "targets' ranges")) || (e = need(A.islot, &islot, NO + 1, "targets' ranges")) ||
+      (e = need(A.res, &res, 7 * NO + 2 * (NT + 1), "targets' ranges")))
     return e;
   A.D = Result{res, res + NO, res + 2 * NO, res + 3 * NO, res + 4 * NO, res + 5 * NO, res + 6 * NO, res + 7 * NO,
                res + 7 * NO + NT + 1};
-  hipLaunchKernelGGL(rt_isindel, dim3(rt_grid(ctx, n_out)), dim3(kThreads), 0, s, (const Ev*)hull, n_out, isi);
+  hipLaunchKernelGGL(rt_isindel, dim3(grid(n_out)), dim3(kThreads), 0, s, (const Ev*)hull, n_out, isi);
   HIP_TRY(hipGetLastError());
-  if ((e = rt_prim(A, [&](void* t, size_t& b) {
+  if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, isi, islot, (uint32_t)0, NO + 1, rocprim::plus<uint32_t>(), s);
        })))
     return e;
-  hipLaunchKernelGGL(rt_write, dim3(rt_grid(ctx, n_out)), dim3(kThreads), 0, s, (const Ev*)hull, (const uint32_t*)islot,
+  hipLaunchKernelGGL(rt_write, dim3(grid(n_out)), dim3(kThreads), 0, s, (const Ev*)hull, (const uint32_t*)islot,
                      n_out, A.D);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(rt_offsets, dim3(rt_grid(ctx, n_t + 1)), dim3(kThreads), 0, s, (const Ev*)hull,
+  hipLaunchKernelGGL(rt_offsets, dim3(grid(n_t + 1)), dim3(kThreads), 0, s, (const Ev*)hull,
                      (const uint32_t*)islot, n_out, n_t, A.D);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(A.ev[7], s));
@@ -661,7 +623,7 @@ bqsr_status bqsr_sam_realign_targets_prepare(bqsr_context* ctx, bqsr_sam* s, voi
                                              bqsr_realign_targets_sizes* out) {
   if (!ctx || !s || !out) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_realign_targets_prepare: bad arguments");
   HIP_TRY(hipSetDevice(ctx->device));
-  return rt_prepare(ctx, *rt_state(s->realign_targets), pileup_view(s), S(stream), out);
+  return rt_prepare(ctx, *job_state<RtState>(s->realign_targets), pileup_view(s), S(stream), out);
 }
 
 bqsr_status bqsr_sam_realign_targets_fetch(bqsr_context* ctx, bqsr_sam* s, const bqsr_realign_targets_host* dst,
@@ -670,7 +632,7 @@ bqsr_status bqsr_sam_realign_targets_fetch(bqsr_context* ctx, bqsr_sam* s, const
   if (!s->realign_targets)
     return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_realign_targets_fetch before bqsr_sam_realign_targets_prepare");
   HIP_TRY(hipSetDevice(ctx->device));
-  return rt_fetch(*rt_state(s->realign_targets), dst, S(stream), "bqsr_sam_realign_targets_fetch");
+  return rt_fetch(*job_state<RtState>(s->realign_targets), dst, S(stream), "bqsr_sam_realign_targets_fetch");
 }
 
 bqsr_status bqsr_arrow_realign_targets_prepare(bqsr_context* ctx, bqsr_arrow* a, void* stream,
@@ -678,7 +640,8 @@ bqsr_status bqsr_arrow_realign_targets_prepare(bqsr_context* ctx, bqsr_arrow* a,
   if (!ctx || !a || !out) return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_realign_targets_prepare: bad arguments");
   HIP_TRY(hipSetDevice(ctx->device));
   // (mapq is no part of a target: the view's mapq columns are never read)
-  return rt_prepare(ctx, *rt_state(a->realign_targets), pileup_view(a, *pileup_state(a->pileup)), S(stream), out);
+  return rt_prepare(ctx, *job_state<RtState>(a->realign_targets), pileup_view(a, *job_state<PileupState>(a->pileup)),
+                    S(stream), out);
 }
 
 bqsr_status bqsr_arrow_realign_targets_fetch(bqsr_context* ctx, bqsr_arrow* a, const bqsr_realign_targets_host* dst,
@@ -687,7 +650,7 @@ bqsr_status bqsr_arrow_realign_targets_fetch(bqsr_context* ctx, bqsr_arrow* a, c
   if (!a->realign_targets)
     return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_realign_targets_fetch before bqsr_arrow_realign_targets_prepare");
   HIP_TRY(hipSetDevice(ctx->device));
-  return rt_fetch(*rt_state(a->realign_targets), dst, S(stream), "bqsr_arrow_realign_targets_fetch");
+  return rt_fetch(*job_state<RtState>(a->realign_targets), dst, S(stream), "bqsr_arrow_realign_targets_fetch");
 }
 
 bqsr_status bqsr_realign_targets_kernel_times(double* ms7) {

@@ -229,11 +229,10 @@ bqsr_status pack_batch_device(bqsr_context* ctx, const PackCols& C, const int32_
                        (const uint64_t*)s->cig_off, (const uint64_t*)s->md_off, n, span, dl);
     HIP_TRY(hipGetLastError());
   }
-  size_t tb = 0;
-  HIP_TRY(rocprim::exclusive_scan(nullptr, tb, span, slot, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
-  void* temp = nullptr;
-  if ((e = dalloc(tmp, (uint8_t**)&temp, std::max<size_t>(tb, 1)))) return e;
-  HIP_TRY(rocprim::exclusive_scan(temp, tb, span, slot, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+  if ((e = with_temp(tmp, [&](void* t, size_t& b) {
+         return rocprim::exclusive_scan(t, b, span, slot, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st);
+       })))
+    return e;
   Lens hl;
   uint64_t n_slots = 0;
   HIP_TRY(hipMemcpyAsync(&hl, dl, sizeof hl, hipMemcpyDeviceToHost, st));

@@ -938,6 +938,17 @@ bqsr_status sam_alloc(std::vector<void*>& keep, T** p, size_t n) {
   keep.push_back((void*)*p);
   return BQSR_OK;
 }
+// a rocprim call: asked for its workspace size, then run in a workspace of that size kept in `keep`
+template <class F>
+bqsr_status with_temp(std::vector<void*>& keep, F&& call) {
+  size_t bytes = 0;
+  HIP_TRY(call((void*)nullptr, bytes));
+  uint8_t* temp = nullptr;
+  const bqsr_status e = sam_alloc(keep, &temp, bytes);
+  if (e != BQSR_OK) return e;
+  HIP_TRY(call((void*)temp, bytes));
+  return BQSR_OK;
+}
 template <class T>
 bqsr_status sam_upload(std::vector<void*>& keep, T** p, const std::vector<T>& v, hipStream_t s) {
   bqsr_status st = sam_alloc(keep, p, v.size());
@@ -966,9 +977,6 @@ bqsr_status sam_scan(const uint64_t* in, int64_t n, uint64_t* out, uint64_t* par
                      out);
   HIP_TRY(hipGetLastError());
   return BQSR_OK;
-}
-unsigned sam_grid(int64_t n, int threads, int cap) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + threads - 1) / threads, cap));
 }
 const char* kSamErrors[] = {"ok", "fewer than 11 fields", "optional field without two ':'", "FLAG is not an integer",
                             "POS is not an integer", "malformed CIGAR", "header line after the first record",

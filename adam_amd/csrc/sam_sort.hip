@@ -223,15 +223,6 @@ extern "C" __global__ void __launch_bounds__(kThreads) sort_gather_long(
 
 namespace {
 
-int bits_of(uint64_t v) {
-  int b = 0;
-  while (v) {
-    ++b;
-    v >>= 1;
-  }
-  return b;
-}
-
 struct SortTmp {
   std::vector<void*> v;
   ~SortTmp() {
@@ -287,11 +278,10 @@ bqsr_status sort_order_device(bqsr_context* ctx, int64_t n, const uint32_t* flag
   hipLaunchKernelGGL(sortk::sort_keys, dim3(g), dim3(sortk::kThreads), 0, s, flags, ref, start,
                      (const uint64_t*)before, n, first_unmapped, sb, key, idx);
   HIP_TRY(hipGetLastError());
-  size_t tb = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, key, key2, idx, order, N, 0, end_bit, s));
-  uint8_t* temp;
-  if ((e = sam_alloc(T.v, &temp, tb)) != BQSR_OK) return e;
-  HIP_TRY(rocprim::radix_sort_pairs(temp, tb, key, key2, idx, order, N, 0, end_bit, s));
+  if ((e = with_temp(T.v, [&](void* t, size_t& b) {
+         return rocprim::radix_sort_pairs(t, b, key, key2, idx, order, N, 0, end_bit, s);
+       })))
+    return e;
   HIP_TRY(hipStreamSynchronize(s));  // (the temporaries go)
   return BQSR_OK;
 }

@@ -658,11 +658,10 @@ bqsr_status tag_values_run(bqsr_context* ctx, tagk::Values V, hipStream_t s) {
   hipLaunchKernelGGL(tagk::tag_value_compact, dim3(g), dim3(tagk::kThreads), 0, s, (const uint64_t*)key,
                      (const uint64_t*)has, (const uint64_t*)off, n, ck, ci);
   HIP_TRY(hipGetLastError());
-  size_t tb = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, ck, ck2, ci, ci2, M, 0, 64, s));
-  uint8_t* temp;
-  if ((e = sam_alloc(T.v, &temp, tb)) != BQSR_OK) return e;
-  HIP_TRY(rocprim::radix_sort_pairs(temp, tb, ck, ck2, ci, ci2, M, 0, 64, s));
+  if ((e = with_temp(T.v, [&](void* t, size_t& b) {
+         return rocprim::radix_sort_pairs(t, b, ck, ck2, ci, ci2, M, 0, 64, s);
+       })))
+    return e;
   const unsigned gm = sam_grid(m, tagk::kThreads, ctx->n_cu * 8);
   hipLaunchKernelGGL(tagk::tag_value_heads, dim3(gm), dim3(tagk::kThreads), 0, s, V.text, (const uint64_t*)ck2,
                      (const uint32_t*)ci2, (const int64_t*)va, (const uint32_t*)vlen, m, head);

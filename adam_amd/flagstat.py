@@ -5,7 +5,7 @@ adam-core/.../rdd/FlagStat.scala:21-116).
     python -m adam_amd.flagstat INPUT.{sam,bam,adam,parquet} [-partition_bytes N]
 
 prints the reference's text on stdout and a ``reads=... phases=...`` line on
-stderr.  SAM text streams through the device in ``transform.sam_partitions``
+stderr.  SAM text streams through the device in ``inputs.sam_partitions``
 partitions, each parsed with the header, counted (bqsr_sam_flagstat) and
 closed; the counts are integer sums, so any number of partitions gives the
 same result.  A BAM is one parse.  ADAMRecord Parquet is read by Arrow with
@@ -23,8 +23,6 @@ import argparse
 import ctypes
 import dataclasses
 import decimal
-import mmap
-import os
 import struct
 import sys
 import time
@@ -32,6 +30,7 @@ from typing import Dict, Optional, Tuple
 
 from . import _capi, bqsr
 from ._capi import check
+from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
 
 # the command's projection (cli/FlagStat.scala:50-57), booleans in bqsr_flagstat_chunk's order
 BOOL_COLUMNS = ("readPaired", "properPair", "readMapped", "mateMapped", "firstOfPair", "secondOfPair",
@@ -166,15 +165,9 @@ def table_chunks(table):
     return chunks, keep
 
 
-# bqsr_sam_flagstat's NULL_FIELD message (flagstat.hip), for a read of a later partition
-_NULL_MAPQ = ("flagstat: read %d has its mate mapped to a different chromosome and a null mapq (the reference's "
-              "getMapq >= 5 throws a NullPointerException)")
-
-
 def _flagstat(path: str, device: int, partition_bytes: int):
-    from .transform import _Phases, _host_bytes, is_bam, is_parquet, sam_partitions
     ctx = bqsr.Context.get(device)
-    ph = _Phases()
+    ph = Phases()
     failed, passed = FlagStatMetrics(), FlagStatMetrics()
     stats: Dict[str, object] = {"reads": 0}
     if is_parquet(path):
@@ -187,43 +180,17 @@ def _flagstat(path: str, device: int, partition_bytes: int):
         del keep
         stats["reads"] = table.num_rows
     else:
-        from .sam import SamText
-        n_reads = 0
-        with open(path, "rb") as fh:
-            data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if os.path.getsize(path) else b""
-            try:
-                # (the views of the mmap are made inside the calls, so that none outlives them)
-                if is_bam(data) or not len(data):
-                    makes = [lambda: _host_bytes(data)]
-                else:
-                    header, ranges = sam_partitions(data, partition_bytes)
-                    if len(ranges) <= 1:
-                        makes = [lambda: _host_bytes(data)]
-                    else:
-                        makes = [lambda a=a, b=b: header + bytes(data[a:b]) for a, b in ranges]
-                    stats["partitions"] = len(makes)
-                bam = is_bam(data)
-                for make in makes:
-                    with ph("parse"):
-                        sam = SamText(make(), ctx, bam=bam)
+        with SamInput(path, ctx, ph, partition_bytes) as src:
+            if not src.bam and len(src.data):
+                stats["partitions"] = src.n_partitions
+            for sam, base in src:
+                with ph("flagstat"):
                     try:
-                        with ph("flagstat"):
-                            try:
-                                f, p = sam_flagstat(sam)
-                            except _capi.BQSRError as e:
-                                if e.status == _capi.NULL_FIELD and e.read >= 0 and n_reads:
-                                    # the message and .read name the ordinal in the whole input
-                                    raise _capi.BQSRError(e.status, _NULL_MAPQ % (e.read + n_reads),
-                                                          e.read + n_reads) from None
-                                raise
-                        failed, passed = failed + f, passed + p
-                        n_reads += sam.counts().n_reads
-                    finally:
-                        sam.close()
-            finally:
-                if isinstance(data, mmap.mmap):
-                    data.close()
-        stats["reads"] = n_reads
+                        f, p = sam_flagstat(sam)
+                    except _capi.BQSRError as e:
+                        raise rebased(e, base) from None
+                failed, passed = failed + f, passed + p
+                stats["reads"] = base + sam.counts().n_reads
     stats["phases"] = ph.t
     return failed, passed, stats
 
@@ -233,8 +200,7 @@ def flagstat(path: str, device: int = 0, partition_bytes: Optional[int] = None
     """adamFlagStat of a SAM, BAM or ADAMRecord Parquet input: (failed,
     passed), the reference's order (rdd/FlagStat.scala:102-114).
     partition_bytes: SAM text per streamed partition (default:
-    transform.DEFAULT_PARTITION_BYTES)."""
-    from .transform import DEFAULT_PARTITION_BYTES
+    inputs.DEFAULT_PARTITION_BYTES)."""
     f, p, _ = _flagstat(path, device, DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes)
     return f, p
 
@@ -292,7 +258,6 @@ def format_flagstat(failed: FlagStatMetrics, passed: FlagStatMetrics) -> str:
 
 
 def main(argv=None) -> int:
-    from .transform import DEFAULT_PARTITION_BYTES
     ap = argparse.ArgumentParser(prog="adam_amd.flagstat", description=__doc__.split("\n\n")[0])
     ap.add_argument("input")
     ap.add_argument("-partition_bytes", type=int, default=DEFAULT_PARTITION_BYTES,
@@ -300,9 +265,8 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     t0 = time.perf_counter()
     failed, passed, st = _flagstat(a.input, 0, a.partition_bytes)
-    st["seconds"] = time.perf_counter() - t0
     print(format_flagstat(failed, passed))
-    print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
+    report(st, t0)
     return 0
 
 

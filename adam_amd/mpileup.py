@@ -50,7 +50,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import mmap
 import os
 import sys
 import time
@@ -60,6 +59,7 @@ import numpy as np
 
 from . import _capi, bqsr
 from ._capi import check
+from .inputs import Phases, SamInput, is_parquet, report, text_output
 
 # Text per window.  A window's bytes exist once on the device and once in
 # pinned host memory; 64 MiB keeps both small beside either memory and is far
@@ -198,7 +198,7 @@ def _filtered(table):
     return kept.drop_columns([col]), rows
 
 
-def _rebased(e: _capi.BQSRError, rows) -> _capi.BQSRError:
+def _input_row(e: _capi.BQSRError, rows) -> _capi.BQSRError:
     """the error naming the read by its index in the table :func:`_filtered`
     was given, not among the rows it kept"""
     if e.status == _capi.REFERENCE_CONFLICT or e.read < 0:
@@ -211,31 +211,23 @@ def _rebased(e: _capi.BQSRError, rows) -> _capi.BQSRError:
 def mpileup(inp: str, out: Optional[str] = None, window_bytes: int = DEFAULT_WINDOW_BYTES, device: int = 0,
             stdout=None) -> Dict[str, object]:
     """`adam mpileup`: the pileup text of a SAM, BAM or ADAMRecord Parquet
-    input, to `out` (written under a temporary name and renamed when the job
-    succeeded; on failure no file appears) or, without it, to stdout (after
-    the job's checks have passed: nothing is printed on a failure).  Returns
-    the job's statistics; raises :class:`_capi.BQSRError` as the module doc
-    says (``.read``: the read's index in the input; for REFERENCE_CONFLICT
-    the position)."""
-    from .transform import _Phases, _host_bytes, is_bam, is_parquet
+    input, to `out` or, without it, to stdout (inputs.text_output: the job's
+    checks have passed before the first byte is written).  Returns the job's
+    statistics; raises :class:`_capi.BQSRError` as the module doc says
+    (``.read``: the read's index in the input; for REFERENCE_CONFLICT the
+    position)."""
     if int(window_bytes) < 1:
         raise ValueError("window_bytes must be at least 1")
-    if out is not None and os.path.isdir(out):
-        raise IsADirectoryError("output path %s is a directory" % out)
-    ctx = bqsr.Context.get(device)
-    ph = _Phases()
+    ph = Phases()
     stats: Dict[str, object] = {}
-    tmp = None if out is None else "%s.partial.%d" % (out, os.getpid())
-    sink = None
-    done = False
-    try:
+    with text_output(out, stdout) as sink:
+        ctx = bqsr.Context.get(device)
+
         def run(prepare, windows, n_reads):
-            nonlocal sink
             with ph("prepare"):
                 sz = prepare()
             kt = kernel_times()
             stats.update(reads=n_reads, kept=sz.n_reads, events=sz.n_events, lines=sz.n_lines, bytes=sz.text_bytes)
-            sink = open(tmp, "wb") if tmp else (stdout or getattr(sys.stdout, "buffer", sys.stdout))
             text_ms = 0.0
             it = windows(sz)
             while True:
@@ -259,35 +251,14 @@ def mpileup(inp: str, out: Optional[str] = None, window_bytes: int = DEFAULT_WIN
                 try:
                     run(lambda: arrow_prepare(A), lambda sz: arrow_mpileup(A, window_bytes, sizes=sz), len(rows))
                 except _capi.BQSRError as e:
-                    raise _rebased(e, rows) from None
+                    raise _input_row(e, rows) from None
             finally:
                 A.close()
         else:
-            from .sam import SamText
-            with open(inp, "rb") as fh:
-                data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if os.path.getsize(inp) else b""
-                try:
-                    with ph("parse"):
-                        sam = SamText(_host_bytes(data), ctx, bam=is_bam(data))
-                    try:
-                        run(lambda: sam_prepare(sam), lambda sz: sam_mpileup(sam, window_bytes, sizes=sz),
-                            sam.counts().n_reads)
-                    finally:
-                        sam.close()
-                finally:
-                    if isinstance(data, mmap.mmap):
-                        data.close()
-        done = True
-    finally:
-        if tmp:
-            if sink is not None:
-                sink.close()
-            if done:
-                os.replace(tmp, out)
-            elif os.path.lexists(tmp):
-                os.unlink(tmp)
-        elif sink is not None and done:
-            sink.flush()
+            with SamInput(inp, ctx, ph) as src:
+                for sam, _ in src:
+                    run(lambda: sam_prepare(sam), lambda sz: sam_mpileup(sam, window_bytes, sizes=sz),
+                        sam.counts().n_reads)
     stats["phases"] = ph.t
     return stats
 
@@ -305,8 +276,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("no such input: %s" % a.input)
     t0 = time.perf_counter()
     st = mpileup(a.input, a.output, a.window_bytes)
-    st["seconds"] = time.perf_counter() - t0
-    print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
+    report(st, t0)
     return 0
 
 

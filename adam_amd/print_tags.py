@@ -9,7 +9,7 @@ prints on stdout, for the records with failedVendorQualityChecks false: with
 ``-list N`` the attributes of the first N of them, then a ``"%3s\\t%d"`` line
 per tag, under a tag named by ``-count`` a ``"\\t%10d\\t%s"`` line per distinct
 value, and ``Total: %d``; a ``reads=... phases=...`` line goes to stderr.  SAM
-text streams through the device in ``transform.sam_partitions`` partitions
+text streams through the device in ``inputs.sam_partitions`` partitions
 (bqsr_sam_tag_counts; integer sums, so any number of partitions gives the same
 result); a BAM is one parse.  ADAMRecord Parquet is read by Arrow with the
 command's projection (only the columns the file has) and every record batch's
@@ -33,8 +33,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import mmap
-import os
 import sys
 import time
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
@@ -43,6 +41,7 @@ import numpy as np
 
 from . import _capi, bqsr
 from ._capi import check
+from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
 
 # the command's projection (cli/PrintTags.scala:68)
 PROJECTION = ("attributes", "primaryAlignment", "readMapped", "readPaired", "failedVendorQualityChecks")
@@ -220,15 +219,6 @@ def table_chunks(table):
     return chunks, keep
 
 
-def _rebased(e: _capi.BQSRError, base: int) -> _capi.BQSRError:
-    """e of a later partition with the read's ordinal in the whole input, in
-    .read and in the message"""
-    if e.read < 0 or not base:
-        return e
-    msg = str(e).split(": ", 1)[1].replace("read %d" % e.read, "read %d" % (e.read + base))
-    return _capi.BQSRError(e.status, msg, e.read + base)
-
-
 def _table_list(table, list_n: int) -> List[str]:
     """the attributes of the first list_n kept records of an Arrow table ('null' for a null)"""
     out: List[str] = []
@@ -265,9 +255,8 @@ def _sam_list(sam, hdr, want: int, out: List[str]) -> None:
 def _run(path: str, list_n: Optional[int], count: Iterable[str], device: int, partition_bytes: int,
          hash_bits: int = HASH_BITS):
     """(list lines, {tag: count}, {tag: {(type, text): count}}, total, stats)"""
-    from .transform import _Phases, _host_bytes, is_bam, is_parquet, sam_partitions
     ctx = bqsr.Context.get(device)
-    ph = _Phases()
+    ph = Phases()
     tags: Dict[str, int] = {}
     values: Dict[str, Dict[ValueKey, int]] = {}
     lines: List[str] = []
@@ -299,63 +288,44 @@ def _run(path: str, list_n: Optional[int], count: Iterable[str], device: int, pa
         stats["reads"] = table.num_rows
     else:
         from .adam_save import header_info
-        from .sam import SamText
-        with open(path, "rb") as fh:
-            data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if os.path.getsize(path) else b""
-            try:
-                bam = is_bam(data)
-                if bam or not len(data):
-                    makes = [lambda: _host_bytes(data)]
-                else:
-                    header, ranges = sam_partitions(data, partition_bytes)
-                    if len(ranges) <= 1:
-                        makes = [lambda: _host_bytes(data)]
-                    else:
-                        makes = [lambda a=a, b=b: header + bytes(data[a:b]) for a, b in ranges]
-                    stats["partitions"] = len(makes)
+        with SamInput(path, ctx, ph, partition_bytes) as src:
+            if not src.bam and len(src.data):
+                stats["partitions"] = src.n_partitions
 
-                def passes(work):
-                    n_reads = 0
-                    for make in makes:
-                        with ph("parse"):
-                            sam = SamText(make(), ctx, bam=bam)
-                        try:
-                            try:
-                                work(sam)
-                            except _capi.BQSRError as e:
-                                raise _rebased(e, n_reads) from None
-                            n_reads += sam.counts().n_reads
-                        finally:
-                            sam.close()
-                    return n_reads
+            def passes(work):
+                n_reads = 0
+                for sam, base in src:
+                    try:
+                        work(sam)
+                    except _capi.BQSRError as e:
+                        raise rebased(e, base) from None
+                    n_reads = base + sam.counts().n_reads
+                return n_reads
 
-                def first(sam):
-                    nonlocal total
-                    with ph("tags"):
-                        c, n = sam_tag_counts(sam)
-                        timed("scan")
-                    _add(tags, c)
-                    total += n
-                    if len(lines) < want_list:  # (only as many leading partitions as needed)
-                        with ph("list"):
-                            _sam_list(sam, header_info(sam), want_list, lines)
+            def first(sam):
+                nonlocal total
+                with ph("tags"):
+                    c, n = sam_tag_counts(sam)
+                    timed("scan")
+                _add(tags, c)
+                total += n
+                if len(lines) < want_list:  # (only as many leading partitions as needed)
+                    with ph("list"):
+                        _sam_list(sam, header_info(sam), want_list, lines)
 
-                stats["reads"] = passes(first)
-                counted = [t for t in names if t in tags]
-                if counted:  # one more pass: every counted tag, partition by partition
-                    for t in counted:
-                        values[t] = {}
+            stats["reads"] = passes(first)
+            counted = [t for t in names if t in tags]
+            if counted:  # one more pass: every counted tag, partition by partition
+                for t in counted:
+                    values[t] = {}
 
-                    def second(sam):
-                        with ph("values"):
-                            for t in counted:
-                                _add(values[t], sam_tag_values(sam, t, hash_bits))
-                                timed("values")
+                def second(sam):
+                    with ph("values"):
+                        for t in counted:
+                            _add(values[t], sam_tag_values(sam, t, hash_bits))
+                            timed("values")
 
-                    passes(second)
-            finally:
-                if isinstance(data, mmap.mmap):
-                    data.close()
+                passes(second)
     stats["phases"] = ph.t
     stats["kernel_ms"] = kernel_ms
     return lines, tags, values, total, stats
@@ -364,7 +334,6 @@ def _run(path: str, list_n: Optional[int], count: Iterable[str], device: int, pa
 def characterize_tags(path: str, device: int = 0, partition_bytes: Optional[int] = None) -> Dict[str, int]:
     """adamCharacterizeTags of the kept records of a SAM, BAM or ADAMRecord
     Parquet input: {tag: count} (AdamRDDFunctions.scala:200-209)."""
-    from .transform import DEFAULT_PARTITION_BYTES
     return _run(path, None, (), device, DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes)[1]
 
 
@@ -373,7 +342,6 @@ def characterize_tag_values(path: str, tag: str, device: int = 0, partition_byte
     """adamCharacterizeTagValues: {(type letter, value text): count} of the
     kept records' values of `tag` (AdamRDDFunctions.scala:211-219).  A tag
     whose length is not 2 raises ValueError (the reference's assert)."""
-    from .transform import DEFAULT_PARTITION_BYTES
     _tag_bytes(tag)
     pb = DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes
     return _run(path, None, (tag,), device, pb, hash_bits)[2].get(tag, {})
@@ -403,14 +371,12 @@ def print_tags(path: str, list_n: Optional[int] = None, count: Iterable[str] = (
     """The text `adam print_tags INPUT [-list list_n] [-count ...]` prints.  A
     `count` name that is not a two-char tag of the input is ignored, as in the
     reference."""
-    from .transform import DEFAULT_PARTITION_BYTES
     pb = DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes
     lines, tags, values, total, _ = _run(path, list_n, tuple(count), device, pb)
     return format_tags(lines, tags, values, total)
 
 
 def main(argv=None) -> int:
-    from .transform import DEFAULT_PARTITION_BYTES
     ap = argparse.ArgumentParser(prog="adam_amd.print_tags", description=__doc__.split("\n\n")[0])
     ap.add_argument("input")
     ap.add_argument("-list", type=int, default=None, metavar="N",
@@ -423,9 +389,8 @@ def main(argv=None) -> int:
     t0 = time.perf_counter()
     count = tuple(a.count.split(",")) if a.count is not None else ()
     lines, tags, values, total, st = _run(a.input, a.list, count, 0, a.partition_bytes)
-    st["seconds"] = time.perf_counter() - t0
     print(format_tags(lines, tags, values, total))
-    print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
+    report(st, t0)
     return 0
 
 

@@ -38,8 +38,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import mmap
-import os
 import sys
 import time
 from typing import Dict, List, Optional, Sequence
@@ -49,7 +47,8 @@ import numpy as np
 from . import _capi, bqsr
 from ._capi import check
 from .adam_save import (BASES, PILEUP_DICT_COLS, PILEUP_FIELDS, PILEUP_STATS_COLS, RG_TAGS, AdamHost, AdamSizes,
-                        AdamWriter, HeaderInfo, _pinned, header_info, pileup_schema)
+                        AdamWriter, HeaderInfo, _pinned, check_out, header_info, pileup_schema)
+from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
 
 # Reads per part file.  A read gives about as many rows as it has bases and a
 # row takes 54 bytes of device columns and as many of pinned host memory
@@ -341,20 +340,11 @@ def locus_filter(table):
     return table.filter(mask)
 
 
-def _rebased(e: _capi.BQSRError, base: int) -> _capi.BQSRError:
-    """the error naming the read's ordinal in the whole input"""
-    if e.read < 0 or not base:
-        return e
-    msg = str(e).split(": ", 1)[1].replace("read %d:" % e.read, "read %d:" % (e.read + base), 1)
-    return _capi.BQSRError(e.status, msg, e.read + base)
-
-
 def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_bytes: int, overwrite: bool,
                device: int, writer_args: Optional[dict] = None) -> Dict[str, object]:
-    from .transform import _Phases, _check_out, _host_bytes, is_bam, is_parquet, sam_partitions
-    _check_out(out, overwrite, True)
+    check_out(out, overwrite, True)
     ctx = bqsr.Context.get(device)
-    ph = _Phases()
+    ph = Phases()
     part_reads = max(1, int(part_reads))
     stats: Dict[str, object] = {"reads": 0, "pileups": 0}
     W = AdamWriter(out, compression, overwrite=overwrite, dict_cols=PILEUP_DICT_COLS, stats_cols=PILEUP_STATS_COLS,
@@ -367,7 +357,7 @@ def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_
                     with ph("pileups"):
                         t = make_table(r0, min(part_reads, n - r0))
                 except _capi.BQSRError as e:
-                    raise _rebased(e, base) from None
+                    raise rebased(e, base) from None
                 if t.num_rows:
                     stats["pileups"] += t.num_rows
                     with ph("write"):
@@ -385,32 +375,13 @@ def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_
                 A.close()
             stats["reads"] = table.num_rows
         else:
-            from .sam import SamText
-            n_reads = 0
-            with open(inp, "rb") as fh:
-                data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if os.path.getsize(inp) else b""
-                try:
-                    bam = is_bam(data)
-                    makes = [lambda: _host_bytes(data)]
-                    if not bam and len(data):
-                        header, ranges = sam_partitions(data, partition_bytes)
-                        if len(ranges) > 1:
-                            makes = [lambda a=a, b=b: header + bytes(data[a:b]) for a, b in ranges]
-                    stats["partitions"] = len(makes)
-                    for make in makes:
-                        with ph("parse"):
-                            sam = SamText(make(), ctx, bam=bam)
-                        try:
-                            hdr = header_info(sam)
-                            n = sam.counts().n_reads
-                            emit(lambda r0, m: sam_pileups(sam, r0, m, hdr), n, n_reads)
-                            n_reads += n
-                        finally:
-                            sam.close()
-                finally:
-                    if isinstance(data, mmap.mmap):
-                        data.close()
-            stats["reads"] = n_reads
+            with SamInput(inp, ctx, ph, partition_bytes) as src:
+                stats["partitions"] = src.n_partitions
+                for sam, base in src:
+                    hdr = header_info(sam)
+                    n = sam.counts().n_reads
+                    emit(lambda r0, m: sam_pileups(sam, r0, m, hdr), n, base)
+                    stats["reads"] = base + n
         if W.parts == 0:  # no pileups at all: one empty part file carries the schema
             W.add(pileup_schema().empty_table())
         ok = True
@@ -431,9 +402,8 @@ def reads2ref(inp: str, out: str, aggregate: bool = False, min_mapq: int = 30, c
     an earlier part-file directory is replaced).  min_mapq is accepted and
     ignored, as the reference never reads its -mapq.  part_reads: reads per
     part file (:data:`DEFAULT_PART_READS`); partition_bytes: SAM text per
-    streamed partition (transform.DEFAULT_PARTITION_BYTES).  Returns the
+    streamed partition (inputs.DEFAULT_PARTITION_BYTES).  Returns the
     job's statistics."""
-    from .transform import DEFAULT_PARTITION_BYTES
     if aggregate:
         raise ValueError("-aggregate is outside this build: PileupAggregator joins read names in Spark's shuffle "
                          "order, so the reference itself does not define its result")
@@ -443,7 +413,6 @@ def reads2ref(inp: str, out: str, aggregate: bool = False, min_mapq: int = 30, c
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    from .transform import DEFAULT_PARTITION_BYTES
     ap = argparse.ArgumentParser(prog="adam_amd.reads2ref", description=__doc__.split("\n\n")[0])
     ap.add_argument("input")
     ap.add_argument("output")
@@ -461,8 +430,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     t0 = time.perf_counter()
     st = reads2ref(a.input, a.output, False, a.mapq, a.parquet_compression, a.part_reads, a.partition_bytes,
                    a.overwrite)
-    st["seconds"] = time.perf_counter() - t0
-    print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
+    report(st, t0)
     return 0
 
 

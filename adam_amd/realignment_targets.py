@@ -45,7 +45,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import mmap
 import os
 import sys
 import time
@@ -55,6 +54,7 @@ import numpy as np
 
 from . import bqsr
 from ._capi import check
+from .inputs import Phases, SamInput, is_parquet, report, text_output
 
 # the ADAMRecord columns read from Parquet: reads2ref's without the read-level
 # ones it only copies and without LocusPredicate's, except readMapped, which
@@ -165,9 +165,8 @@ def realignment_targets(path: str, device: int = 0, stats: Optional[dict] = None
     ``snp_*`` arrays.  Raises :class:`_capi.BQSRError` (``.read``: the read's
     index in the input) where the reference throws.  `stats`, when given,
     receives the job's sizes, phase and kernel times."""
-    from .transform import _Phases, _host_bytes, is_bam, is_parquet
     ctx = bqsr.Context.get(device)
-    ph = _Phases()
+    ph = Phases()
 
     def job(prepare, fetch, n_reads):
         with ph("prepare"):
@@ -191,19 +190,9 @@ def realignment_targets(path: str, device: int = 0, stats: Optional[dict] = None
         finally:
             A.close()
     else:
-        from .sam import SamText
-        with open(path, "rb") as fh:
-            data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if os.path.getsize(path) else b""
-            try:
-                with ph("parse"):
-                    sam = SamText(_host_bytes(data), ctx, bam=is_bam(data))
-                try:
-                    out = job(lambda: sam_prepare(sam), lambda sz: sam_targets(sam, sizes=sz), sam.counts().n_reads)
-                finally:
-                    sam.close()
-            finally:
-                if isinstance(data, mmap.mmap):
-                    data.close()
+        with SamInput(path, ctx, ph) as src:
+            for sam, _ in src:
+                out = job(lambda: sam_prepare(sam), lambda sz: sam_targets(sam, sizes=sz), sam.counts().n_reads)
     if stats is not None:
         stats["phases"] = ph.t
     return out
@@ -227,27 +216,12 @@ def format_targets(t: Dict[str, np.ndarray], targets_only: bool = False) -> str:
 
 def write_targets(inp: str, out: Optional[str] = None, targets_only: bool = False, device: int = 0,
                   stdout=None) -> Dict[str, object]:
-    """The command: the targets of `inp` as text to `out` (written under a
-    temporary name and renamed when the job succeeded; on failure no file
-    appears) or, without it, to stdout (nothing on a failure).  Returns the
-    job's statistics."""
-    if out is not None and os.path.isdir(out):
-        raise IsADirectoryError("output path %s is a directory" % out)
+    """The command: the targets of `inp` as text to `out` or, without it, to
+    stdout (inputs.text_output).  Returns the job's statistics."""
     stats: Dict[str, object] = {}
-    text = format_targets(realignment_targets(inp, device, stats), targets_only).encode()
-    if out is None:
-        sink = stdout or getattr(sys.stdout, "buffer", sys.stdout)
+    with text_output(out, stdout) as sink:
+        text = format_targets(realignment_targets(inp, device, stats), targets_only).encode()
         sink.write(text)
-        sink.flush()
-    else:
-        tmp = "%s.partial.%d" % (out, os.getpid())
-        try:
-            with open(tmp, "wb") as fh:
-                fh.write(text)
-            os.replace(tmp, out)
-        finally:
-            if os.path.lexists(tmp):
-                os.unlink(tmp)
     stats["bytes"] = len(text)
     return stats
 
@@ -262,8 +236,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("no such input: %s" % a.input)
     t0 = time.perf_counter()
     st = write_targets(a.input, a.output, a.targets_only)
-    st["seconds"] = time.perf_counter() - t0
-    print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
+    report(st, t0)
     return 0
 
 

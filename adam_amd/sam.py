@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _capi, bqsr
 from ._capi import check
+from .inputs import is_bam
 from .records import RecordBatch
 
 
@@ -129,7 +130,7 @@ class SamText:
         """A .sam or .bam file (BAM by its BGZF magic)."""
         with open(path, "rb") as fh:
             data = fh.read()
-        return cls(data, ctx, bam=data[:4] == b"\x1f\x8b\x08\x04")
+        return cls(data, ctx, bam=is_bam(data))
 
     @property
     def bam_form(self) -> int:

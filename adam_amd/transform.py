@@ -68,7 +68,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import mmap
 import os
 import shutil
 import sys
@@ -80,32 +79,10 @@ import numpy as np
 from . import _capi, bqsr
 from . import distributed as D
 from ._capi import check
+from .adam_save import check_out as _check_out
+from .inputs import DEFAULT_PARTITION_BYTES, SamInput, is_bam, is_parquet, report, sam_partitions  # noqa: F401
+from .inputs import Phases as _Phases, host_bytes as _host_bytes  # noqa: F401
 from .sam import SamText
-
-DEFAULT_PARTITION_BYTES = 8 << 30  # SAM text per partition: ~3x that in HBM while parsed (288 GB per GPU)
-
-
-def sam_partitions(data, partition_bytes: int) -> Tuple[bytes, List[Tuple[int, int]]]:
-    """(header, ranges): the SAM header lines and the byte ranges [a, b) of
-    the records, each range cut after the first newline at or beyond
-    partition_bytes from its start (so every record lies in one range)."""
-    n = len(data)
-    pos = 0
-    while pos < n and data[pos:pos + 1] == b"@":
-        nl = data.find(b"\n", pos)
-        pos = n if nl < 0 else nl + 1
-    ranges = []
-    a = pos
-    step = max(1, int(partition_bytes))
-    while a < n:
-        b = min(n, a + step)
-        if b < n:
-            nl = data.find(b"\n", b - 1)
-            b = n if nl < 0 else nl + 1
-        ranges.append((a, b))
-        a = b
-    return bytes(data[:pos]), ranges
-
 
 def _bqsr_partitions(data, header: bytes, ranges: List[Tuple[int, int]], snp, ctx, device: int, emit,
                      max_exc: int = 1 << 16, dups=None) -> Dict[str, float]:
@@ -235,32 +212,6 @@ def _partitions(data, header: bytes, ranges, mark_duplicates: bool, recalibrate:
         if dups is not None:
             dups.close()
     return stats
-
-
-def is_parquet(path: str) -> bool:
-    """ADAM's own format: a Parquet file (magic PAR1) or a directory of part
-    files (what adamSave writes), or a .adam / .parquet name."""
-    if path.endswith((".adam", ".parquet")) or os.path.isdir(path):
-        return True
-    try:
-        with open(path, "rb") as fh:
-            return fh.read(4) == b"PAR1"
-    except OSError:
-        return False
-
-
-def _check_out(path: str, overwrite: bool, adam: bool) -> None:
-    """The output path must not exist (adamSave's FileOutputFormat refuses an
-    existing one); with overwrite, only a regular file, or (ADAM output) a
-    directory of nothing but part files, may be replaced."""
-    from .adam_save import is_adam_output
-    for p in (path, path + ".partial"):
-        if not os.path.lexists(p):
-            continue
-        if not overwrite:
-            raise FileExistsError("output path %s already exists" % p)
-        if os.path.isdir(p) and not (adam and is_adam_output(p)):
-            raise FileExistsError("refusing to replace directory %s" % p)
 
 
 def transform_parquet(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bool = False,
@@ -562,37 +513,6 @@ class _AdamOut:
         self.w.close(ok)
 
 
-class _Phases:
-    """wall time per named phase (the stats' phase split)"""
-
-    def __init__(self):
-        self.t: Dict[str, float] = {}
-
-    def __call__(self, name: str):
-        import contextlib
-
-        @contextlib.contextmanager
-        def cm():
-            t0 = time.perf_counter()
-            try:
-                yield
-            finally:
-                self.t[name] = self.t.get(name, 0.0) + time.perf_counter() - t0
-        return cm()
-
-
-def _host_bytes(data):
-    """the input as a bytes-like object ctypes can pass without a copy: a
-    read-only mmap is passed as a numpy view's address"""
-    if isinstance(data, mmap.mmap):
-        return np.frombuffer(data, np.uint8)
-    return data
-
-
-def is_bam(data) -> bool:
-    return bytes(data[:4]) == b"\x1f\x8b\x08\x04"
-
-
 def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bool = False,
               dbsnp: Optional[str] = None, device: int = 0, partition_bytes: int = DEFAULT_PARTITION_BYTES,
               compression: str = "gzip", part_reads: int = 1 << 19, overwrite: bool = False,
@@ -620,14 +540,10 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
                          "use a .adam / .parquet output, or SAM / BAM input")
     if is_parquet(inp):
         return transform_parquet(inp, out, mark_duplicates, recalibrate, dbsnp, device, overwrite, sort_reads)
-    if sort_reads and os.path.getsize(inp):  # refused before any output file or parse exists
-        with open(inp, "rb") as fh:
-            data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
-            try:
-                if not is_bam(data) and len(sam_partitions(data, partition_bytes)[1]) > 1:
-                    raise ValueError("-sort_reads needs the input in one partition; raise -partition_bytes")
-            finally:
-                data.close()
+    if sort_reads:  # refused before any output file or parse exists
+        with SamInput(inp, None, None, partition_bytes) as src:
+            if src.n_partitions > 1:
+                raise ValueError("-sort_reads needs the input in one partition; raise -partition_bytes")
     t0 = time.perf_counter()
     # ADAM output by name, or over an earlier adamSave directory (never just
     # because `out` is some existing directory: the sinks refuse that)
@@ -643,57 +559,45 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
     ok = False
     stats: Dict[str, float] = {}
     try:
-        with open(inp, "rb") as fh:
-            data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if os.path.getsize(inp) else b""
-            try:
-                bam = is_bam(data)
-                ranges = None
-                if (recalibrate or mark_duplicates or sort_reads) and not bam and len(data):
-                    header, ranges = sam_partitions(data, partition_bytes)
-                if ranges is not None and len(ranges) > 1:
-                    stats = _partitions(data, header, ranges, mark_duplicates, recalibrate, dbsnp, ctx, device,
-                                        sink.emit)
-                else:
-                    ph = _Phases()
-                    with ph("parse"):
-                        sam = SamText(_host_bytes(data), ctx, bam=bam)
-                    try:
-                        stats["reads"] = sam.counts().n_reads
-                        if mark_duplicates:
-                            with ph("markdup"):
-                                stats["duplicates"] = sam.mark_duplicates()
-                        if recalibrate:
-                            from .job import ResidentJob
-                            snp = bqsr.SnpTable.from_vcf(dbsnp) if dbsnp else bqsr.SnpTable()
-                            with ph("batch"):
-                                job = ResidentJob(None, None, snp if snp.table else None, device, sam=sam)
-                            try:
-                                with ph("bqsr"):
-                                    job.step()
-                                p = job._ptr
-                                quals = (job.bh, p(job.out_qual), p(job.out_start), p(job.out_len), p(job.exc),
-                                         job.n_exc, job.sp)
-                                if sort_reads:  # the recalibrated text first: the apply's outputs are in input order
-                                    with ph("sort"):
-                                        check(_capi.lib().bqsr_sam_rewrite_quals(ctx.handle, sam.h, *quals))
-                                        sam.sort()
-                                    quals = None
-                                with ph("emit"):
-                                    sink.emit(0, sam, quals)
-                            finally:
-                                job.close()
-                        else:
-                            if sort_reads:
-                                with ph("sort"):  # (MarkDuplicates' FLAG bits go into the text there)
+        ph = _Phases()
+        # (without a step that works across the whole input the records go through in one parse)
+        with SamInput(inp, ctx, ph, partition_bytes if recalibrate or mark_duplicates or sort_reads else None) as src:
+            if src.n_partitions > 1:
+                stats = _partitions(src.data, src.header, src.ranges, mark_duplicates, recalibrate, dbsnp, ctx, device,
+                                    sink.emit)
+            else:
+                for sam, _ in src:
+                    stats["reads"] = sam.counts().n_reads
+                    if mark_duplicates:
+                        with ph("markdup"):
+                            stats["duplicates"] = sam.mark_duplicates()
+                    if recalibrate:
+                        from .job import ResidentJob
+                        snp = bqsr.SnpTable.from_vcf(dbsnp) if dbsnp else bqsr.SnpTable()
+                        with ph("batch"):
+                            job = ResidentJob(None, None, snp if snp.table else None, device, sam=sam)
+                        try:
+                            with ph("bqsr"):
+                                job.step()
+                            p = job._ptr
+                            quals = (job.bh, p(job.out_qual), p(job.out_start), p(job.out_len), p(job.exc),
+                                     job.n_exc, job.sp)
+                            if sort_reads:  # the recalibrated text first: the apply's outputs are in input order
+                                with ph("sort"):
+                                    check(_capi.lib().bqsr_sam_rewrite_quals(ctx.handle, sam.h, *quals))
                                     sam.sort()
+                                quals = None
                             with ph("emit"):
-                                sink.emit(0, sam, None)
-                    finally:
-                        sam.close()
-                    stats["phases"] = ph.t
-            finally:
-                if isinstance(data, mmap.mmap):
-                    data.close()
+                                sink.emit(0, sam, quals)
+                        finally:
+                            job.close()
+                    else:
+                        if sort_reads:
+                            with ph("sort"):  # (MarkDuplicates' FLAG bits go into the text there)
+                                sam.sort()
+                        with ph("emit"):
+                            sink.emit(0, sam, None)
+                stats["phases"] = ph.t
         ok = True
     finally:
         t1 = time.perf_counter()
@@ -738,11 +642,12 @@ def main(argv=None) -> int:
         ap.error("-bam_compressor applies to BAM output only (an output name ending in .bam)")
     if a.bam_compressor == "device" and a.bam_compression_level is not None:
         ap.error(DEVICE_LEVEL_REFUSAL)
+    t0 = time.perf_counter()
     st = transform(a.input, a.output, a.mark_duplicate_reads, a.recalibrate_base_qualities, a.dbsnp_sites,
                    partition_bytes=a.partition_bytes, compression=a.parquet_compression, part_reads=a.part_reads,
                    overwrite=a.overwrite, sort_reads=a.sort_reads, bam_level=a.bam_compression_level,
                    bam_compressor=a.bam_compressor)
-    print(" ".join("%s=%s" % kv for kv in st.items()), file=sys.stderr)
+    report(st, t0)
     return 0
 
 

@@ -44,7 +44,7 @@ def arrow_text_of(table):
     try:
         return b"".join(A.mpileup())
     except _capi.BQSRError as e:  # (the read's index in `table`, as the command reports it)
-        raise M._rebased(e, rows) from None
+        raise M._input_row(e, rows) from None
     finally:
         A.close()
 
