@@ -38,6 +38,7 @@ EXPORTS = [
     "bqsr_finalize_device", "bqsr_observe_stage", "bqsr_apply_stage", "bqsr_job_reset_async", "bqsr_job_result", "bqsr_copy_async",
     "bqsr_job_errors_export_async", "bqsr_job_errors_import_async", "bqsr_job_status_async", "bqsr_job_status_get",
     "bqsr_copy_dyn_async", "bqsr_compact_outputs_async", "bqsr_batch_exception_count_ptr",
+    "bqsr_batch_fold_stats",
     "bqsr_sort_order", "bqsr_sam_sort",  # include/adam_sam.h
     "bqsr_sam_flagstat", "bqsr_flagstat_arrow", "bqsr_flagstat_arrow_device",
     "bqsr_bgzf_inflate", "bqsr_sam_bam_form", "bqsr_sam_markdup_path",
@@ -83,6 +84,17 @@ class Dims(ctypes.Structure):
 class FinalStats(ctypes.Structure):
     _fields_ = [("average_reported_error", ctypes.c_double), ("global_error", ctypes.c_double),
                 ("global_obs", ctypes.c_int64), ("global_mm", ctypes.c_int64), ("n_groups", ctypes.c_int32)]
+
+
+class FoldStats(ctypes.Structure):
+    """bqsr_fold_stats: which paths a batch's last expectedMismatch fold took."""
+    _fields_ = [("n_tiles", ctypes.c_int64), ("stream_used", ctypes.c_int64), ("stream_cap", ctypes.c_int64),
+                ("lds_stream", ctypes.c_int64), ("n_blocks", ctypes.c_int32), ("reads_per_tile", ctypes.c_int32),
+                ("cand_blocks", ctypes.c_int32), ("nobase_blocks", ctypes.c_int32),
+                ("nobase_between", ctypes.c_int32), ("tileless_blocks", ctypes.c_int32),
+                ("longest_run", ctypes.c_int32), ("capped_blocks", ctypes.c_int32),
+                ("segs_total", ctypes.c_int32), ("segs_run", ctypes.c_int32), ("segs_event", ctypes.c_int32),
+                ("segs_global", ctypes.c_int32), ("segs_refused", ctypes.c_int32), ("lds_segs", ctypes.c_int32)]
 
 
 class DeviceReads(ctypes.Structure):
@@ -145,6 +157,7 @@ def lib():
             "bqsr_batch_upload_async": (ctypes.c_int, [vp, vp, vp]),
             "bqsr_batch_set_window": (ctypes.c_int, [vp, i32, i32]),
             "bqsr_batch_reads_per_tile": (i32, [vp]),
+            "bqsr_batch_fold_stats": (ctypes.c_int, [vp, ctypes.POINTER(FoldStats), vp]),
             "bqsr_table_words": (i64, [Dims]),
             "bqsr_table_create": (ctypes.c_int, [vp, Dims, vp, pp]),
             "bqsr_table_destroy": (None, [vp]),

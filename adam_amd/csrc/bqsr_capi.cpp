@@ -1297,6 +1297,77 @@ bqsr_status bqsr_batch_set_window(bqsr_batch* b, int32_t q_lo, int32_t rg_lo) {
 }
 int32_t bqsr_batch_reads_per_tile(const bqsr_batch* b) { return b ? b->rd.reads_per_tile : -1; }
 
+// which paths the batch's last fold took, from what its kernels left in device
+// memory (bqsr_fold.hip: the plan's blocks, bqsr_fold_segs' segment lists and
+// stream fill); host only
+bqsr_status bqsr_batch_fold_stats(bqsr_batch* b, bqsr_fold_stats* out, void* stream) {
+  if (!b || !out) return fail(BQSR_ERR_INVALID_ARG, "bqsr_batch_fold_stats: null argument");
+  if (!b->hq_valid) return fail(BQSR_ERR_INVALID_ARG, "bqsr_batch_fold_stats: no fold has run on this batch");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  hipStream_t s = S(stream);
+  HIP_TRY(hipStreamSynchronize(s));
+  const FoldParams& F = b->fold;
+  const int nb = b->n_blocks;
+  int32_t n_cand = 0;
+  uint32_t seg_used = 0;
+  unsigned long long stream_used = 0;
+  std::vector<FoldBlock> blk((size_t)nb);
+  HIP_TRY(hipMemcpy(&n_cand, F.n_cand, sizeof n_cand, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&seg_used, F.seg_used, sizeof seg_used, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&stream_used, F.stream_used, sizeof stream_used, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(blk.data(), F.blk, blk.size() * sizeof(FoldBlock), hipMemcpyDeviceToHost));
+  if (n_cand < 0 || n_cand > nb || (size_t)seg_used > (size_t)nb * kFoldMaxSegs)
+    return fail(BQSR_ERR_DEVICE, "bqsr_batch_fold_stats: the fold's counters are out of range");
+  std::vector<int32_t> nseg((size_t)n_cand), seg_base((size_t)n_cand);
+  std::vector<FoldSeg> seg((size_t)seg_used);
+  if (n_cand) {
+    HIP_TRY(hipMemcpy(nseg.data(), F.nseg, nseg.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(seg_base.data(), F.seg_base, seg_base.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  if (seg_used) HIP_TRY(hipMemcpy(seg.data(), F.seg, seg.size() * sizeof(FoldSeg), hipMemcpyDeviceToHost));
+  bqsr_fold_stats st{};
+  st.n_tiles = b->rd.n_tiles;
+  st.stream_used = (int64_t)stream_used;
+  st.stream_cap = F.stream_cap;
+  st.lds_stream = kChainLdsStream;
+  st.lds_segs = kChainLdsSegs;
+  st.n_blocks = nb;
+  st.reads_per_tile = b->rd.reads_per_tile;
+  int first_live = nb, last_live = -1;
+  for (int i = 0; i < nb; ++i) {
+    const FoldBlock& B = blk[(size_t)i];
+    const bool nobase = B.cidx < 0 && B.e == kFoldNoBase;
+    if (B.cidx >= 0) ++st.cand_blocks;
+    if (nobase) ++st.nobase_blocks;
+    else {
+      first_live = std::min(first_live, i);
+      last_live = i;
+      if (B.cidx < 0) st.longest_run = std::max(st.longest_run, -B.cidx);
+    }
+    if (b->rd.n_tiles * i / nb == b->rd.n_tiles * (i + 1) / nb) ++st.tileless_blocks;
+  }
+  for (int i = first_live + 1; i < last_live; ++i)
+    if (blk[(size_t)i].cidx < 0 && blk[(size_t)i].e == kFoldNoBase) ++st.nobase_between;
+  for (int c = 0; c < n_cand; ++c) {
+    const int32_t ns = nseg[(size_t)c], s0 = seg_base[(size_t)c];
+    if (ns < 0 || ns > kFoldMaxSegs || s0 < 0 || (int64_t)s0 + ns > (int64_t)seg_used)
+      return fail(BQSR_ERR_DEVICE, "bqsr_batch_fold_stats: a segment list is out of range");
+    if (ns == kFoldMaxSegs) ++st.capped_blocks;
+    st.segs_total += ns;
+    for (int32_t i = s0; i < s0 + ns; ++i) {
+      const FoldSeg& G = seg[(size_t)i];
+      if (G.kind == kSegRun) ++st.segs_run;
+      else if (G.kind == kSegEvent) ++st.segs_event;
+      else {
+        ++st.segs_global;
+        if (G.off < 0) ++st.segs_refused;
+      }
+    }
+  }
+  *out = st;
+  return ok();
+}
+
 // ---------------------------------------------------------------- table ----
 
 int64_t bqsr_table_words(bqsr_dims d) { return (d.n_rg < 1 || d.max_len < 1) ? -1 : table_words(d); }

@@ -377,6 +377,33 @@ bqsr_status bqsr_apply_result(bqsr_batch* b, int64_t* n_exceptions, void* stream
  * rg_lo, quals q_lo.. (chosen from the packed quals; settable for device batches). */
 bqsr_status bqsr_batch_set_window(bqsr_batch* b, int32_t q_lo, int32_t rg_lo);
 int32_t bqsr_batch_reads_per_tile(const bqsr_batch* b);
+/* Which paths the batch's last expectedMismatch fold took (DESIGN.md §"The
+ * expectedMismatch fold"; no reference counterpart: for tests).  Waits for
+ * `stream` and copies what the fold's kernels left in device memory: the
+ * blocks' classification, the candidate blocks' segment lists and the event
+ * stream's fill.  No kernel runs.  BQSR_ERR_INVALID_ARG before the batch's
+ * first fold. */
+typedef struct bqsr_fold_stats {
+  int64_t n_tiles;          /* read tiles of the batch                                              */
+  int64_t stream_used;      /* event-stream bytes asked for (64-B padded; may exceed stream_cap)    */
+  int64_t stream_cap;       /* event-stream capacity                                                */
+  int64_t lds_stream;       /* stream bytes the chain prefetches into LDS; beyond: scratch path     */
+  int32_t n_blocks;         /* fold blocks (one per CU)                                             */
+  int32_t reads_per_tile;
+  int32_t cand_blocks;      /* blocks that may hold an event: split into segments                   */
+  int32_t nobase_blocks;    /* blocks without a folded base                                         */
+  int32_t nobase_between;   /* of those, with a folded block somewhere before and somewhere after  */
+  int32_t tileless_blocks;  /* blocks whose tile range is empty (fewer tiles than blocks)           */
+  int32_t longest_run;      /* blocks in the longest merged run of event-free blocks                */
+  int32_t capped_blocks;    /* candidate blocks that filled all their segments (overflow segment)   */
+  int32_t segs_total;       /* segments of all candidate blocks                                     */
+  int32_t segs_run;         /*   tiles that stay in one binade: one integer addition                */
+  int32_t segs_event;       /*   tiles that may hold an event, quals in the stream                  */
+  int32_t segs_global;      /*   folded from the read columns: overflow segments and segs_refused   */
+  int32_t segs_refused;     /*   event segments that found no stream room                           */
+  int32_t lds_segs;         /* segments the chain prefetches into LDS; beyond: read from global     */
+} bqsr_fold_stats;
+bqsr_status bqsr_batch_fold_stats(bqsr_batch* b, bqsr_fold_stats* out, void* stream);
 /* base slots of the packed layout (sum over reads of max(Ls, Lq) rounded up to 16): the size of
  * apply's out_qual */
 int64_t bqsr_batch_slots(const bqsr_batch* b);
