@@ -25,7 +25,7 @@ STATUS_NAMES = ["OK", "NULL_RG", "MD_PARSE", "CIGAR_SHORT", "BAD_REVCOMP_BASE", 
 MPILEUP_STATUS_NAMES = ["UNSORTED", "REFERENCE_CONFLICT"]
 UNSORTED, REFERENCE_CONFLICT = 17, 18
 
-# every symbol include/adam_bqsr.h declares
+# every symbol include/adam_bqsr.h and include/adam_sam.h declare
 EXPORTS = [
     "bqsr_abi_version", "bqsr_last_error", "bqsr_last_error_read", "bqsr_status_name", "bqsr_context_create",
     "bqsr_context_destroy", "bqsr_context_tune", "bqsr_sites_create", "bqsr_sites_destroy", "bqsr_batch_create", "bqsr_batch_destroy",
@@ -104,6 +104,10 @@ class DeviceReads(ctypes.Structure):
                 ("slots_aligned", ctypes.c_int32)]
 
 
+# the types a module's sig table is written in
+vp, i32, i64, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+pp, i64p, dblp = ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(dbl)
+
 _lib = None
 _lock = threading.Lock()
 
@@ -127,8 +131,6 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        vp, i32, i64, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
-        pp = ctypes.POINTER(ctypes.c_void_p)
         sig = {
             "bqsr_abi_version": (ctypes.c_int, []),
             "bqsr_last_error": (ctypes.c_char_p, []),
@@ -200,15 +202,38 @@ def lib():
             "bqsr_job_status_async": (ctypes.c_int, [vp, vp, i32, vp]),
             "bqsr_job_status_get": (ctypes.c_int, [vp, i32, i32, ctypes.POINTER(dbl), ctypes.POINTER(i64)]),
         }
+        _lib = bind(L, sig)
+    return _lib
+
+
+def bind(L, sig):
+    """L with restype and argtypes set from `sig`, {name: (restype, argtypes)}:
+    what a module's ``_lib()`` returns.  L keeps the tables it was given (by
+    identity, and alive, so no other table can take a kept one's place): a
+    second call with one changes nothing."""
+    done = L.__dict__.setdefault("_sig_tables", {})
+    if id(sig) not in done:
         for name, (res, args) in sig.items():
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
-        _lib = L
-    return _lib
+        done[id(sig)] = sig
+    return L
 
 
 def check(status: int):
     if status != BQSR_OK:
         L = lib()
         raise BQSRError(status, L.bqsr_last_error().decode(), L.bqsr_last_error_read())
+
+
+def stage_times(fn, names, handle=None, array=False):
+    """{stage: ms} of a ``bqsr_*_kernel_times`` call `fn`, in the order of
+    `names` (the module's KERNELS).  `fn` takes `handle` first when one is
+    given, then one ``double*`` per stage or, with `array`, one to them all."""
+    v = (ctypes.c_double * len(names))()
+    lead = [] if handle is None else [handle]
+    at = ctypes.addressof(v)
+    out = [v] if array else [ctypes.cast(at + 8 * i, ctypes.POINTER(ctypes.c_double)) for i in range(len(names))]
+    check(fn(*(lead + out)))
+    return dict(zip(names, v))

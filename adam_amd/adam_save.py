@@ -28,7 +28,8 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from ._capi import check
+from . import _capi
+from ._capi import check, i32, i64, i64p, vp
 
 # adam.avdl:4-68, in order: (name, arrow type name)
 ADAM_FIELDS: List[Tuple[str, str]] = [
@@ -93,30 +94,18 @@ class AdamHost(ctypes.Structure):
                 ("int_valid", ctypes.c_void_p * 6), ("bools", ctypes.c_void_p * 11)]
 
 
-_bound = False
+_SIG = {
+    "bqsr_sam_adam_set_quals": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "bqsr_sam_adam_prepare": (ctypes.c_int, [vp, vp, i64, i64, vp, ctypes.POINTER(AdamSizes)]),
+    "bqsr_sam_adam_columns": (ctypes.c_int, [vp, vp, ctypes.POINTER(AdamHost), vp]),
+    "bqsr_sam_header_text": (ctypes.c_int, [vp, ctypes.c_char_p, i64, i64p]),
+    "bqsr_parquet_gzip": (ctypes.c_int, [vp, i64, ctypes.c_char_p, i32, ctypes.c_char_p, i32, i64p]),
+    "bqsr_gzip_bytes": (ctypes.c_int, [vp, i64, i32, i32, vp, i64, i64p]),
+}
 
 
 def _lib():
-    global _bound
-    from . import sam as S
-    L = S._lib()
-    if not _bound:
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        L.bqsr_sam_adam_set_quals.restype = ctypes.c_int
-        L.bqsr_sam_adam_set_quals.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp]
-        L.bqsr_sam_adam_prepare.restype = ctypes.c_int
-        L.bqsr_sam_adam_prepare.argtypes = [vp, vp, i64, i64, vp, ctypes.POINTER(AdamSizes)]
-        L.bqsr_sam_adam_columns.restype = ctypes.c_int
-        L.bqsr_sam_adam_columns.argtypes = [vp, vp, ctypes.POINTER(AdamHost), vp]
-        L.bqsr_sam_header_text.restype = ctypes.c_int
-        L.bqsr_sam_header_text.argtypes = [vp, ctypes.c_char_p, i64, ctypes.POINTER(i64)]
-        L.bqsr_parquet_gzip.restype = ctypes.c_int
-        L.bqsr_parquet_gzip.argtypes = [vp, i64, ctypes.c_char_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32,
-                                        ctypes.POINTER(i64)]
-        L.bqsr_gzip_bytes.restype = ctypes.c_int
-        L.bqsr_gzip_bytes.argtypes = [vp, i64, ctypes.c_int32, ctypes.c_int32, vp, i64, ctypes.POINTER(i64)]
-        _bound = True
-    return L
+    return _capi.bind(_capi.lib(), _SIG)
 
 
 def _iso8601_epoch_ms(v: str) -> Optional[int]:

@@ -63,7 +63,7 @@ import numpy as np
 
 from . import _capi, bqsr
 from . import reads2ref as R
-from ._capi import check
+from ._capi import check, dblp, i64, pp, vp
 from .adam_save import (BASES, PILEUP_DICT_COLS, PILEUP_FIELDS, PILEUP_STATS_COLS, RG_TAGS, AdamWriter, check_out,
                         header_info, pileup_schema)
 from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
@@ -111,39 +111,27 @@ class AggHost(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f, _, _ in _HOST]
 
 
-_bound = False
+KERNELS = ("keys", "sort", "scans", "emit")
+_SIG = {
+    "bqsr_pileup_agg_create": (ctypes.c_int, [vp, pp]),
+    "bqsr_pileup_agg_destroy": (None, [vp]),
+    "bqsr_pileup_agg_add_host": (ctypes.c_int, [vp, ctypes.POINTER(AggRows), vp]),
+    "bqsr_sam_pileup_agg_add": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, vp]),
+    "bqsr_arrow_pileup_agg_add": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, vp]),
+    "bqsr_pileup_agg_run": (ctypes.c_int, [vp, vp, ctypes.POINTER(AggSizes)]),
+    "bqsr_pileup_agg_fetch": (ctypes.c_int, [vp, ctypes.POINTER(AggHost), vp]),
+    "bqsr_pileup_agg_kernel_times": (ctypes.c_int, [dblp, dblp, dblp, dblp]),
+}
 
 
 def _lib():
-    global _bound
-    L = R._lib()
-    if not _bound:
-        vp, i64, dp = ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)
-        L.bqsr_pileup_agg_create.restype = ctypes.c_int
-        L.bqsr_pileup_agg_create.argtypes = [vp, ctypes.POINTER(vp)]
-        L.bqsr_pileup_agg_destroy.restype = None
-        L.bqsr_pileup_agg_destroy.argtypes = [vp]
-        L.bqsr_pileup_agg_add_host.restype = ctypes.c_int
-        L.bqsr_pileup_agg_add_host.argtypes = [vp, ctypes.POINTER(AggRows), vp]
-        for f in (L.bqsr_sam_pileup_agg_add, L.bqsr_arrow_pileup_agg_add):
-            f.restype = ctypes.c_int
-            f.argtypes = [vp, vp, vp, vp, vp, i64, vp]
-        L.bqsr_pileup_agg_run.restype = ctypes.c_int
-        L.bqsr_pileup_agg_run.argtypes = [vp, vp, ctypes.POINTER(AggSizes)]
-        L.bqsr_pileup_agg_fetch.restype = ctypes.c_int
-        L.bqsr_pileup_agg_fetch.argtypes = [vp, ctypes.POINTER(AggHost), vp]
-        L.bqsr_pileup_agg_kernel_times.restype = ctypes.c_int
-        L.bqsr_pileup_agg_kernel_times.argtypes = [dp, dp, dp, dp]
-        _bound = True
-    return L
+    return _capi.bind(_capi.lib(), _SIG)
 
 
 def kernel_times() -> Dict[str, float]:
     """device-event times (ms) of this thread's last run: keys, sort, scans,
     emit (measurement only)"""
-    v = [ctypes.c_double() for _ in range(4)]
-    _lib().bqsr_pileup_agg_kernel_times(*[ctypes.byref(x) for x in v])
-    return dict(zip(("keys", "sort", "scans", "emit"), (x.value for x in v)))
+    return _capi.stage_times(_lib().bqsr_pileup_agg_kernel_times, KERNELS)
 
 
 class Aggregation:
@@ -507,7 +495,7 @@ def aggregate_pileups(inp: str, out: str, compression: str = "gzip", part_rows: 
     part_rows, part_reads = max(1, int(part_rows)), max(1, int(part_reads))
     stats: Dict[str, object] = {}
     U = Units()
-    L = _lib()
+    L = R._lib()
     with Aggregation(ctx) as agg:
         if is_parquet(inp):
             import pyarrow.parquet as pq

@@ -37,7 +37,7 @@ from collections import Counter, defaultdict
 from typing import Dict, List, Optional, Tuple
 
 from . import _capi
-from ._capi import check
+from ._capi import check, dblp, i32, pp, vp
 
 CATS = ("unpairedPrimary", "pairedFirstPrimary", "pairedSecondPrimary", "unpairedSecondary", "pairedFirstSecondary",
         "pairedSecondSecondary", "unmapped")
@@ -690,38 +690,26 @@ class _Side(ctypes.Structure):
                 ("n_chunks", ctypes.c_int32)]
 
 
-_bound = False
+KERNELS = ("join", "scalar", "baseqs")
+_SIG = {
+    "bqsr_compare_create": (ctypes.c_int, [vp, ctypes.POINTER(_Options), pp]),
+    "bqsr_compare_destroy": (None, [vp]),
+    "bqsr_compare_sides": (ctypes.c_int, [vp, ctypes.POINTER(_Side), ctypes.POINTER(_Side), ctypes.POINTER(_Term), i32,
+                                          vp, ctypes.POINTER(_Result)]),
+    "bqsr_compare_values": (ctypes.c_int, [vp, i32, vp, vp]),
+    "bqsr_compare_baseqs": (ctypes.c_int, [vp, vp]),
+    "bqsr_compare_rows": (ctypes.c_int, [vp, vp, vp]),
+    "bqsr_compare_kernel_times": (ctypes.c_int, [vp, dblp, dblp, dblp]),
+}
 
 
 def _lib():
-    global _bound
-    L = _capi.lib()
-    if not _bound:
-        vp, i64p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)
-        L.bqsr_compare_create.restype = ctypes.c_int
-        L.bqsr_compare_create.argtypes = [vp, ctypes.POINTER(_Options), ctypes.POINTER(vp)]
-        L.bqsr_compare_destroy.restype = None
-        L.bqsr_compare_destroy.argtypes = [vp]
-        L.bqsr_compare_sides.restype = ctypes.c_int
-        L.bqsr_compare_sides.argtypes = [vp, ctypes.POINTER(_Side), ctypes.POINTER(_Side), ctypes.POINTER(_Term),
-                                         ctypes.c_int32, vp, ctypes.POINTER(_Result)]
-        L.bqsr_compare_values.restype = ctypes.c_int
-        L.bqsr_compare_values.argtypes = [vp, ctypes.c_int32, vp, vp]
-        L.bqsr_compare_baseqs.restype = ctypes.c_int
-        L.bqsr_compare_baseqs.argtypes = [vp, vp]
-        L.bqsr_compare_rows.restype = ctypes.c_int
-        L.bqsr_compare_rows.argtypes = [vp, vp, vp]
-        L.bqsr_compare_kernel_times.restype = ctypes.c_int
-        L.bqsr_compare_kernel_times.argtypes = [vp] + [ctypes.POINTER(ctypes.c_double)] * 3
-        _bound = True
-    return L
+    return _capi.bind(_capi.lib(), _SIG)
 
 
 def _kernel_times(h) -> Tuple[float, float, float]:
     """(join, scalar, baseqs + UTF-8 decode) kernel milliseconds of the handle's last run (measurement only)"""
-    a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-    _lib().bqsr_compare_kernel_times(h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
-    return a.value, b.value, c.value
+    return tuple(_capi.stage_times(_lib().bqsr_compare_kernel_times, KERNELS, handle=h).values())
 
 
 def _is_utf8(encoding: str) -> int:

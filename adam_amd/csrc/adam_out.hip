@@ -560,8 +560,7 @@ bqsr_status bqsr_sam_adam_prepare(bqsr_context* ctx, bqsr_sam* s, int64_t r0, in
   adam_quals(P, A, s);
   HIP_TRY(hipMemsetAsync(A.err, 0xFF, 8, st));
   const unsigned g = sam_grid(n, 256, ctx->n_cu * 8);
-  if (n > 0) hipLaunchKernelGGL(adamk::adam_len, dim3(g), dim3(256), 0, st, P);
-  HIP_TRY(hipGetLastError());
+  if (n > 0) JOB_TRY(launch(adamk::adam_len, g, 256, st, P));
   bqsr_status rs;
   for (int c = 0; c < adamk::kStr; ++c)
     if ((rs = sam_scan(A.len + (size_t)c * n, n, A.off + (size_t)c * (n + 1), A.part, st)) != BQSR_OK) return rs;
@@ -614,11 +613,10 @@ bqsr_status bqsr_sam_adam_columns(bqsr_context* ctx, bqsr_sam* s, const bqsr_ada
   P.W = A.W;
   adam_quals(P, A, s);
   if (n > 0) {
-    hipLaunchKernelGGL(adamk::adam_write, dim3(sam_grid(n, 256, ctx->n_cu * 8)), dim3(256), 0, st, P);
+    JOB_TRY(launch(adamk::adam_write, sam_grid(n, 256, ctx->n_cu * 8), 256, st, P));
   } else {
-    hipLaunchKernelGGL(adamk::adam_empty_offsets, dim3(1), dim3(64), 0, st, A.soff, n);
+    JOB_TRY(launch(adamk::adam_empty_offsets, 1, 64, st, A.soff, n));
   }
-  HIP_TRY(hipGetLastError());
   const size_t N1 = (size_t)n + 1, WB = (size_t)A.W * 8;
   auto cp = [&](void* d, const void* src, size_t bytes) -> hipError_t {
     if (!d || !bytes) return hipSuccess;

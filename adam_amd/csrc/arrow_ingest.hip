@@ -429,9 +429,7 @@ bqsr_status bqsr_arrow_load(bqsr_context* ctx, const bqsr_arrow_chunk* chunks, i
     D.lib = lib;
     Cols O{{A->beg[0], A->beg[1], A->beg[2], A->beg[3], A->beg[4]}, A->flags, A->rg, A->ref, A->start,
            A->name_valid, A->sq, A->lib};
-    hipLaunchKernelGGL(arrow_chunk_cols, dim3(sam_grid(m, kThreads, ctx->n_cu * 16)), dim3(kThreads), 0, s, D, O,
-                       (int)(r0 + m == n));
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(arrow_chunk_cols, sam_grid(m, kThreads, ctx->n_cu * 16), kThreads, s, D, O, (int)(r0 + m == n)));
     // the chunk's staging buffers are freed after its kernel ran
     HIP_TRY(hipStreamSynchronize(s));
     for (void* p : tmp) (void)hipFree(p);
@@ -464,7 +462,7 @@ bqsr_status bqsr_arrow_load(bqsr_context* ctx, const bqsr_arrow_chunk* chunks, i
   LP.bad_cigar = bad;
   LP.max_rg = max_rg;
   const unsigned g = sam_grid(n, kThreads, ctx->n_cu * 16);
-  if (n) hipLaunchKernelGGL(arrow_lens, dim3(g), dim3(kThreads), 0, s, LP);
+  if (n) JOB_TRY(launch(arrow_lens, g, kThreads, s, LP));
   for (int k = 0; k < kStr; ++k)
     if ((st = sam_scan(len[k], n, off[k], part, s)) != BQSR_OK) return st;
   uint64_t totals[kStr];
@@ -501,8 +499,7 @@ bqsr_status bqsr_arrow_load(bqsr_context* ctx, const bqsr_arrow_chunk* chunks, i
   DP.qual = A->qual;
   DP.md = A->md;
   DP.cig = A->cig;
-  if (n) hipLaunchKernelGGL(arrow_decode, dim3(g), dim3(kThreads), 0, s, DP);
-  HIP_TRY(hipGetLastError());
+  if (n) JOB_TRY(launch(arrow_decode, g, kThreads, s, DP));
   HIP_TRY(hipStreamSynchronize(s));
   *out = A.release();
   return ok();
@@ -573,7 +570,7 @@ bqsr_status bqsr_arrow_qual_prepare(bqsr_context* ctx, bqsr_arrow* a, const bqsr
   P.len = len;
   P.off = off;
   const unsigned g = sam_grid(n, kThreads, ctx->n_cu * 16);
-  if (n) hipLaunchKernelGGL(arrow_qual_len, dim3(g), dim3(kThreads), 0, s, P);
+  if (n) JOB_TRY(launch(arrow_qual_len, g, kThreads, s, P));
   if ((st = sam_scan(len, n, off, part, s)) != BQSR_OK) return st;
   uint64_t total = 0;
   if (n) HIP_TRY(hipMemcpyAsync(&total, off + n, 8, hipMemcpyDeviceToHost, s));
@@ -587,8 +584,7 @@ bqsr_status bqsr_arrow_qual_prepare(bqsr_context* ctx, bqsr_arrow* a, const bqsr
   P.out = a->q_out;
   P.off32 = a->q_off;
   P.valid = a->q_valid;
-  if (n) hipLaunchKernelGGL(arrow_qual_write, dim3(g), dim3(kThreads), 0, s, P);
-  HIP_TRY(hipGetLastError());
+  if (n) JOB_TRY(launch(arrow_qual_write, g, kThreads, s, P));
   HIP_TRY(hipStreamSynchronize(s));
   a->q_bytes = (int64_t)total;
   if (n_bytes) *n_bytes = (int64_t)total;
@@ -633,9 +629,7 @@ bqsr_status bqsr_arrow_mark_duplicates(bqsr_context* ctx, bqsr_arrow* a, int64_t
     hipStream_t s = hipStreamPerThread;
     const unsigned g = sam_grid(a->n, mdupd::kThreads, ctx->n_cu * 16);
     HIP_TRY(hipMemsetAsync(d->cnt, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(mdupd::mdup_set_apply, dim3(g), dim3(mdupd::kThreads), 0, s, (const uint32_t*)d->bits,
-                       (int64_t)0, a->n, a->flags, d->cnt);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(mdupd::mdup_set_apply, g, mdupd::kThreads, s, d->bits, (int64_t)0, a->n, a->flags, d->cnt));
     HIP_TRY(hipStreamSynchronize(s));
   }
   if (n_duplicates) *n_duplicates = nd;
@@ -662,9 +656,8 @@ bqsr_status bqsr_arrow_flag_bitmap(const bqsr_arrow* a, uint32_t flag, uint8_t* 
   uint8_t* d = nullptr;
   const size_t nb = (size_t)(a->n + 7) / 8;
   HIP_TRY(hipMalloc((void**)&d, nb + 8));
-  hipLaunchKernelGGL(arwk::arrow_flag_bits, dim3(sam_grid(a->n, arwk::kThreads, a->ctx->n_cu * 16)),
-                     dim3(arwk::kThreads), 0, s, (const uint32_t*)a->flags, a->n, flag, d);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_err(arwk::arrow_flag_bits, sam_grid(a->n, arwk::kThreads, a->ctx->n_cu * 16), arwk::kThreads, s,
+                            a->flags, a->n, flag, d);
   if (e == hipSuccess) e = hipMemcpyAsync(bitmap, d, nb, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   (void)hipFree(d);

@@ -558,20 +558,15 @@ bqsr_status bgzf_inflate_runs(bqsr_context* ctx, const uint8_t* data, int64_t n,
       for (b1 = b0 + 1; b1 < nb && hb[(size_t)b1].dst + hb[(size_t)b1].isize - hb[(size_t)b0].dst <= kTokRun;) ++b1;
       const int64_t nr_b = b1 - b0, tok0 = hb[(size_t)b0].dst;
       if (nr_b <= (int64_t)ctx->n_cu * 2 * bgzfk::kInfThreads)  // (all in flight at once)
-        hipLaunchKernelGGL(bgzfk::bgzf_tokens_kernel<bgzfk::kInfThreads>,
-                           dim3((unsigned)((nr_b + bgzfk::kInfThreads - 1) / bgzfk::kInfThreads)), dim3(bgzfk::kInfThreads),
-                           0, s, (const uint8_t*)d_comp, (const bgzfk::Blk*)d_blk + b0, nr_b, d_tok, tok0, d_ntok + b0,
-                           d_status + b0);
+        JOB_TRY(launch(bgzfk::bgzf_tokens_kernel<bgzfk::kInfThreads>,
+                       (unsigned)((nr_b + bgzfk::kInfThreads - 1) / bgzfk::kInfThreads), bgzfk::kInfThreads, s, d_comp,
+                       (const bgzfk::Blk*)d_blk + b0, nr_b, d_tok, tok0, d_ntok + b0, d_status + b0));
       else
-        hipLaunchKernelGGL(bgzfk::bgzf_tokens_kernel<bgzfk::kInfThreadsDeep>,
-                           dim3((unsigned)((nr_b + bgzfk::kInfThreadsDeep - 1) / bgzfk::kInfThreadsDeep)),
-                           dim3(bgzfk::kInfThreadsDeep), 0, s, (const uint8_t*)d_comp, (const bgzfk::Blk*)d_blk + b0, nr_b,
-                           d_tok, tok0, d_ntok + b0, d_status + b0);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(bgzfk::bgzf_resolve_kernel, dim3((unsigned)nr_b), dim3(bgzfk::kResThreads), 0, s,
-                         (const bgzfk::Blk*)d_blk + b0, (const uint32_t*)d_tok, tok0, (const int32_t*)d_ntok + b0, d_raw,
-                         d_status + b0);
-      HIP_TRY(hipGetLastError());
+        JOB_TRY(launch(bgzfk::bgzf_tokens_kernel<bgzfk::kInfThreadsDeep>,
+                       (unsigned)((nr_b + bgzfk::kInfThreadsDeep - 1) / bgzfk::kInfThreadsDeep), bgzfk::kInfThreadsDeep,
+                       s, d_comp, (const bgzfk::Blk*)d_blk + b0, nr_b, d_tok, tok0, d_ntok + b0, d_status + b0));
+      JOB_TRY(launch(bgzfk::bgzf_resolve_kernel, (unsigned)nr_b, bgzfk::kResThreads, s, (const bgzfk::Blk*)d_blk + b0,
+                     d_tok, tok0, (const int32_t*)d_ntok + b0, d_raw, d_status + b0));
     }
   }
   hs.assign((size_t)std::max<int64_t>(1, nb), 0);
@@ -630,10 +625,9 @@ bqsr_status bam_inflate_device(bqsr_context* ctx, const uint8_t* data, int64_t n
   HIP_TRY(hipMemsetAsync(C.bad, 0, 4, s));
   const unsigned gb = (unsigned)std::max<int64_t>(1, (nb + 63) / 64);
   if (nb > 0) {
-    hipLaunchKernelGGL(bgzfk::bam_chain_guess, dim3(gb), dim3(64), 0, s, C);
-    hipLaunchKernelGGL(bgzfk::bam_chain_check, dim3(gb), dim3(64), 0, s, C);
+    JOB_TRY(launch(bgzfk::bam_chain_guess, gb, 64, s, C));
+    JOB_TRY(launch(bgzfk::bam_chain_check, gb, 64, s, C));
   }
-  HIP_TRY(hipGetLastError());
   if ((st = sam_scan(C.count, nb, base, part, s)) != BQSR_OK) return st;
   int32_t bad = 0;
   uint64_t total = 0;
@@ -646,8 +640,7 @@ bqsr_status bam_inflate_device(bqsr_context* ctx, const uint8_t* data, int64_t n
   if ((st = sam_alloc(tmp, &rec, (size_t)nr + 1)) != BQSR_OK) return st;
   C.base = base;
   C.rec = rec;
-  if (nb > 0) hipLaunchKernelGGL(bgzfk::bam_chain_write, dim3(gb), dim3(64), 0, s, C);
-  HIP_TRY(hipGetLastError());
+  if (nb > 0) JOB_TRY(launch(bgzfk::bam_chain_write, gb, 64, s, C));
   const uint64_t end = (uint64_t)(m - BH.body);
   HIP_TRY(hipMemcpyAsync(rec + nr, &end, 8, hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -752,8 +745,7 @@ bqsr_status bqsr_bam_parse(bqsr_context* ctx, const uint8_t* data, int64_t n, vo
   P.len = len;
   P.off = off;
   const unsigned g = sam_grid(nr, 256, ctx->n_cu * 16);
-  if (nr > 0) hipLaunchKernelGGL(bamk::bam_lines_len, dim3(g), dim3(256), 0, s, P);
-  HIP_TRY(hipGetLastError());
+  if (nr > 0) JOB_TRY(launch(bamk::bam_lines_len, g, 256, s, P));
   if ((st = sam_scan(len, nr, off, part, s)) != BQSR_OK) return st;
   unsigned long long e_word = ~0ull;
   uint64_t body_bytes = 0;
@@ -773,10 +765,7 @@ bqsr_status bqsr_bam_parse(bqsr_context* ctx, const uint8_t* data, int64_t n, vo
   hipError_t e = hipMemsetAsync(d_text + n_text, 0, 64, s);
   if (e == hipSuccess && H.body > 0) e = hipMemcpyAsync(d_text, hdr.data(), hdr.size(), hipMemcpyHostToDevice, s);
   P.out = d_text;
-  if (e == hipSuccess && nr > 0) {
-    hipLaunchKernelGGL(bamk::bam_lines_write, dim3(g), dim3(256), 0, s, P);
-    e = hipGetLastError();
-  }
+  if (e == hipSuccess && nr > 0) e = launch_err(bamk::bam_lines_write, g, 256, s, P);
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the header copy reads `hdr`)
   if (e != hipSuccess) {
     (void)hipFree(d_text);

@@ -429,7 +429,7 @@ struct BamBufs {
   uint64_t* patch = nullptr;
   uint8_t* blob = nullptr;
   int64_t cap_patch = 0, cap_blob = 0, n_float = 0, blob_bytes = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  StageClock<4> clock;
   bool prepared = false;
   const void *text = nullptr, *spans = nullptr;  // what pass 1 measured: pass 2 runs over the same text only
   void free_rows() {
@@ -442,14 +442,15 @@ struct BamBufs {
     free_rows();
     for (void* p : {(void*)err, (void*)cnt, (void*)out, (void*)patch, (void*)blob})
       if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
   }
 };
 
 namespace {
 
-thread_local double g_bam_ms[2] = {0.0, 0.0};
+// pass 1 and pass 2 of the calling thread's last prepare / records or members call, and the clock's marks
+enum { BAM_LEN, BAM_WRITE, BAM_STAGES };
+enum { BAM_LEN_0, BAM_LEN_1, BAM_WRITE_0, BAM_WRITE_1 };
+thread_local double g_bam_ms[BAM_STAGES] = {0.0, 0.0};
 
 const char* kBamErrors[bamo::kBamCodes] = {
     "ok",
@@ -566,6 +567,21 @@ int64_t bgzf_member(const DeflateOut& D, void* comp, int level, const uint8_t* i
   return size;
 }
 
+// Pass 2 over the prepared range, between its two marks, for both sinks: bqsr_sam_bam_records here and
+// bqsr_sam_bam_members (bgzf_deflate.hip).  A sink zeroes the stage with bam_write_begin, runs the pass and,
+// after its synchronize, reads the time with bam_write_end.
+void bam_write_begin() { g_bam_ms[BAM_WRITE] = 0.0; }
+
+bqsr_status bam_write_pass(bqsr_context* ctx, const bqsr_sam* s, BamBufs& A, hipStream_t st) {
+  const bamo::BamParams P = bam_params(s, A);
+  HIP_TRY(A.clock.mark(BAM_WRITE_0, st));
+  if (A.n > 0) JOB_TRY(launch(bamo::bam_write, sam_grid(A.n, 256, ctx->n_cu * 8), 256, st, P));
+  HIP_TRY(A.clock.mark(BAM_WRITE_1, st));
+  return BQSR_OK;
+}
+
+void bam_write_end(BamBufs& A) { A.clock.add(g_bam_ms[BAM_WRITE], BAM_WRITE_0, BAM_WRITE_1); }
+
 }  // namespace
 
 extern "C" {
@@ -579,9 +595,7 @@ bqsr_status bqsr_sam_bam_prepare(bqsr_context* ctx, bqsr_sam* s, int64_t r0, int
   if (!s->bam) s->bam = std::make_shared<BamBufs>();
   BamBufs& A = *(BamBufs*)s->bam.get();
   A.prepared = false;
-  g_bam_ms[0] = g_bam_ms[1] = 0.0;
-  for (int k = 0; k < 4; ++k)
-    if (!A.ev[k]) HIP_TRY(hipEventCreate(&A.ev[k]));
+  g_bam_ms[BAM_LEN] = g_bam_ms[BAM_WRITE] = 0.0;
   if (A.cap_n < n) {  // per-record buffers, kept across calls
     A.free_rows();
     const size_t N = (size_t)n + 1;
@@ -601,10 +615,9 @@ bqsr_status bqsr_sam_bam_prepare(bqsr_context* ctx, bqsr_sam* s, int64_t r0, int
   bamo::BamParams P = bam_params(s, A);
   HIP_TRY(hipMemsetAsync(A.err, 0xFF, 8, st));
   HIP_TRY(hipMemsetAsync(A.cnt, 0, 4 * 8, st));
-  HIP_TRY(hipEventRecord(A.ev[0], st));
-  if (n > 0) hipLaunchKernelGGL(bamo::bam_len, dim3(sam_grid(n, 256, ctx->n_cu * 8)), dim3(256), 0, st, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[1], st));
+  HIP_TRY(A.clock.mark(BAM_LEN_0, st));
+  if (n > 0) JOB_TRY(launch(bamo::bam_len, sam_grid(n, 256, ctx->n_cu * 8), 256, st, P));
+  HIP_TRY(A.clock.mark(BAM_LEN_1, st));
   bqsr_status rs = sam_scan(A.len, n, A.off, A.part, st);
   if (rs != BQSR_OK) return rs;
   unsigned long long ew = ~0ull, cnt[2] = {0, 0};
@@ -613,8 +626,7 @@ bqsr_status bqsr_sam_bam_prepare(bqsr_context* ctx, bqsr_sam* s, int64_t r0, int
   HIP_TRY(hipMemcpyAsync(cnt, A.cnt, 16, hipMemcpyDeviceToHost, st));
   if (n > 0) HIP_TRY(hipMemcpyAsync(&total, A.off + n, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, A.ev[0], A.ev[1]) == hipSuccess) g_bam_ms[0] = ms;
+  A.clock.add(g_bam_ms[BAM_LEN], BAM_LEN_0, BAM_LEN_1);
   if (ew != ~0ull) {
     const uint32_t code = (uint32_t)(ew & 0xFF);
     const int64_t read = r0 + (int64_t)(ew >> 8);
@@ -659,12 +671,8 @@ bqsr_status bqsr_sam_bam_records(bqsr_context* ctx, bqsr_sam* s, uint8_t* dst, v
   if (A.total > 0 && !dst) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_bam_records: no destination");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = S(stream);
-  g_bam_ms[1] = 0.0;
-  const bamo::BamParams P = bam_params(s, A);
-  HIP_TRY(hipEventRecord(A.ev[2], st));
-  if (A.n > 0) hipLaunchKernelGGL(bamo::bam_write, dim3(sam_grid(A.n, 256, ctx->n_cu * 8)), dim3(256), 0, st, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[3], st));
+  bam_write_begin();
+  JOB_TRY(bam_write_pass(ctx, s, A, st));
   std::vector<uint64_t> patch((size_t)A.n_float * 2);
   std::vector<char> blob((size_t)A.blob_bytes + 1, 0);
   if (A.total > 0) HIP_TRY(hipMemcpyAsync(dst, A.out, (size_t)A.total, hipMemcpyDeviceToHost, st));
@@ -673,8 +681,7 @@ bqsr_status bqsr_sam_bam_records(bqsr_context* ctx, bqsr_sam* s, uint8_t* dst, v
     HIP_TRY(hipMemcpyAsync(blob.data(), A.blob, (size_t)A.blob_bytes, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, A.ev[2], A.ev[3]) == hipSuccess) g_bam_ms[1] = ms;
+  bam_write_end(A);
   // the float slots: strtof of the text pass 2 set aside (correctly rounded, as the C library does it)
   for (int64_t k = 0; k < A.n_float; ++k) {
     const uint64_t at = patch[2 * (size_t)k], bo = patch[2 * (size_t)k + 1];
@@ -778,8 +785,8 @@ bqsr_status bqsr_bgzf_compress(const uint8_t* in, int64_t n, int32_t level, uint
 }
 
 bqsr_status bqsr_bam_kernel_times(double* len_ms, double* write_ms) {
-  if (len_ms) *len_ms = g_bam_ms[0];
-  if (write_ms) *write_ms = g_bam_ms[1];
+  if (len_ms) *len_ms = g_bam_ms[BAM_LEN];
+  if (write_ms) *write_ms = g_bam_ms[BAM_WRITE];
   return ok();
 }
 

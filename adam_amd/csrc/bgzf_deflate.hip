@@ -605,7 +605,10 @@ extern "C" __global__ void bam_float_scatter(uint8_t* out, int64_t total, const 
 
 namespace {
 
-thread_local double g_deflate_ms[2] = {0.0, 0.0};
+// the member kernel and the pack kernel of the calling thread's last device deflate, and the clock's marks
+enum { DEFLATE_MEMBERS, DEFLATE_PACK, DEFLATE_STAGES };
+enum { DEFLATE_MEMBERS_0, DEFLATE_MEMBERS_1, DEFLATE_PACK_0, DEFLATE_PACK_1 };
+thread_local double g_deflate_ms[DEFLATE_STAGES] = {0.0, 0.0};
 
 // d_in[0, n) (device memory, 4-byte aligned, readable to n rounded up to 4)
 // deflated into members, packed: *d_out (kept in tmp), *total bytes, *nm members
@@ -615,7 +618,7 @@ bqsr_status bgzf_deflate_device(bqsr_context* ctx, const uint8_t* d_in, int64_t 
   *nm_out = nm;
   *total = 0;
   *d_out = nullptr;
-  g_deflate_ms[0] = g_deflate_ms[1] = 0.0;
+  g_deflate_ms[DEFLATE_MEMBERS] = g_deflate_ms[DEFLATE_PACK] = 0.0;
   if (nm == 0) return BQSR_OK;
   const unsigned grid = (unsigned)std::min<int64_t>(nm, std::max<int64_t>(1, (int64_t)ctx->n_cu));
   bqsr_status st;
@@ -627,19 +630,10 @@ bqsr_status bgzf_deflate_device(bqsr_context* ctx, const uint8_t* d_in, int64_t 
       (st = sam_alloc(tmp, &sizes, (size_t)nm + 1)) != BQSR_OK || (st = sam_alloc(tmp, &off, (size_t)nm + 1)) != BQSR_OK ||
       (st = sam_alloc(tmp, &part, (size_t)(nm / samk::kScanChunk + 2))) != BQSR_OK)
     return st;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct Ev {
-    hipEvent_t* e;
-    ~Ev() {
-      for (int k = 0; k < 4; ++k)
-        if (e[k]) (void)hipEventDestroy(e[k]);
-    }
-  } free_ev{ev};
-  for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreate(&ev[k]));
-  HIP_TRY(hipEventRecord(ev[0], s));
-  hipLaunchKernelGGL(dflk::bgzf_deflate_kernel, dim3(grid), dim3(dflk::kThreads), 0, s, d_in, n, nm, tok, slots, sizes);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev[1], s));
+  StageClock<4> clock;
+  HIP_TRY(clock.mark(DEFLATE_MEMBERS_0, s));
+  JOB_TRY(launch(dflk::bgzf_deflate_kernel, grid, dflk::kThreads, s, d_in, n, nm, tok, slots, sizes));
+  HIP_TRY(clock.mark(DEFLATE_MEMBERS_1, s));
   if ((st = sam_scan(sizes, nm, off, part, s)) != BQSR_OK) return st;
   uint64_t tot = 0;
   HIP_TRY(hipMemcpyAsync(&tot, off + nm, 8, hipMemcpyDeviceToHost, s));
@@ -647,15 +641,13 @@ bqsr_status bgzf_deflate_device(bqsr_context* ctx, const uint8_t* d_in, int64_t 
   if (tot > (uint64_t)nm * dflk::kSlot) return fail(BQSR_ERR_DEVICE, "bgzf deflate: member sizes out of range");
   uint8_t* packed;
   if ((st = sam_alloc(tmp, &packed, (size_t)tot + 64)) != BQSR_OK) return st;
-  HIP_TRY(hipEventRecord(ev[2], s));
-  hipLaunchKernelGGL(dflk::bgzf_pack_kernel, dim3((unsigned)std::min<int64_t>(nm, (int64_t)ctx->n_cu * 8)), dim3(256), 0, s,
-                     (const uint8_t*)slots, (const uint64_t*)sizes, (const uint64_t*)off, nm, packed);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev[3], s));
+  HIP_TRY(clock.mark(DEFLATE_PACK_0, s));
+  JOB_TRY(launch(dflk::bgzf_pack_kernel, (unsigned)std::min<int64_t>(nm, (int64_t)ctx->n_cu * 8), 256, s, slots, sizes,
+                 off, nm, packed));
+  HIP_TRY(clock.mark(DEFLATE_PACK_1, s));
   HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) g_deflate_ms[0] = ms;
-  if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) g_deflate_ms[1] = ms;
+  clock.add(g_deflate_ms[DEFLATE_MEMBERS], DEFLATE_MEMBERS_0, DEFLATE_MEMBERS_1);
+  clock.add(g_deflate_ms[DEFLATE_PACK], DEFLATE_PACK_0, DEFLATE_PACK_1);
   *d_out = packed;
   *total = (int64_t)tot;
   return BQSR_OK;
@@ -735,14 +727,10 @@ bqsr_status bqsr_sam_bam_members(bqsr_context* ctx, bqsr_sam* s, void* stream, u
   *out_len = 0;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = S(stream);
-  g_bam_ms[1] = 0.0;
-  g_deflate_ms[0] = g_deflate_ms[1] = 0.0;
+  bam_write_begin();
+  g_deflate_ms[DEFLATE_MEMBERS] = g_deflate_ms[DEFLATE_PACK] = 0.0;
   if (A.total == 0) return ok();
-  const bamo::BamParams P = bam_params(s, A);
-  HIP_TRY(hipEventRecord(A.ev[2], st));
-  if (A.n > 0) hipLaunchKernelGGL(bamo::bam_write, dim3(sam_grid(A.n, 256, ctx->n_cu * 8)), dim3(256), 0, st, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[3], st));
+  JOB_TRY(bam_write_pass(ctx, s, A, st));
   std::vector<void*> tmp;
   struct Free {
     std::vector<void*>& v;
@@ -768,16 +756,14 @@ bqsr_status bqsr_sam_bam_members(bqsr_context* ctx, bqsr_sam* s, void* stream, u
     }
     uint32_t* d_val;
     if ((rs = sam_upload(tmp, &d_val, val, st)) != BQSR_OK) return rs;
-    hipLaunchKernelGGL(dflk::bam_float_scatter, dim3(sam_grid(A.n_float, 256, ctx->n_cu * 8)), dim3(256), 0, st, A.out,
-                       A.total, (const uint64_t*)A.patch, (const uint32_t*)d_val, A.n_float);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(dflk::bam_float_scatter, sam_grid(A.n_float, 256, ctx->n_cu * 8), 256, st, A.out, A.total, A.patch,
+                   d_val, A.n_float));
     HIP_TRY(hipStreamSynchronize(st));  // (val is read by the copy)
   }
   uint8_t* d_out;
   int64_t total = 0, nm = 0;
   if ((rs = bgzf_deflate_device(ctx, A.out, A.total, st, tmp, &d_out, &total, &nm)) != BQSR_OK) return rs;
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, A.ev[2], A.ev[3]) == hipSuccess) g_bam_ms[1] = ms;
+  bam_write_end(A);
   *out_len = total;
   if (total > cap) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_bam_members: the output does not fit (see *out_len)");
   if (total > 0) HIP_TRY(hipMemcpy(dst, d_out, (size_t)total, hipMemcpyDeviceToHost));
@@ -794,8 +780,8 @@ bqsr_status bqsr_deflate_code_lengths(const uint32_t* freq, int32_t n_syms, int3
 }
 
 bqsr_status bqsr_bgzf_deflate_times(double* deflate_ms, double* pack_ms) {
-  if (deflate_ms) *deflate_ms = g_deflate_ms[0];
-  if (pack_ms) *pack_ms = g_deflate_ms[1];
+  if (deflate_ms) *deflate_ms = g_deflate_ms[DEFLATE_MEMBERS];
+  if (pack_ms) *pack_ms = g_deflate_ms[DEFLATE_PACK];
   return ok();
 }
 

@@ -662,8 +662,12 @@ struct bqsr_compare {
   uint32_t *row1 = nullptr, *row2 = nullptr;
   int64_t n_pos = 0, n_mapq = 0, n_rows = 0;
   bool ran = false;
-  hipEvent_t ev[10] = {};  // join, scalar, baseqs windows; [6..9] the two sides' UTF-8 decode passes
-  double ms[3] = {0.0, 0.0, 0.0};  // the last run's join, scalar and baseqs (+ decode) kernels (measurement only)
+  // the last run's join, scalar and baseqs (+ UTF-8 decode) kernels (measurement only), and the clock's marks:
+  // a begin and an end per stage, then per side's decode pass
+  enum { JOIN, SCALAR, BASEQS, STAGES };
+  enum { JOIN_0, JOIN_1, SCALAR_0, SCALAR_1, BASEQS_0, BASEQS_1, DECODE1_0, DECODE1_1, DECODE2_0, DECODE2_1, MARKS };
+  StageClock<MARKS> clock;
+  double ms[STAGES] = {0.0, 0.0, 0.0};
   bool decoded[2] = {false, false};
   void release() {
     for (void* p : keep) (void)hipFree(p);
@@ -676,8 +680,6 @@ struct bqsr_compare {
   }
   ~bqsr_compare() {
     release();
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
   }
 };
 
@@ -737,11 +739,10 @@ bqsr_status bqsr_compare_create(bqsr_context* ctx, const bqsr_compare_options* o
   auto* c = new bqsr_compare();
   c->ctx = ctx;
   c->opt = o;
-  for (hipEvent_t& ev : c->ev)
-    if (hipEventCreate(&ev) != hipSuccess) {
-      delete c;
-      return fail(BQSR_ERR_DEVICE, "bqsr_compare_create: hipEventCreate failed");
-    }
+  if (c->clock.create() != hipSuccess) {
+    delete c;
+    return fail(BQSR_ERR_DEVICE, "bqsr_compare_create: hipEventCreate failed");
+  }
   *out = c;
   return ok();
 }
@@ -796,10 +797,8 @@ bqsr_status compare_arrow_columns(bqsr_compare* c, const bqsr_compare_side* in, 
     };
     if ((e = up(&df, hf, vb)) || (e = up(&dfv, hfv, vb)) || (e = up(&dm, hm, (size_t)m)) || (e = up(&dmv, hmv, vb)))
       return e;
-    hipLaunchKernelGGL(cmp_arrow_chunk, dim3(sam_grid(m, kThreads, c->ctx->n_cu * 16)), dim3(kThreads), 0, st,
-                       (const uint32_t*)a->flags, (const uint8_t*)df, (const uint8_t*)dfv, (const int32_t*)dm,
-                       (const uint8_t*)dmv, m, base, cat, mapq, ok);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_arrow_chunk, sam_grid(m, kThreads, c->ctx->n_cu * 16), kThreads, st, a->flags, df, dfv, dm, dmv,
+                   m, base, cat, mapq, ok));
     base += m;
   }
   HIP_TRY(hipStreamSynchronize(st));  // (the host buffers are the caller's: read before the call returns)
@@ -844,8 +843,7 @@ bqsr_status compare_side(bqsr_compare* c, const bqsr_compare_side* in, bool utf8
   uint8_t* cat = nullptr;
   if ((e = sam_alloc(T.v, &cat, (size_t)n))) return e;
   if (s) {
-    hipLaunchKernelGGL(cmp_cat_sam, dim3(g), dim3(kThreads), 0, st, (const uint32_t*)s->raw_flag, n, cat);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_cat_sam, g, kThreads, st, s->raw_flag, n, cat));
   } else {
     int32_t* mq = nullptr;
     uint8_t* ok = nullptr;
@@ -859,13 +857,10 @@ bqsr_status compare_side(bqsr_compare* c, const bqsr_compare_side* in, bool utf8
     uint8_t* dq = nullptr;
     uint32_t* qlen = nullptr;
     if ((e = sam_alloc(T.v, &dq, (size_t)s->qual_bytes)) || (e = sam_alloc(T.v, &qlen, (size_t)n))) return e;
-    HIP_TRY(hipEventRecord(c->ev[6 + 2 * side], st));
-    hipLaunchKernelGGL(cmp_decode_utf8, dim3(sam_grid(n, kThreads / 64, c->ctx->n_cu * 16)), dim3(kThreads), 0, st,
-                       (const uint8_t*)s->d_text,
-                       (const uint64_t*)s->qual_span, (const uint64_t*)s->qual_off, n, dq, qlen,
-                       ctr + kCBadUtf + side);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[7 + 2 * side], st));
+    HIP_TRY(c->clock.mark(side ? bqsr_compare::DECODE2_0 : bqsr_compare::DECODE1_0, st));
+    JOB_TRY(launch(cmp_decode_utf8, sam_grid(n, kThreads / 64, c->ctx->n_cu * 16), kThreads, st, s->d_text,
+                   s->qual_span, s->qual_off, n, dq, qlen, ctr + kCBadUtf + side));
+    HIP_TRY(c->clock.mark(side ? bqsr_compare::DECODE2_1 : bqsr_compare::DECODE1_1, st));
     c->decoded[side] = true;
     D.qbase = dq;
     D.qlen = qlen;
@@ -880,29 +875,23 @@ bqsr_status compare_side(bqsr_compare* c, const bqsr_compare_side* in, bool utf8
     return e;
   HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));
   // mark_duplicates.hip's passes: keys, sort, heads, verify
-  hipLaunchKernelGGL(mdupd::mdup_keys, dim3(g), dim3(mdupd::kThreads), 0, st, S, key, idx);
-  if (c->opt.hash_bits < 64) hipLaunchKernelGGL(cmp_mask_keys, dim3(g), dim3(kThreads), 0, st, key, n, c->opt.hash_bits);
+  JOB_TRY(launch(mdupd::mdup_keys, g, mdupd::kThreads, st, S, key, idx));
+  if (c->opt.hash_bits < 64) JOB_TRY(launch(cmp_mask_keys, g, kThreads, st, key, n, c->opt.hash_bits));
   if (S.name_valid)
-    hipLaunchKernelGGL(cmp_null_name_keys, dim3(g), dim3(kThreads), 0, st, S.name_valid, (const uint32_t*)idx, key, n,
-                       c->opt.hash_bits);
-  HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_null_name_keys, g, kThreads, st, S.name_valid, idx, key, n, c->opt.hash_bits));
   if ((e = with_temp(T.v, [&](void* t, size_t& b) {
          return rocprim::radix_sort_pairs(t, b, key, key2, idx, idx2, N, 0, 64, st);
        })))
     return e;
-  hipLaunchKernelGGL(mdupd::mdup_heads, dim3(g), dim3(mdupd::kThreads), 0, st, (const uint64_t*)key2, n, head);
+  JOB_TRY(launch(mdupd::mdup_heads, g, mdupd::kThreads, st, key2, n, head));
   if ((e = with_temp(T.v, [&](void* t, size_t& b) {
          return rocprim::inclusive_scan(t, b, head, incl, N, rocprim::plus<uint32_t>(), st);
        })))
     return e;
-  hipLaunchKernelGGL(mdupd::mdup_head_pos, dim3(g), dim3(mdupd::kThreads), 0, st, (const uint32_t*)head,
-                     (const uint32_t*)incl, n, hpos);
-  hipLaunchKernelGGL(mdupd::mdup_verify, dim3(g), dim3(mdupd::kThreads), 0, st, S, (const uint32_t*)idx2,
-                     (const uint32_t*)incl, (const uint32_t*)hpos, bad);
+  JOB_TRY(launch(mdupd::mdup_head_pos, g, mdupd::kThreads, st, head, incl, n, hpos));
+  JOB_TRY(launch(mdupd::mdup_verify, g, mdupd::kThreads, st, S, idx2, incl, hpos, bad));
   if (S.name_valid)
-    hipLaunchKernelGGL(cmp_verify_null, dim3(g), dim3(kThreads), 0, st, S.name_valid, (const uint32_t*)idx2,
-                       (const uint32_t*)incl, (const uint32_t*)hpos, n, bad);
-  HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_verify_null, g, kThreads, st, S.name_valid, idx2, incl, hpos, n, bad));
   uint32_t nb32 = 0;
   int hbad = 0;
   HIP_TRY(hipMemcpyAsync(&nb32, incl + (n - 1), 4, hipMemcpyDeviceToHost, st));
@@ -913,10 +902,8 @@ bqsr_status compare_side(bqsr_compare* c, const bqsr_compare_side* in, bool utf8
   if (out->collision) return BQSR_OK;
   Desc* desc = nullptr;
   if ((e = sam_alloc(T.v, &desc, (size_t)out->nb)) || (e = sam_alloc(T.v, &out->nhash, (size_t)out->nb))) return e;
-  hipLaunchKernelGGL(cmp_desc, dim3(sam_grid(out->nb, kThreads, c->ctx->n_cu * 16)), dim3(kThreads), 0, st, S,
-                     (const uint8_t*)cat, (const uint32_t*)idx2, (const uint32_t*)hpos, out->nb,
-                     c->opt.hash_bits, desc, out->nhash);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(cmp_desc, sam_grid(out->nb, kThreads, c->ctx->n_cu * 16), kThreads, st, S, cat, idx2, hpos, out->nb,
+                 c->opt.hash_bits, desc, out->nhash));
   D.idx = idx2;
   D.head_pos = hpos;
   D.desc = desc;
@@ -983,7 +970,7 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
   HIP_TRY(hipSetDevice(c->ctx->device));
   hipStream_t st = S(stream);
   c->release();
-  c->ms[0] = c->ms[1] = c->ms[2] = 0.0;
+  for (double& v : c->ms) v = 0.0;
   c->decoded[0] = c->decoded[1] = false;
   uint32_t want = c->opt.comparisons;
   Terms TT{};
@@ -1018,7 +1005,7 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
   uint32_t *p1 = nullptr, *p2 = nullptr;
   cmp_ull *cnt = nullptr, *off = nullptr;
   uint32_t* matched2 = nullptr;
-  HIP_TRY(hipEventRecord(c->ev[0], st));
+  HIP_TRY(c->clock.mark(bqsr_compare::JOIN_0, st));
   if ((e = sam_alloc(T.v, &cnt, (size_t)nb1)) || (e = sam_alloc(T.v, &off, (size_t)nb1)) ||
       (e = sam_alloc(T.v, &matched2, (size_t)nb2)))
     return e;
@@ -1030,14 +1017,13 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
     if ((e = sam_alloc(T.v, &nh2s, (size_t)nb2)) || (e = sam_alloc(T.v, &bid2, (size_t)nb2)) ||
         (e = sam_alloc(T.v, &bid2s, (size_t)nb2)))
       return e;
-    hipLaunchKernelGGL(cmp_iota, dim3(sam_grid(nb2, kThreads, cap)), dim3(kThreads), 0, st, nb2, bid2);
+    JOB_TRY(launch(cmp_iota, sam_grid(nb2, kThreads, cap), kThreads, st, nb2, bid2));
     if ((e = with_temp(T.v, [&](void* t, size_t& b) {
            return rocprim::radix_sort_pairs(t, b, B.nhash, nh2s, bid2, bid2s, (size_t)nb2, 0, 64, st);
          })))
       return e;
-    hipLaunchKernelGGL(cmp_join_count, dim3(sam_grid(nb1, kThreads, cap)), dim3(kThreads), 0, st, A.D, B.D,
-                       (const uint64_t*)A.nhash, (const uint64_t*)nh2s, (const uint32_t*)bid2s, cnt, matched2);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_join_count, sam_grid(nb1, kThreads, cap), kThreads, st, A.D, B.D, A.nhash, nh2s, bid2s, cnt,
+                   matched2));
     if ((e = with_temp(T.v, [&](void* t, size_t& b) {
            return rocprim::exclusive_scan(t, b, cnt, off, (cmp_ull)0, (size_t)nb1, rocprim::plus<cmp_ull>(), st);
          })))
@@ -1051,18 +1037,15 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
     np = (int64_t)(last[0] + last[1]);
     if (np) {
       if ((e = sam_alloc(T.v, &p1, (size_t)np)) || (e = sam_alloc(T.v, &p2, (size_t)np))) return e;
-      hipLaunchKernelGGL(cmp_join_emit, dim3(sam_grid(nb1, kThreads, cap)), dim3(kThreads), 0, st, A.D, B.D,
-                         (const uint64_t*)A.nhash, (const uint64_t*)nh2s, (const uint32_t*)bid2s,
-                         (const cmp_ull*)off, p1, p2);
-      HIP_TRY(hipGetLastError());
+      JOB_TRY(launch(cmp_join_emit, sam_grid(nb1, kThreads, cap), kThreads, st, A.D, B.D, A.nhash, nh2s, bid2s, off, p1,
+                     p2));
     }
   }
   if (nb1 + nb2) {
-    hipLaunchKernelGGL(cmp_uniques, dim3(sam_grid(std::max(nb1, nb2), kThreads, cap)), dim3(kThreads), 0, st,
-                       (const cmp_ull*)cnt, nb1, (const uint32_t*)matched2, nb2, ctr + kCUnique);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_uniques, sam_grid(std::max(nb1, nb2), kThreads, cap), kThreads, st, cnt, nb1, matched2, nb2,
+                   ctr + kCUnique));
   }
-  HIP_TRY(hipEventRecord(c->ev[1], st));
+  HIP_TRY(c->clock.mark(bqsr_compare::JOIN_1, st));
   out->n_pairs = np;
   // ---- pass 3: scalars and the work list
   uint8_t* pmask = nullptr;
@@ -1072,16 +1055,14 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
   Items I{};
   int64_t nw = 0, chars = 0;
   cmp_ull* coff = nullptr;
-  HIP_TRY(hipEventRecord(c->ev[2], st));
+  HIP_TRY(c->clock.mark(bqsr_compare::SCALAR_0, st));
   if (np) {
     if ((e = sam_alloc(T.v, &pmask, (size_t)np)) || (e = sam_alloc(T.v, &nwork, (size_t)np)) ||
         (e = sam_alloc(T.v, &woff, (size_t)np)) || (e = sam_alloc(T.v, &posval, (size_t)np)) ||
         (e = sam_alloc(T.v, &pflag, (size_t)np)))
       return e;
     const unsigned gp = sam_grid(np, kThreads, cap);
-    hipLaunchKernelGGL(cmp_pairs, dim3(gp), dim3(kThreads), 0, st, A.D, B.D, (const uint32_t*)p1, (const uint32_t*)p2,
-                       np, want, TT, pmask, nwork, posval, pflag, ctr);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_pairs, gp, kThreads, st, A.D, B.D, p1, p2, np, want, TT, pmask, nwork, posval, pflag, ctr));
     if ((e = with_temp(T.v, [&](void* t, size_t& b) {
            return rocprim::exclusive_scan(t, b, nwork, woff, (cmp_ull)0, (size_t)np, rocprim::plus<cmp_ull>(), st);
          })))
@@ -1100,13 +1081,10 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
         (e = sam_alloc(T.v, &I.q1, W)) || (e = sam_alloc(T.v, &I.q2, W)) || (e = sam_alloc(T.v, &I.len, W)) ||
         (e = sam_alloc(T.v, &I.mkey, W)) || (e = sam_alloc(T.v, &coff, W + 1)))
       return e;
-    hipLaunchKernelGGL(cmp_items, dim3(sam_grid(np, kThreads, cap)), dim3(kThreads), 0, st, A.D, B.D,
-                       (const uint32_t*)p1, (const uint32_t*)p2, np, (const uint8_t*)pmask, (const cmp_ull*)woff, I);
-    hipLaunchKernelGGL(cmp_item_values, dim3(sam_grid(nw, kThreads, cap)), dim3(kThreads), 0, st, A.D, B.D, nw, want,
-                       TT, I, pflag, ctr);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_items, sam_grid(np, kThreads, cap), kThreads, st, A.D, B.D, p1, p2, np, pmask, woff, I));
+    JOB_TRY(launch(cmp_item_values, sam_grid(nw, kThreads, cap), kThreads, st, A.D, B.D, nw, want, TT, I, pflag, ctr));
   }
-  HIP_TRY(hipEventRecord(c->ev[3], st));
+  HIP_TRY(c->clock.mark(bqsr_compare::SCALAR_1, st));
   // the unbounded histograms: sort and run-length-encode
   if ((want & (1u << kPos)) && np)
     if ((e = compare_rle<int64_t>(c, T, st, posval, np, &c->pos_val, &c->pos_cnt, &c->n_pos))) return e;
@@ -1127,7 +1105,7 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
     HIP_TRY(hipStreamSynchronize(st));
     chars = (int64_t)total;
   }
-  HIP_TRY(hipEventRecord(c->ev[4], st));
+  HIP_TRY(c->clock.mark(bqsr_compare::BASEQS_0, st));
   if (chars) {
     BaseqArgs G{};
     G.q1 = A.D.qbase;
@@ -1146,10 +1124,9 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
     G.T = TT;
     const int64_t groups = c->opt.baseq_groups ? c->opt.baseq_groups : (int64_t)c->ctx->n_cu * 2;
     const unsigned gb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(G.n_chunks, groups));
-    hipLaunchKernelGGL(cmp_baseqs, dim3(gb), dim3(kBqThreads), 0, st, G);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_baseqs, gb, kBqThreads, st, G));
   }
-  HIP_TRY(hipEventRecord(c->ev[5], st));
+  HIP_TRY(c->clock.mark(bqsr_compare::BASEQS_1, st));
   out->baseq_chars = chars;
   // ---- pass 5: findreads
   if (n_terms && np) {
@@ -1160,9 +1137,7 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
     const size_t P = (size_t)np;
     if ((e = sam_alloc(T.v, &pass, P)) || (e = sam_alloc(T.v, &sel, P)) || (e = sam_alloc(T.v, &nsel, 1))) return e;
     const uint32_t all = n_terms >= 32 ? ~0u : (1u << n_terms) - 1u;
-    hipLaunchKernelGGL(cmp_predicate, dim3(sam_grid(np, kThreads, cap)), dim3(kThreads), 0, st,
-                       (const uint32_t*)pflag, np, all, pass);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(cmp_predicate, sam_grid(np, kThreads, cap), kThreads, st, pflag, np, all, pass));
     if ((e = with_temp(T.v, [&](void* t, size_t& b) {  // one select: the passing pairs' indices
            return rocprim::select(t, b, rocprim::counting_iterator<uint32_t>(0), pass, sel, nsel, P, st);
          })))
@@ -1174,17 +1149,15 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
       if ((e = sam_alloc(T.v, &skey, (size_t)hs)) || (e = sam_alloc(T.v, &sval, (size_t)hs)) ||
           (e = sam_alloc(T.v, &okey, (size_t)hs)) || (e = sam_alloc(T.v, &oval, (size_t)hs)))
         return e;
-      hipLaunchKernelGGL(cmp_row_keys, dim3(sam_grid((int64_t)hs, kThreads, cap)), dim3(kThreads), 0, st, A.D, B.D,
-                         (const uint32_t*)p1, (const uint32_t*)p2, (const uint32_t*)sel, (int64_t)hs, skey, sval);
-      HIP_TRY(hipGetLastError());
+      JOB_TRY(launch(cmp_row_keys, sam_grid((int64_t)hs, kThreads, cap), kThreads, st, A.D, B.D, p1, p2, sel,
+                     (int64_t)hs, skey, sval));
       if ((e = with_temp(T.v, [&](void* t, size_t& b) {
              return rocprim::radix_sort_pairs(t, b, skey, okey, sval, oval, (size_t)hs, 0, 64, st);
            })))
         return e;
       if ((e = sam_alloc(c->keep, &c->row1, (size_t)hs)) || (e = sam_alloc(c->keep, &c->row2, (size_t)hs))) return e;
-      hipLaunchKernelGGL(cmp_split_rows, dim3(sam_grid((int64_t)hs, kThreads, cap)), dim3(kThreads), 0, st,
-                         (const cmp_ull*)oval, (int64_t)hs, c->row1, c->row2);
-      HIP_TRY(hipGetLastError());
+      JOB_TRY(launch(cmp_split_rows, sam_grid((int64_t)hs, kThreads, cap), kThreads, st, oval, (int64_t)hs, c->row1,
+                     c->row2));
     }
     c->n_rows = (int64_t)hs;
   }
@@ -1192,12 +1165,12 @@ bqsr_status bqsr_compare_sides(bqsr_compare* c, const bqsr_compare_side* in1, co
   HIP_TRY(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
-  float ms = 0.f;
-  for (int k = 0; k < 3; ++k)
-    if (hipEventElapsedTime(&ms, c->ev[2 * k], c->ev[2 * k + 1]) == hipSuccess) c->ms[k] = ms;
-  for (int side = 0; side < 2; ++side)  // a UTF-8 side's decode pass belongs to the baseqs time
-    if (c->decoded[side] && hipEventElapsedTime(&ms, c->ev[6 + 2 * side], c->ev[7 + 2 * side]) == hipSuccess)
-      c->ms[2] += ms;
+  c->clock.add(c->ms[bqsr_compare::JOIN], bqsr_compare::JOIN_0, bqsr_compare::JOIN_1);
+  c->clock.add(c->ms[bqsr_compare::SCALAR], bqsr_compare::SCALAR_0, bqsr_compare::SCALAR_1);
+  c->clock.add(c->ms[bqsr_compare::BASEQS], bqsr_compare::BASEQS_0, bqsr_compare::BASEQS_1);
+  // a UTF-8 side's decode pass belongs to the baseqs time
+  if (c->decoded[0]) c->clock.add(c->ms[bqsr_compare::BASEQS], bqsr_compare::DECODE1_0, bqsr_compare::DECODE1_1);
+  if (c->decoded[1]) c->clock.add(c->ms[bqsr_compare::BASEQS], bqsr_compare::DECODE2_0, bqsr_compare::DECODE2_1);
   for (int side = 0; side < 2; ++side)
     if (h[kCBadUtf + side] != ~0ull) {
       char buf[160];
@@ -1263,9 +1236,9 @@ bqsr_status bqsr_compare_rows(const bqsr_compare* c, uint32_t* head1, uint32_t* 
 
 bqsr_status bqsr_compare_kernel_times(const bqsr_compare* c, double* join_ms, double* scalar_ms, double* baseqs_ms) {
   if (!c) return fail(BQSR_ERR_INVALID_ARG, "bqsr_compare_kernel_times: null");
-  if (join_ms) *join_ms = c->ms[0];
-  if (scalar_ms) *scalar_ms = c->ms[1];
-  if (baseqs_ms) *baseqs_ms = c->ms[2];
+  if (join_ms) *join_ms = c->ms[bqsr_compare::JOIN];
+  if (scalar_ms) *scalar_ms = c->ms[bqsr_compare::SCALAR];
+  if (baseqs_ms) *baseqs_ms = c->ms[bqsr_compare::BASEQS];
   return BQSR_OK;
 }
 

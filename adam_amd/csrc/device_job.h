@@ -1,11 +1,73 @@
 // The host-side helpers of a resident device job: what a command's state
-// struct, its buffers, its rocprim calls and its launch grids are made from.
-// A new job starts from here.  Included by bqsr_capi.cpp once, after fail /
-// HIP_TRY and bqsr_context, before sam_ingest.hip.  (The one-shot form of
-// dev_prim, with_temp, sits next to sam_alloc in sam_ingest.hip.)
+// struct, its buffers, its rocprim calls, its kernel launches, its launch grids
+// and its stage times are made from.  A new job starts from here: DevBuf /
+// dev_need / dev_prim for memory, launch for every kernel, a StageClock in the
+// state struct with an enum of its stages, and on the Python side one `sig`
+// table bound with _capi.bind and _capi.stage_times over the stage names.
+// Included by bqsr_capi.cpp once, after fail / HIP_TRY and bqsr_context, before
+// sam_ingest.hip.  (The one-shot form of dev_prim, with_temp, sits next to
+// sam_alloc in sam_ingest.hip.)
 #pragma once
 
+// a step of a job that answers with a bqsr_status (HIP_TRY's counterpart; the message is the step's own)
+#define JOB_TRY(expr)                  \
+  do {                                 \
+    const bqsr_status s_ = (expr);     \
+    if (s_ != BQSR_OK) return s_;      \
+  } while (0)
+
 namespace {
+
+// a kernel launch and what hipGetLastError() says after it; the arguments convert to the kernel's parameter
+// types.  For a site that gathers a hipError_t and frees what it holds itself; every other site uses launch.
+template <class... P, class... A>
+hipError_t launch_err(void (*kernel)(P...), dim3 grid, dim3 threads, hipStream_t s, A&&... args) {
+  kernel<<<grid, threads, 0, s>>>(std::forward<A>(args)...);
+  return hipGetLastError();
+}
+
+// a kernel launch and its check
+template <class... P, class... A>
+bqsr_status launch(void (*kernel)(P...), dim3 grid, dim3 threads, hipStream_t s, A&&... args) {
+  const hipError_t e = launch_err(kernel, grid, threads, s, std::forward<A>(args)...);
+  if (e != hipSuccess) return fail(BQSR_ERR_DEVICE, std::string("hipGetLastError() failed: ") + hipGetErrorString(e));
+  return BQSR_OK;
+}
+
+// N marks on a stream, the time between any two of them added to a stage.  One
+// mark may end a stage and start the next.  The events are made at the first
+// mark (or by create()) and live as long as the clock, which owns them and is
+// not copied.  add() adds: a job zeroes its stages at its start, so a stage
+// read once holds that span and one read per chunk (compare's decode passes,
+// the Arrow tag calls) holds their sum.
+template <int N>
+struct StageClock {
+  hipEvent_t ev[N] = {};
+  StageClock() = default;
+  StageClock(const StageClock&) = delete;
+  StageClock& operator=(const StageClock&) = delete;
+  ~StageClock() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t create() {
+    for (hipEvent_t& e : ev)
+      if (!e) {
+        const hipError_t r = hipEventCreate(&e);
+        if (r != hipSuccess) return r;
+      }
+    return hipSuccess;
+  }
+  hipError_t mark(int i, hipStream_t s) {
+    const hipError_t r = create();
+    return r != hipSuccess ? r : hipEventRecord(ev[i], s);
+  }
+  // after the job's synchronize: the milliseconds from mark a to mark b, added to ms (left alone if the query fails)
+  void add(double& ms, int a, int b) const {
+    float v = 0.f;
+    if (hipEventElapsedTime(&v, ev[a], ev[b]) == hipSuccess) ms += v;
+  }
+};
 
 // a device buffer that only grows
 struct DevBuf {

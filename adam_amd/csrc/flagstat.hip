@@ -325,10 +325,8 @@ bqsr_status bqsr_sam_flagstat(bqsr_context* ctx, const bqsr_sam* sm, void* strea
   FlagstatDev F;
   bqsr_status e;
   if ((e = flagstat_begin(ctx, F, s)) != BQSR_OK) return e;
-  hipLaunchKernelGGL(fstk::flagstat_sam, dim3(flagstat_grid(ctx, (n + 63) / 64, 8)), dim3(fstk::kThreads), 0, s,
-                     (const uint8_t*)sm->d_text, (const uint64_t*)sm->line_span, (const uint32_t*)sm->raw_flag,
-                     (const uint32_t*)sm->flags, (const int32_t*)sm->sq_id, sm->sq_tab, n, (int64_t)0, F.d);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(fstk::flagstat_sam, flagstat_grid(ctx, (n + 63) / 64, 8), fstk::kThreads, s, sm->d_text, sm->line_span,
+                 sm->raw_flag, sm->flags, sm->sq_id, sm->sq_tab, n, (int64_t)0, F.d));
   return flagstat_end(F, s, "flagstat", out);
 }
 
@@ -388,9 +386,7 @@ bqsr_status bqsr_flagstat_arrow(bqsr_context* ctx, const bqsr_flagstat_chunk* ch
       HIP_TRY(bitmap(iv[k] ? ivv[k] : nullptr, &C.ivv[k]));
     }
     const int64_t groups = (m + 63) / 64;
-    hipLaunchKernelGGL(fstk::flagstat_arrow, dim3(flagstat_grid(ctx, (groups + 63) / 64, 4)),
-                       dim3(fstk::kThreads), 0, s, C, F.d);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(fstk::flagstat_arrow, flagstat_grid(ctx, (groups + 63) / 64, 4), fstk::kThreads, s, C, F.d));
     r0 += m;
   }
   return flagstat_end(F, s, "flagstat", out);
@@ -420,9 +416,8 @@ bqsr_status bqsr_flagstat_arrow_device(bqsr_context* ctx, const bqsr_flagstat_ch
   C.ivv[2] = chunk->mapq ? (const uint64_t*)chunk->mapq_validity : nullptr;
   if (C.n == 0) return ok();
   const int64_t groups = (C.n + 63) / 64;
-  hipLaunchKernelGGL(fstk::flagstat_arrow, dim3(flagstat_grid(ctx, (groups + 63) / 64, 4)),
-                     dim3(fstk::kThreads), 0, S(stream), C, (unsigned long long*)counters);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(fstk::flagstat_arrow, flagstat_grid(ctx, (groups + 63) / 64, 4), fstk::kThreads, S(stream), C,
+                 (unsigned long long*)counters));
   return ok();
 }
 

@@ -369,37 +369,33 @@ bqsr_status mark_duplicates_device(bqsr_sam* s, int64_t* n_duplicates, std::vect
   if (he == hipSuccess) he = hipMemsetAsync(ndup, 0, sizeof(unsigned long long), st);
   if (he != hipSuccess) return fail(BQSR_ERR_DEVICE, hipGetErrorString(he));
   // 1. buckets: (rg, QNAME) keys sorted with the read index
-  hipLaunchKernelGGL(mdup_keys, dim3(g), dim3(kThreads), 0, st, S, key, idx);
+  JOB_TRY(launch(mdup_keys, g, kThreads, st, S, key, idx));
   size_t t1 = tb;
   HIP_TRY(rocprim::radix_sort_pairs(temp, t1, key, key2, idx, idx2, (size_t)n, 0, 64, st));
-  hipLaunchKernelGGL(mdup_heads, dim3(g), dim3(kThreads), 0, st, (const uint64_t*)key2, n, head);
+  JOB_TRY(launch(mdup_heads, g, kThreads, st, key2, n, head));
   size_t t2 = tb;
   HIP_TRY(rocprim::inclusive_scan(temp, t2, head, incl, (size_t)n, rocprim::plus<uint32_t>(), st));
-  hipLaunchKernelGGL(mdup_head_pos, dim3(g), dim3(kThreads), 0, st, (const uint32_t*)head, (const uint32_t*)incl, n,
-                     hpos);
-  hipLaunchKernelGGL(mdup_verify, dim3(g), dim3(kThreads), 0, st, S, (const uint32_t*)idx2, (const uint32_t*)incl,
-                     (const uint32_t*)hpos, bad);
+  JOB_TRY(launch(mdup_head_pos, g, kThreads, st, head, incl, n, hpos));
+  JOB_TRY(launch(mdup_verify, g, kThreads, st, S, idx2, incl, hpos, bad));
   uint32_t nb32 = 0;
   HIP_TRY(hipMemcpyAsync(&nb32, incl + (n - 1), 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const int64_t nb = nb32;
   const unsigned gb = (unsigned)std::min<int64_t>((nb + kThreads - 1) / kThreads, (int64_t)s->ctx->n_cu * 16);
   // 2. per bucket
-  hipLaunchKernelGGL(mdup_buckets, dim3(gb), dim3(kThreads), 0, st, S, (const uint32_t*)idx2, (const uint32_t*)hpos,
-                     nb, kll, kr, first, score, bad);
+  JOB_TRY(launch(mdup_buckets, gb, kThreads, st, S, idx2, hpos, nb, kll, kr, first, score, bad));
   // 3. bucket order: first appearance, then right position, then (left, library) -- stable passes
-  hipLaunchKernelGGL(mdup_first_keys, dim3(gb), dim3(kThreads), 0, st, (const uint32_t*)first, nb, ka, ord2);
+  JOB_TRY(launch(mdup_first_keys, gb, kThreads, st, first, nb, ka, ord2));
   size_t t3 = tb;
   HIP_TRY(rocprim::radix_sort_pairs(temp, t3, ka, kb, ord2, ord, (size_t)nb, 0, 32, st));
-  hipLaunchKernelGGL(mdup_gather, dim3(gb), dim3(kThreads), 0, st, (const uint64_t*)kr, (const uint32_t*)ord, nb, ka);
+  JOB_TRY(launch(mdup_gather, gb, kThreads, st, kr, ord, nb, ka));
   t3 = tb;
   HIP_TRY(rocprim::radix_sort_pairs(temp, t3, ka, kb, ord, ord2, (size_t)nb, 0, 52, st));
-  hipLaunchKernelGGL(mdup_gather, dim3(gb), dim3(kThreads), 0, st, (const uint64_t*)kll, (const uint32_t*)ord2, nb, ka);
+  JOB_TRY(launch(mdup_gather, gb, kThreads, st, kll, ord2, nb, ka));
   t3 = tb;
   HIP_TRY(rocprim::radix_sort_pairs(temp, t3, ka, kb, ord2, ord, (size_t)nb, 0, 64, st));
   // 4. groups; 5. flags
-  hipLaunchKernelGGL(mdup_groups, dim3(gb), dim3(kThreads), 0, st, (const uint32_t*)ord, (const uint64_t*)kll,
-                     (const uint64_t*)kr, (const int32_t*)score, nb, outcome);
+  JOB_TRY(launch(mdup_groups, gb, kThreads, st, ord, kll, kr, score, nb, outcome));
   int hbad = 0;
   HIP_TRY(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -407,8 +403,7 @@ bqsr_status mark_duplicates_device(bqsr_sam* s, int64_t* n_duplicates, std::vect
     *bad_word = hbad;
     return ok();
   }
-  hipLaunchKernelGGL(mdup_mark, dim3(g), dim3(kThreads), 0, st, (const uint32_t*)idx2, (const uint32_t*)incl, n,
-                     (const uint8_t*)outcome, s->flags, ndup);
+  JOB_TRY(launch(mdup_mark, g, kThreads, st, idx2, incl, n, outcome, s->flags, ndup));
   unsigned long long hn = 0;
   HIP_TRY(hipMemcpyAsync(&hn, ndup, sizeof hn, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -717,9 +712,8 @@ bqsr_status dup_set_add_cols(bqsr_dup_set* d, const mdupd::DevSam& S) {
   d->part_n.push_back(n);
   if (n == 0) return ok();
   const unsigned g = (unsigned)std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)d->ctx->n_cu * 16);
-  hipLaunchKernelGGL(mdup_set_records, dim3(g), dim3(kThreads), 0, st, S, d->n, d->k1, d->k2, d->pos, d->score,
-                     d->lib, d->cls, d->bad);
-  hipError_t he = hipGetLastError();
+  hipError_t he = launch_err(mdup_set_records, g, kThreads, st, S, d->n, d->k1, d->k2, d->pos, d->score, d->lib, d->cls,
+                             d->bad);
   if (he == hipSuccess) he = hipStreamSynchronize(st);
   if (he != hipSuccess) return fail(BQSR_ERR_DEVICE, hipGetErrorString(he));
   d->n += n;
@@ -778,18 +772,16 @@ bqsr_status bqsr_dup_set_finish(bqsr_dup_set* d, int64_t* n_duplicates) {
   if ((e = dalloc(tmp, (uint8_t**)&temp, tb))) return e;
   const unsigned g = (unsigned)std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)d->ctx->n_cu * 16);
   // 1. slots sorted by (k1, k2), stable: k2 pass, then k1 pass
-  hipLaunchKernelGGL(mdup_iota, dim3(g), dim3(kThreads), 0, st, n, idx);
+  JOB_TRY(launch(mdup_iota, g, kThreads, st, n, idx));
   size_t t = tb;
   HIP_TRY(rocprim::radix_sort_pairs(temp, t, d->k2, kb, idx, idx2, N, 0, 64, st));
-  hipLaunchKernelGGL(mdup_gather, dim3(g), dim3(kThreads), 0, st, (const uint64_t*)d->k1, (const uint32_t*)idx2, n, ka);
+  JOB_TRY(launch(mdup_gather, g, kThreads, st, d->k1, idx2, n, ka));
   t = tb;
   HIP_TRY(rocprim::radix_sort_pairs(temp, t, ka, kb, idx2, idx, N, 0, 64, st));
-  hipLaunchKernelGGL(mdup_set_heads, dim3(g), dim3(kThreads), 0, st, (const uint64_t*)kb, (const uint64_t*)d->k2,
-                     (const uint32_t*)idx, n, head);
+  JOB_TRY(launch(mdup_set_heads, g, kThreads, st, kb, d->k2, idx, n, head));
   t = tb;
   HIP_TRY(rocprim::inclusive_scan(temp, t, head, incl, N, rocprim::plus<uint32_t>(), st));
-  hipLaunchKernelGGL(mdup_head_pos, dim3(g), dim3(kThreads), 0, st, (const uint32_t*)head, (const uint32_t*)incl, n,
-                     hpos);
+  JOB_TRY(launch(mdup_head_pos, g, kThreads, st, head, incl, n, hpos));
   uint32_t nb32 = 0;
   HIP_TRY(hipMemcpyAsync(&nb32, incl + (n - 1), 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -800,23 +792,20 @@ bqsr_status bqsr_dup_set_finish(bqsr_dup_set* d, int64_t* n_duplicates) {
     return e;
   const unsigned gb = (unsigned)std::min<int64_t>((nb + kThreads - 1) / kThreads, (int64_t)d->ctx->n_cu * 16);
   // 2. per bucket; 3. bucket order; 4. groups (the single-parse passes)
-  hipLaunchKernelGGL(mdup_set_buckets, dim3(gb), dim3(kThreads), 0, st, (const uint64_t*)d->pos,
-                     (const int32_t*)d->score, (const uint16_t*)d->lib, (const uint8_t*)d->cls, (const uint32_t*)idx,
-                     (const uint32_t*)hpos, nb, n, kll, kr, first, score);
-  hipLaunchKernelGGL(mdup_first_keys, dim3(gb), dim3(kThreads), 0, st, (const uint32_t*)first, nb, ka, ord2);
+  JOB_TRY(launch(mdup_set_buckets, gb, kThreads, st, d->pos, d->score, d->lib, d->cls, idx, hpos, nb, n, kll, kr, first,
+                 score));
+  JOB_TRY(launch(mdup_first_keys, gb, kThreads, st, first, nb, ka, ord2));
   t = tb;
   HIP_TRY(rocprim::radix_sort_pairs(temp, t, ka, kb, ord2, ord, (size_t)nb, 0, 32, st));
-  hipLaunchKernelGGL(mdup_gather, dim3(gb), dim3(kThreads), 0, st, (const uint64_t*)kr, (const uint32_t*)ord, nb, ka);
+  JOB_TRY(launch(mdup_gather, gb, kThreads, st, kr, ord, nb, ka));
   t = tb;
   HIP_TRY(rocprim::radix_sort_pairs(temp, t, ka, kb, ord, ord2, (size_t)nb, 0, 52, st));
-  hipLaunchKernelGGL(mdup_gather, dim3(gb), dim3(kThreads), 0, st, (const uint64_t*)kll, (const uint32_t*)ord2, nb, ka);
+  JOB_TRY(launch(mdup_gather, gb, kThreads, st, kll, ord2, nb, ka));
   t = tb;
   HIP_TRY(rocprim::radix_sort_pairs(temp, t, ka, kb, ord2, ord, (size_t)nb, 0, 64, st));
-  hipLaunchKernelGGL(mdup_groups, dim3(gb), dim3(kThreads), 0, st, (const uint32_t*)ord, (const uint64_t*)kll,
-                     (const uint64_t*)kr, (const int32_t*)score, nb, outcome);
+  JOB_TRY(launch(mdup_groups, gb, kThreads, st, ord, kll, kr, score, nb, outcome));
   // 5. the bits
-  hipLaunchKernelGGL(mdup_set_mark, dim3(g), dim3(kThreads), 0, st, (const uint32_t*)idx, (const uint32_t*)incl, n,
-                     (const uint8_t*)outcome, (const uint8_t*)d->cls, d->bits, d->cnt);
+  JOB_TRY(launch(mdup_set_mark, g, kThreads, st, idx, incl, n, outcome, d->cls, d->bits, d->cnt));
   unsigned long long hn = 0;
   HIP_TRY(hipMemcpyAsync(&hn, d->cnt, sizeof hn, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -842,9 +831,7 @@ bqsr_status bqsr_dup_set_apply(bqsr_dup_set* d, int64_t part, bqsr_sam* s, int64
   if (n) {
     HIP_TRY(hipMemsetAsync(d->cnt, 0, sizeof(unsigned long long), st));
     const unsigned g = (unsigned)std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)d->ctx->n_cu * 16);
-    hipLaunchKernelGGL(mdup_set_apply, dim3(g), dim3(kThreads), 0, st, (const uint32_t*)d->bits,
-                       d->part_base[(size_t)part], n, s->flags, d->cnt);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(mdup_set_apply, g, kThreads, st, d->bits, d->part_base[(size_t)part], n, s->flags, d->cnt));
     HIP_TRY(hipMemcpyAsync(&hn, d->cnt, sizeof hn, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }

@@ -519,15 +519,14 @@ struct MpState {
   int64_t nk = 0, n_ev = 0, n_lines = 0, text_bytes = 0;
   int pos_bits = 1;
   bool prepared = false;
-  hipEvent_t ev[8] = {};
-  ~MpState() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  StageClock<8> clock;
 };
 
-// walk, emit, sort, group, text: the calling thread's last prepare / text calls
-thread_local double g_mpileup_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+// the stages of the calling thread's last prepare / text calls (mpileup.KERNELS), and the clock's marks: the one
+// after emit starts sort, the one after sort starts group
+enum { MP_WALK, MP_EMIT, MP_SORT, MP_GROUP, MP_TEXT, MP_STAGES };
+enum { MP_WALK_0, MP_WALK_1, MP_EMIT_0, MP_SORT_0, MP_GROUP_0, MP_GROUP_1, MP_TEXT_0, MP_TEXT_1 };
+thread_local double g_mpileup_ms[MP_STAGES] = {0.0, 0.0, 0.0, 0.0, 0.0};
 
 struct MpView {
   mpk::Reads A;
@@ -559,8 +558,6 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
   A.nk = A.n_ev = A.n_lines = A.text_bytes = 0;
   *out = bqsr_mpileup_sizes{0, 0, 0, 0};
   for (double& t : g_mpileup_ms) t = 0.0;
-  for (hipEvent_t& e : A.ev)
-    if (!e) HIP_TRY(hipEventCreate(&e));
   const int64_t n = V.n_reads;
   if (n > (int64_t)INT32_MAX)
     return fail(BQSR_ERR_UNSUPPORTED, "mpileup: more than 2^31 - 1 reads in one job");
@@ -599,16 +596,13 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
     return e;
   HIP_TRY(hipMemsetAsync(small, 0xFF, 16 * 8, s));
   HIP_TRY(hipMemsetAsync(small + 2, 0, 8, s));
-  HIP_TRY(hipEventRecord(A.ev[0], s));
-  hipLaunchKernelGGL(mp_keep, dim3(grid(n)), dim3(kThreads), 0, s, V.A, n, keep);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(A.clock.mark(MP_WALK_0, s));
+  JOB_TRY(launch(mp_keep, grid(n), kThreads, s, V.A, n, keep));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, keep, kpos, (uint32_t)0, (size_t)n + 1, rocprim::plus<uint32_t>(), s);
        })))
     return e;
-  hipLaunchKernelGGL(mp_compact, dim3(grid(n)), dim3(kThreads), 0, s, (const uint32_t*)keep,
-                     (const uint32_t*)kpos, n, kidx);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(mp_compact, grid(n), kThreads, s, keep, kpos, n, kidx));
   uint32_t nk32 = 0;
   HIP_TRY(hipMemcpyAsync(&nk32, kpos + n, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -632,9 +626,8 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
     return e;
   HIP_TRY(hipMemsetAsync(X.cnt + nk, 0, 8, s));
   WalkParams W{V.A, X, kidx, nk, small, small + 1, small + 2};
-  hipLaunchKernelGGL(mp_walk, dim3(grid(nk)), dim3(kThreads), 0, s, W);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[1], s));
+  JOB_TRY(launch(mp_walk, grid(nk), kThreads, s, W));
+  HIP_TRY(A.clock.mark(MP_WALK_1, s));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, X.cnt, es, (uint64_t)0, K + 1, rocprim::plus<uint64_t>(), s);
        })) ||
@@ -649,8 +642,7 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
   HIP_TRY(hipMemcpyAsync(&total, es + nk, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&n_seg, segid1 + (nk - 1), 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, A.ev[0], A.ev[1]) == hipSuccess) g_mpileup_ms[0] = ms;
+  A.clock.add(g_mpileup_ms[MP_WALK], MP_WALK_0, MP_WALK_1);
   if (st3[0] != ~0ull) {
     const int status = (int)(st3[0] & 0xFF);
     const int64_t read = (int64_t)(st3[0] >> 8);
@@ -683,15 +675,14 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
       (e = need(A.val_a, &val_a, M, "events")) || (e = need(A.val_b, &val_b, M, "events")))
     return e;
   EmitParams E{V.A, X, kidx, es, segid1, nk, m, pos_bits, key_a, val_a};
-  HIP_TRY(hipEventRecord(A.ev[2], s));
-  hipLaunchKernelGGL(mp_emit, dim3(grid(m)), dim3(kThreads), 0, s, E);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[3], s));
+  HIP_TRY(A.clock.mark(MP_EMIT_0, s));
+  JOB_TRY(launch(mp_emit, grid(m), kThreads, s, E));
+  HIP_TRY(A.clock.mark(MP_SORT_0, s));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::radix_sort_pairs(t, b, key_a, key_b, val_a, val_b, M, 0, (unsigned)key_bits, s);
        })))
     return e;
-  HIP_TRY(hipEventRecord(A.ev[4], s));
+  HIP_TRY(A.clock.mark(MP_GROUP_0, s));
   A.key = key_b;
   A.val = val_b;
   // ---- group ----
@@ -703,8 +694,7 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
       (e = need(A.mask, &mask, M, "events")) || (e = need(A.first, &first, M + 1, "events")))
     return e;
   GroupParams G{V.A, kidx, key_b, val_b, m, head, len, mask};
-  hipLaunchKernelGGL(mp_heads, dim3(grid(m)), dim3(kThreads), 0, s, G);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(mp_heads, grid(m), kThreads, s, G));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::inclusive_scan(t, b, head, line1, M, rocprim::plus<uint32_t>(), s);
        })) ||
@@ -721,9 +711,7 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
       (e = need(A.linebase, &linebase, NL, "lines")) || (e = need(A.linelen, &linelen, NL + 1, "lines")) ||
       (e = need(A.lineoff, &lineoff, NL + 1, "lines")))
     return e;
-  hipLaunchKernelGGL(mp_first, dim3(grid(m)), dim3(kThreads), 0, s, (const uint32_t*)head,
-                     (const uint32_t*)line1, m, first);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(mp_first, grid(m), kThreads, s, head, line1, m, first));
   // per line the OR of its events' reference-base bits (head is free: the unique keys go there, the count after them)
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::reduce_by_key(t, b, line1, mask, M, head, linemask, linemask + nl, mpk::BitOr(),
@@ -732,21 +720,20 @@ bqsr_status mp_prepare(bqsr_context* ctx, MpState& A, const MpView& V, hipStream
     return e;
   LineParams LP{V.A, kidx, key_b, val_b, first, evoff, linemask, (const uint64_t*)A.name_off.p, nl, pos_bits,
                 hdrlen, linebase, linelen, small + 3};
-  hipLaunchKernelGGL(mp_lines, dim3(grid(nl)), dim3(kThreads), 0, s, LP);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(mp_lines, grid(nl), kThreads, s, LP));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, linelen, lineoff, (uint64_t)0, NL + 1, rocprim::plus<uint64_t>(), s);
        })))
     return e;
-  HIP_TRY(hipEventRecord(A.ev[5], s));
+  HIP_TRY(A.clock.mark(MP_GROUP_1, s));
   unsigned long long conflict = ~0ull;
   uint64_t bytes = 0;
   HIP_TRY(hipMemcpyAsync(&conflict, small + 3, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&bytes, lineoff + nl, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (hipEventElapsedTime(&ms, A.ev[2], A.ev[3]) == hipSuccess) g_mpileup_ms[1] = ms;
-  if (hipEventElapsedTime(&ms, A.ev[3], A.ev[4]) == hipSuccess) g_mpileup_ms[2] = ms;
-  if (hipEventElapsedTime(&ms, A.ev[4], A.ev[5]) == hipSuccess) g_mpileup_ms[3] = ms;
+  A.clock.add(g_mpileup_ms[MP_EMIT], MP_EMIT_0, MP_SORT_0);
+  A.clock.add(g_mpileup_ms[MP_SORT], MP_SORT_0, MP_GROUP_0);
+  A.clock.add(g_mpileup_ms[MP_GROUP], MP_GROUP_0, MP_GROUP_1);
   if (conflict != ~0ull) {  // name the reference and the position
     uint32_t j0 = 0;
     uint64_t key = 0, val = 0;
@@ -778,13 +765,12 @@ bqsr_status mp_text_call(bqsr_context* ctx, MpState& A, const MpView& V, int64_t
     return fail(BQSR_ERR_INVALID_ARG, std::string(who) + ": line0 or the budget out of range");
   *n_lines = 0;
   *n_bytes = 0;
-  g_mpileup_ms[4] = 0.0;
+  g_mpileup_ms[MP_TEXT] = 0.0;
   if (line0 == A.n_lines) return ok();
   unsigned long long* small = (unsigned long long*)A.small.p;
   uint64_t* win = (uint64_t*)(small + 8);
-  hipLaunchKernelGGL(mp_window, dim3(1), dim3(64), 0, s, (const uint64_t*)A.lineoff.p, (const uint32_t*)A.first.p,
-                     A.n_lines, line0, (uint64_t)budget, win);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(mp_window, 1, 64, s, (const uint64_t*)A.lineoff.p, (const uint32_t*)A.first.p, A.n_lines, line0,
+                 (uint64_t)budget, win));
   uint64_t w[6];
   HIP_TRY(hipMemcpyAsync(w, win, sizeof w, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -801,14 +787,12 @@ bqsr_status mp_text_call(bqsr_context* ctx, MpState& A, const MpView& V, int64_t
                (const uint64_t*)A.evoff.p, (const uint64_t*)A.lineoff.p, (const uint32_t*)A.hdrlen.p,
                (const uint8_t*)A.linebase.p, (const uint8_t*)A.names.p, (const uint64_t*)A.name_off.p,
                (int64_t)w[4], (int64_t)w[5], w[1], nbytes, A.pos_bits, out};
-  HIP_TRY(hipEventRecord(A.ev[6], s));
-  hipLaunchKernelGGL(mp_text, dim3(pileup_job_grid(ctx, T.e1 - T.e0, kThreads)), dim3(kThreads), 0, s, T);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[7], s));
+  HIP_TRY(A.clock.mark(MP_TEXT_0, s));
+  JOB_TRY(launch(mp_text, pileup_job_grid(ctx, T.e1 - T.e0, kThreads), kThreads, s, T));
+  HIP_TRY(A.clock.mark(MP_TEXT_1, s));
   HIP_TRY(hipMemcpyAsync(dst, out, (size_t)nbytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, A.ev[6], A.ev[7]) == hipSuccess) g_mpileup_ms[4] = ms;
+  A.clock.add(g_mpileup_ms[MP_TEXT], MP_TEXT_0, MP_TEXT_1);
   *n_lines = l1 - line0;
   *n_bytes = (int64_t)nbytes;
   return ok();
@@ -893,7 +877,7 @@ bqsr_status bqsr_arrow_mpileup_text(bqsr_context* ctx, bqsr_arrow* a, int64_t li
 
 bqsr_status bqsr_mpileup_kernel_times(double* ms5) {
   if (!ms5) return fail(BQSR_ERR_INVALID_ARG, "bqsr_mpileup_kernel_times: null");
-  for (int k = 0; k < 5; ++k) ms5[k] = g_mpileup_ms[k];
+  for (int k = 0; k < MP_STAGES; ++k) ms5[k] = g_mpileup_ms[k];
   return BQSR_OK;
 }
 

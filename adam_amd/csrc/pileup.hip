@@ -444,7 +444,7 @@ struct PileupState {
   uint8_t* col_block = nullptr;
   int64_t r0 = 0, n = 0, n_rows = 0;
   bool prepared = false;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  StageClock<4> clock;
   std::vector<void*> per_parse, per_range;
   static void drop(std::vector<void*>& v) {
     for (void* p : v) (void)hipFree(p);
@@ -455,13 +455,13 @@ struct PileupState {
     drop(per_range);
     for (void* p : {(void*)err, (void*)a_mapq, (void*)a_mapq_ok, (void*)col_block})
       if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
   }
 };
 
-// the two kernels' times of the calling thread's last prepare / columns
-thread_local double g_pileup_ms[2] = {0.0, 0.0};
+// the two kernels' times of the calling thread's last prepare / columns, and the clock's marks around them
+enum { PILEUP_COUNT, PILEUP_EMIT, PILEUP_STAGES };
+enum { PILEUP_COUNT_0, PILEUP_COUNT_1, PILEUP_EMIT_0, PILEUP_EMIT_1 };
+thread_local double g_pileup_ms[PILEUP_STAGES] = {0.0, 0.0};
 
 struct PileupView {
   pilk::Reads R;
@@ -496,8 +496,6 @@ bqsr_status pileup_prepare(bqsr_context* ctx, PileupState& A, const PileupView& 
   out->bitmap_words = 0;
   bqsr_status e;
   if (!A.err) HIP_TRY(hipMalloc((void**)&A.err, 8));
-  for (int k = 0; k < 4; ++k)
-    if (!A.ev[k]) HIP_TRY(hipEventCreate(&A.ev[k]));
   if (A.cap_cig < V.cig_ops || A.cap_md < V.md_bytes) {
     PileupState::drop(A.per_parse);
     A.cap_cig = A.cap_md = -1;
@@ -522,26 +520,24 @@ bqsr_status pileup_prepare(bqsr_context* ctx, PileupState& A, const PileupView& 
   A.r0 = r0;
   A.n = n;
   A.n_rows = 0;
-  g_pileup_ms[0] = g_pileup_ms[1] = 0.0;
+  g_pileup_ms[PILEUP_COUNT] = g_pileup_ms[PILEUP_EMIT] = 0.0;
   if (n == 0) {
     A.prepared = true;
     return ok();
   }
   HIP_TRY(hipMemsetAsync(A.err, 0xFF, 8, s));
   pilk::CountParams P{V.R, A.X, r0, n, A.err};
-  HIP_TRY(hipEventRecord(A.ev[0], s));
-  hipLaunchKernelGGL(pilk::pileup_count, dim3(pileup_grid(ctx, (n + pilk::kThreads - 1) / pilk::kThreads)),
-                     dim3(pilk::kThreads), 0, s, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[1], s));
+  HIP_TRY(A.clock.mark(PILEUP_COUNT_0, s));
+  JOB_TRY(launch(pilk::pileup_count, pileup_grid(ctx, (n + pilk::kThreads - 1) / pilk::kThreads), pilk::kThreads, s,
+                 P));
+  HIP_TRY(A.clock.mark(PILEUP_COUNT_1, s));
   if ((e = sam_scan(A.X.cnt, n, A.rs, A.part, s)) != BQSR_OK) return e;
   unsigned long long ew = ~0ull;
   uint64_t total = 0;
   HIP_TRY(hipMemcpyAsync(&ew, A.err, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&total, A.rs + n, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, A.ev[0], A.ev[1]) == hipSuccess) g_pileup_ms[0] = ms;
+  A.clock.add(g_pileup_ms[PILEUP_COUNT], PILEUP_COUNT_0, PILEUP_COUNT_1);
   if (ew != ~0ull) {
     const int status = (int)(ew & 0xFF);
     const int64_t read = r0 + (int64_t)(ew >> 8);
@@ -560,7 +556,7 @@ bqsr_status pileup_prepare(bqsr_context* ctx, PileupState& A, const PileupView& 
 bqsr_status pileup_columns(bqsr_context* ctx, PileupState& A, const PileupView& V, const bqsr_pileup_host* dst,
                            hipStream_t s, const char* who) {
   if (!A.prepared) return fail(BQSR_ERR_INVALID_ARG, std::string(who) + " before its prepare call");
-  g_pileup_ms[1] = 0.0;
+  g_pileup_ms[PILEUP_EMIT] = 0.0;
   const int64_t m = A.n_rows;
   if (m == 0) return ok();
   const size_t W = (size_t)((m + 63) / 64);
@@ -598,11 +594,10 @@ bqsr_status pileup_columns(bqsr_context* ctx, PileupState& A, const PileupView& 
   }
   pilk::EmitParams P{V.R, A.X, A.rs, A.r0, A.n, m, A.C};
   const int64_t groups = (m + 63) / 64;
-  HIP_TRY(hipEventRecord(A.ev[2], s));
-  hipLaunchKernelGGL(pilk::pileup_emit, dim3(pileup_grid(ctx, (groups + pilk::kWaves - 1) / pilk::kWaves)),
-                     dim3(pilk::kThreads), 0, s, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[3], s));
+  HIP_TRY(A.clock.mark(PILEUP_EMIT_0, s));
+  JOB_TRY(launch(pilk::pileup_emit, pileup_grid(ctx, (groups + pilk::kWaves - 1) / pilk::kWaves), pilk::kThreads, s,
+                 P));
+  HIP_TRY(A.clock.mark(PILEUP_EMIT_1, s));
   auto cp = [&](void* d, const void* src, size_t bytes) -> hipError_t {
     if (!d || !bytes) return hipSuccess;
     return hipMemcpyAsync(d, src, bytes, hipMemcpyDeviceToHost, s);
@@ -626,8 +621,7 @@ bqsr_status pileup_columns(bqsr_context* ctx, PileupState& A, const PileupView& 
   if (e == hipSuccess) e = cp(dst->map_quality_valid, A.C.v_mapq, W * 8);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return fail(BQSR_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, A.ev[2], A.ev[3]) == hipSuccess) g_pileup_ms[1] = ms;
+  A.clock.add(g_pileup_ms[PILEUP_EMIT], PILEUP_EMIT_0, PILEUP_EMIT_1);
   return ok();
 }
 
@@ -679,10 +673,8 @@ bqsr_status pileup_arrow_mapq(bqsr_context* ctx, bqsr_arrow* a, PileupState& A, 
         if ((e = sam_alloc(T.v, &dv, (size_t)(m + 7) / 8)) != BQSR_OK) return e;
         HIP_TRY(hipMemcpyAsync(dv, mapq_validity[c], (size_t)(m + 7) / 8, hipMemcpyHostToDevice, s));
       }
-      hipLaunchKernelGGL(pilk::pileup_mapq_chunk, dim3(sam_grid(m, pilk::kThreads, ctx->n_cu * 8)),
-                         dim3(pilk::kThreads), 0, s, (const int32_t*)(A.a_mapq + base), (const uint8_t*)dv, m,
-                         A.a_mapq + base, A.a_mapq_ok + base);
-      HIP_TRY(hipGetLastError());
+      JOB_TRY(launch(pilk::pileup_mapq_chunk, sam_grid(m, pilk::kThreads, ctx->n_cu * 8), pilk::kThreads, s,
+                     (const int32_t*)(A.a_mapq + base), dv, m, A.a_mapq + base, A.a_mapq_ok + base));
     }
     base += m;
   }
@@ -737,8 +729,8 @@ bqsr_status bqsr_arrow_pileup_columns(bqsr_context* ctx, bqsr_arrow* a, const bq
 }
 
 bqsr_status bqsr_pileup_kernel_times(double* count_ms, double* emit_ms) {
-  if (count_ms) *count_ms = g_pileup_ms[0];
-  if (emit_ms) *emit_ms = g_pileup_ms[1];
+  if (count_ms) *count_ms = g_pileup_ms[PILEUP_COUNT];
+  if (emit_ms) *emit_ms = g_pileup_ms[PILEUP_EMIT];
   return BQSR_OK;
 }
 

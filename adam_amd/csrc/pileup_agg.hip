@@ -501,7 +501,7 @@ struct bqsr_pileup_agg {
   pagk::Out O{};
   std::vector<void*> result;
   unsigned long long* err = nullptr;  // the grouping error word, the six key statistics, the fold error word
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  StageClock<5> clock;  // (AGG_MARKS below)
   void drop_result() {
     for (void* p : result) (void)hipFree(p);
     result.clear();
@@ -515,8 +515,6 @@ struct bqsr_pileup_agg {
     for (void** p : columns())
       if (*p) (void)hipFree(*p);
     if (err) (void)hipFree(err);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
   }
   std::array<void**, 17> columns() {
     return {(void**)&R.reference_id, (void**)&R.position,       (void**)&R.range_offset, (void**)&R.range_length,
@@ -532,8 +530,12 @@ namespace {
 constexpr size_t kAggWidth[17] = {4, 8, 4, 4, 1, 1, 4, 4, 4, 4, 4, 8, 8, 4, 4, 4, 2};
 constexpr int64_t kAggMaxRows = 2147483647LL;
 
-// keys, sort, scans, emit of the calling thread's last run
-thread_local double g_agg_ms[4] = {0.0, 0.0, 0.0, 0.0};
+// the stages of the calling thread's last run (aggregate_pileups.KERNELS): stage k lies between marks k and k + 1
+enum { AGG_KEYS, AGG_SORT, AGG_SCANS, AGG_EMIT, AGG_STAGES };
+// the clock's marks: each between two ends one stage and starts the next
+enum { AGG_KEYS_0, AGG_SORT_0, AGG_SCANS_0, AGG_EMIT_0, AGG_EMIT_1, AGG_MARKS };
+static_assert(AGG_MARKS == 5, "bqsr_pileup_agg::clock holds AGG_MARKS marks");
+thread_local double g_agg_ms[AGG_STAGES] = {0.0, 0.0, 0.0, 0.0};
 
 // room for `more` rows after the handle's: the columns grow by doubling, the rows kept
 bqsr_status agg_reserve(bqsr_pileup_agg* h, int64_t more, hipStream_t s, const char* who) {
@@ -616,13 +618,11 @@ bqsr_status agg_add_reads(bqsr_context* ctx, bqsr_pileup_agg* h, PileupState& A,
   C.v_mapq = words + 3 * W;
   pilk::EmitParams P{V.R, A.X, A.rs, A.r0, A.n, m, C};
   const int64_t groups = (m + 63) / 64;
-  hipLaunchKernelGGL(pilk::pileup_emit, dim3(pileup_grid(ctx, (groups + pilk::kWaves - 1) / pilk::kWaves)),
-                     dim3(pilk::kThreads), 0, s, P);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(pilk::pileup_emit, pileup_grid(ctx, (groups + pilk::kWaves - 1) / pilk::kWaves), pilk::kThreads, s,
+                 P));
   pagk::PackReads Q{h->R, b, m, A.r0, name_base, read, words, words + W, words + 2 * W, words + 3 * W, ref_id, d_sample, d_rg};
-  hipLaunchKernelGGL(pagk::agg_pack_reads, dim3(pileup_grid(ctx, (m + pagk::kThreads - 1) / pagk::kThreads)),
-                     dim3(pagk::kThreads), 0, s, Q);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(pagk::agg_pack_reads, pileup_grid(ctx, (m + pagk::kThreads - 1) / pagk::kThreads), pagk::kThreads, s,
+                 Q));
   HIP_TRY(hipStreamSynchronize(s));  // (the temporaries go)
   h->n += m;
   return ok();
@@ -640,7 +640,6 @@ bqsr_status bqsr_pileup_agg_create(bqsr_context* ctx, bqsr_pileup_agg** out) {
   if (!h) return fail(BQSR_ERR_DEVICE, "bqsr_pileup_agg_create: out of memory");
   h->ctx = ctx;
   HIP_TRY(hipMalloc((void**)&h->err, 8 * 8));
-  for (int k = 0; k < 5; ++k) HIP_TRY(hipEventCreate(&h->ev[k]));
   *out = h.release();
   return ok();
 }
@@ -690,9 +689,8 @@ bqsr_status bqsr_pileup_agg_add_host(bqsr_pileup_agg* h, const bqsr_pileup_agg_r
       P.bm[k] = dv;
     }
   }
-  hipLaunchKernelGGL(pagk::agg_pack_host, dim3(pileup_grid(h->ctx, (m + pagk::kThreads - 1) / pagk::kThreads)),
-                     dim3(pagk::kThreads), 0, s, P);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(pagk::agg_pack_host, pileup_grid(h->ctx, (m + pagk::kThreads - 1) / pagk::kThreads), pagk::kThreads, s,
+                 P));
   HIP_TRY(hipStreamSynchronize(s));  // (the staged bitmaps go, the caller's buffers are free)
   h->n += m;
   return ok();
@@ -753,11 +751,10 @@ bqsr_status bqsr_pileup_agg_run(bqsr_pileup_agg* h, void* stream, bqsr_pileup_ag
   // keys
   unsigned long long init[8] = {~0ull, 0, 0, 0, ~0ull, ~0ull, ~0ull, ~0ull}, st[8];
   HIP_TRY(hipMemcpyAsync(h->err, init, sizeof init, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipEventRecord(h->ev[0], s));
-  hipLaunchKernelGGL(pagk::agg_keys, dim3(grid), dim3(pagk::kThreads), 0, s,
-                     pagk::KeysParams{h->R, n, minor, h->err, h->err + 7, h->err + 1});
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev[1], s));
+  HIP_TRY(h->clock.mark(AGG_KEYS_0, s));
+  JOB_TRY(launch(pagk::agg_keys, grid, pagk::kThreads, s, pagk::KeysParams{h->R, n, minor, h->err, h->err + 7,
+                 h->err + 1}));
+  HIP_TRY(h->clock.mark(AGG_SORT_0, s));
   HIP_TRY(hipMemcpyAsync(st, h->err, sizeof st, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (st[0] != ~0ull) {
@@ -778,19 +775,16 @@ bqsr_status bqsr_pileup_agg_run(bqsr_pileup_agg* h, void* stream, bqsr_pileup_ag
   for (int which = 0; which < 3; ++which) {
     const int bits = bits_of((uint64_t)(st[1 + which] ^ st[4 + which]));
     if (which && !bits) continue;
-    hipLaunchKernelGGL(pagk::agg_sort_key, dim3(grid), dim3(pagk::kThreads), 0, s, h->R, (const uint64_t*)minor, which,
-                       (const uint32_t*)cur, n, key_a, src);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(pagk::agg_sort_key, grid, pagk::kThreads, s, h->R, minor, which, cur, n, key_a, src));
     size_t tb2 = tb;
     HIP_TRY(rocprim::radix_sort_pairs(temp, tb2, key_a, key_b, src, dst, N, 0, std::max(1, bits), s));
     cur = dst;
     std::swap(src, dst);
   }
   const uint32_t* order = cur;  // == idx_b
-  HIP_TRY(hipEventRecord(h->ev[2], s));
+  HIP_TRY(h->clock.mark(AGG_SCANS_0, s));
   // heads, scan 1 pass 1, the number of groups
-  hipLaunchKernelGGL(pagk::agg_heads, dim3(grid), dim3(pagk::kThreads), 0, s, h->R, (const uint64_t*)minor, order, n,
-                     flags);
+  JOB_TRY(launch(pagk::agg_heads, grid, pagk::kThreads, s, h->R, minor, order, n, flags));
   pagk::ScanParams P{};
   P.R = h->R;
   P.order = order;
@@ -801,9 +795,8 @@ bqsr_status bqsr_pileup_agg_run(bqsr_pileup_agg* h, void* stream, bqsr_pileup_ag
   P.agg2 = agg2;
   P.row = (uint2*)key_a;
   P.err = h->err + 7;
-  hipLaunchKernelGGL(pagk::agg_scan1_tiles, dim3(grid), dim3(pagk::kThreads), 0, s, P);
-  hipLaunchKernelGGL(pagk::agg_top1, dim3(1), dim3(pagk::kTopThreads), 0, s, agg1, n_tiles);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(pagk::agg_scan1_tiles, grid, pagk::kThreads, s, P));
+  JOB_TRY(launch(pagk::agg_top1, 1, pagk::kTopThreads, s, agg1, n_tiles));
   pagk::S1 last;
   HIP_TRY(hipMemcpyAsync(&last, agg1 + (n_tiles - 1), sizeof last, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -830,28 +823,24 @@ bqsr_status bqsr_pileup_agg_run(bqsr_pileup_agg* h, void* stream, bqsr_pileup_ag
     if ((e = sam_alloc(keep, &O.v[k], W)) != BQSR_OK) return e;
   const uint32_t n32 = (uint32_t)n;
   HIP_TRY(hipMemcpyAsync(Gr.offsets + G, &n32, 4, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(pagk::agg_scan1_rows, dim3(grid), dim3(pagk::kThreads), 0, s, P);
-  hipLaunchKernelGGL(pagk::agg_top2, dim3(1), dim3(pagk::kTopThreads), 0, s, agg2, n_tiles);
-  hipLaunchKernelGGL(pagk::agg_scan2_rows, dim3(grid), dim3(pagk::kThreads), 0, s, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev[3], s));
+  JOB_TRY(launch(pagk::agg_scan1_rows, grid, pagk::kThreads, s, P));
+  JOB_TRY(launch(pagk::agg_top2, 1, pagk::kTopThreads, s, agg2, n_tiles));
+  JOB_TRY(launch(pagk::agg_scan2_rows, grid, pagk::kThreads, s, P));
+  HIP_TRY(h->clock.mark(AGG_EMIT_0, s));
   const int64_t words = (G + 63) / 64;
-  hipLaunchKernelGGL(pagk::agg_emit, dim3(pileup_grid(ctx, (words + pagk::kWaves - 1) / pagk::kWaves)),
-                     dim3(pagk::kThreads), 0, s, pagk::EmitParams{h->R, order, Gr, G, O, h->err + 7});
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev[4], s));
+  JOB_TRY(launch(pagk::agg_emit, pileup_grid(ctx, (words + pagk::kWaves - 1) / pagk::kWaves), pagk::kThreads, s,
+                 pagk::EmitParams{h->R, order, Gr, G, O, h->err + 7}));
+  HIP_TRY(h->clock.mark(AGG_EMIT_1, s));
   int32_t* names;
   if ((e = sam_alloc(keep, &names, N)) != BQSR_OK) return e;
-  hipLaunchKernelGGL(pagk::agg_names, dim3(grid), dim3(pagk::kThreads), 0, s, (const int32_t*)h->R.name, order, n,
-                     names);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(pagk::agg_names, grid, pagk::kThreads, s, h->R.name, order, n, names));
   unsigned long long ew = ~0ull;
   HIP_TRY(hipMemcpyAsync(&ew, h->err + 7, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  for (int k = 0; k < 4; ++k) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]) == hipSuccess) g_agg_ms[k] = ms;
-  }
+  h->clock.add(g_agg_ms[AGG_KEYS], AGG_KEYS_0, AGG_SORT_0);
+  h->clock.add(g_agg_ms[AGG_SORT], AGG_SORT_0, AGG_SCANS_0);
+  h->clock.add(g_agg_ms[AGG_SCANS], AGG_SCANS_0, AGG_EMIT_0);
+  h->clock.add(g_agg_ms[AGG_EMIT], AGG_EMIT_0, AGG_EMIT_1);
   if (ew != ~0ull) {
     h->drop_result();
     return agg_error(ew, who);
@@ -910,10 +899,10 @@ bqsr_status bqsr_pileup_agg_fetch(bqsr_pileup_agg* h, const bqsr_pileup_agg_host
 }
 
 bqsr_status bqsr_pileup_agg_kernel_times(double* keys_ms, double* sort_ms, double* scans_ms, double* emit_ms) {
-  if (keys_ms) *keys_ms = g_agg_ms[0];
-  if (sort_ms) *sort_ms = g_agg_ms[1];
-  if (scans_ms) *scans_ms = g_agg_ms[2];
-  if (emit_ms) *emit_ms = g_agg_ms[3];
+  if (keys_ms) *keys_ms = g_agg_ms[AGG_KEYS];
+  if (sort_ms) *sort_ms = g_agg_ms[AGG_SORT];
+  if (scans_ms) *scans_ms = g_agg_ms[AGG_SCANS];
+  if (emit_ms) *emit_ms = g_agg_ms[AGG_EMIT];
   return BQSR_OK;
 }
 

@@ -309,15 +309,14 @@ struct RtState {
   std::vector<int64_t> t_start, t_end;
   bqsr_realign_targets_sizes sizes{0, 0, 0, 0, 0, 0};
   bool prepared = false;
-  hipEvent_t ev[8] = {};
-  ~RtState() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  StageClock<8> clock;
 };
 
-// count, emit, sort, rods, candidates, fold (host), sets: the calling thread's last prepare
-thread_local double g_realign_ms[7] = {0, 0, 0, 0, 0, 0, 0};
+// the stages of the calling thread's last prepare (realignment_targets.KERNELS; the fold is timed on the host),
+// and the clock's marks: count's end starts emit, emit's end sort, sort's end rods, rods' end candidates
+enum { RT_COUNT, RT_EMIT, RT_SORT, RT_RODS, RT_CANDIDATES, RT_FOLD_HOST, RT_SETS, RT_STAGES };
+enum { RT_COUNT_0, RT_EMIT_0, RT_SORT_0, RT_RODS_0, RT_CANDIDATES_0, RT_CANDIDATES_1, RT_SETS_0, RT_SETS_1 };
+thread_local double g_realign_ms[RT_STAGES] = {0, 0, 0, 0, 0, 0, 0};
 
 // joinTargets over singleton sets, left to right over the candidates in their
 // declared order: the running last target a = (as, ae), the next candidate b
@@ -357,8 +356,6 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   A.t_end.clear();
   *out = A.sizes;
   for (double& t : g_realign_ms) t = 0.0;
-  for (hipEvent_t& e : A.ev)
-    if (!e) HIP_TRY(hipEventCreate(&e));
   const int64_t n = V.n_reads;
   if (n > (int64_t)INT32_MAX)
     return fail(BQSR_ERR_UNSUPPORTED, "realignment_targets: more than 2^31 - 1 reads in one job");
@@ -368,8 +365,13 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
     return ok();
   };
   if (n == 0) return done();
+  // emit, sort and rods, read after a synchronize that follows the mark at rods' end
+  auto upto_rods = [&]() {
+    A.clock.add(g_realign_ms[RT_EMIT], RT_EMIT_0, RT_SORT_0);
+    A.clock.add(g_realign_ms[RT_SORT], RT_SORT_0, RT_RODS_0);
+    A.clock.add(g_realign_ms[RT_RODS], RT_RODS_0, RT_CANDIDATES_0);
+  };
   bqsr_status e;
-  float ms = 0.f;
   auto need = [](DevBuf& b, auto** p, size_t count, const char* what) {
     return dev_need(b, p, count, "realignment_targets", what);
   };
@@ -390,10 +392,9 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   HIP_TRY(hipMemsetAsync(small + 1, 0, 8, s));
   HIP_TRY(hipMemsetAsync(X.cnt + n, 0, 8, s));
   CountParams C{pilk::CountParams{V.R, X, 0, n, small}, small + 1};
-  HIP_TRY(hipEventRecord(A.ev[0], s));
-  hipLaunchKernelGGL(rt_count, dim3(grid(n)), dim3(kThreads), 0, s, C);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[1], s));
+  HIP_TRY(A.clock.mark(RT_COUNT_0, s));
+  JOB_TRY(launch(rt_count, grid(n), kThreads, s, C));
+  HIP_TRY(A.clock.mark(RT_EMIT_0, s));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, X.cnt, rs, (uint64_t)0, N + 1, rocprim::plus<uint64_t>(), s);
        })))
@@ -403,7 +404,7 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   HIP_TRY(hipMemcpyAsync(st2, small, 16, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&total, rs + n, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (hipEventElapsedTime(&ms, A.ev[0], A.ev[1]) == hipSuccess) g_realign_ms[0] = ms;
+  A.clock.add(g_realign_ms[RT_COUNT], RT_COUNT_0, RT_EMIT_0);
   if (st2[0] != ~0ull) {
     const int status = (int)(st2[0] & 0xFF);
     const int64_t read = (int64_t)(st2[0] >> 8);
@@ -427,23 +428,20 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
       (e = need(A.val_a, &val_a, M + 2, "pileup rows")) || (e = need(A.val_b, &val_b, M, "pileup rows")))
     return e;
   EmitParams E{V.R, X, rs, n, m, key_a, val_a};
-  hipLaunchKernelGGL(rt_emit, dim3(grid(m)), dim3(kThreads), 0, s, E);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[2], s));
+  JOB_TRY(launch(rt_emit, grid(m), kThreads, s, E));
+  HIP_TRY(A.clock.mark(RT_SORT_0, s));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::radix_sort_pairs(t, b, key_a, key_b, val_a, val_b, M, 0, (unsigned)pos_bits, s);
        })))
     return e;
-  HIP_TRY(hipEventRecord(A.ev[3], s));
+  HIP_TRY(A.clock.mark(RT_RODS_0, s));
   // ---- rods (the sort's spare halves hold the per-row words) ----
   uint64_t* q = key_a;                         // [M]
   uint32_t* head = (uint32_t*)val_a;           // [M + 2]; later the event flags
   uint32_t* rod1 = (uint32_t*)val_a + (M + 2);  // [M + 2]
   uint32_t* evoff;
   if ((e = need(A.evoff, &evoff, M + 1, "pileup rows"))) return e;
-  hipLaunchKernelGGL(rt_heads, dim3(grid(m)), dim3(kThreads), 0, s, (const uint64_t*)key_b,
-                     (const uint64_t*)val_b, m, head, q);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(rt_heads, grid(m), kThreads, s, key_b, val_b, m, head, q));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::inclusive_scan(t, b, head, rod1, M, rocprim::plus<uint32_t>(), s);
        })))
@@ -460,9 +458,7 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
        })))
     return e;
   uint32_t* isev = head;
-  hipLaunchKernelGGL(rt_evflag, dim3(grid(m)), dim3(kThreads), 0, s, (const uint64_t*)val_b,
-                     (const uint32_t*)rod1, (const uint64_t*)rodq, m, isev);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(rt_evflag, grid(m), kThreads, s, val_b, rod1, rodq, m, isev));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, isev, evoff, (uint32_t)0, M + 1, rocprim::plus<uint32_t>(), s);
        })))
@@ -473,11 +469,9 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   const int64_t n_ev = n_ev32;
   const size_t NE = (size_t)n_ev;
   if (n_ev == 0) {
-    HIP_TRY(hipEventRecord(A.ev[4], s));
+    HIP_TRY(A.clock.mark(RT_CANDIDATES_0, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (hipEventElapsedTime(&ms, A.ev[1], A.ev[2]) == hipSuccess) g_realign_ms[1] = ms;
-    if (hipEventElapsedTime(&ms, A.ev[2], A.ev[3]) == hipSuccess) g_realign_ms[2] = ms;
-    if (hipEventElapsedTime(&ms, A.ev[3], A.ev[4]) == hipSuccess) g_realign_ms[3] = ms;
+    upto_rods();
     return done();
   }
   Ev *ev_a, *ev_b, *hull;
@@ -486,9 +480,8 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
       (e = need(A.hull, &hull, NE, "events")) || (e = need(A.candrod, &candrod, NE + 1, "events")))
     return e;
   EventParams EP{V.R, X, key_b, val_b, rod1, isev, evoff, m, ev_a};
-  hipLaunchKernelGGL(rt_events, dim3(grid(m)), dim3(kThreads), 0, s, EP);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[4], s));
+  JOB_TRY(launch(rt_events, grid(m), kThreads, s, EP));
+  HIP_TRY(A.clock.mark(RT_CANDIDATES_0, s));
   // ---- candidates: the rods with events, their hulls, ascending by (start, position) ----
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::reduce_by_key(t, b, rocprim::make_transform_iterator((const Ev*)ev_a, RodOf()), (const Ev*)ev_a,
@@ -508,17 +501,13 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
       (e = need(A.cend, &cend, NC, "candidates")) || (e = need(A.tid, &tid, NC, "candidates")) ||
       (e = need(A.multi, &multi, NC, "candidates")) || (e = need(A.rod2t, &rod2t, NR, "rods")))
     return e;
-  hipLaunchKernelGGL(rt_candkeys, dim3(grid(n_cand)), dim3(kThreads), 0, s, (const Ev*)hull, n_cand, ckey_a,
-                     cval_a);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(rt_candkeys, grid(n_cand), kThreads, s, hull, n_cand, ckey_a, cval_a));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::radix_sort_pairs(t, b, ckey_a, ckey_b, cval_a, cval_b, NC, 0, (unsigned)pos_bits, s);
        })))
     return e;
-  hipLaunchKernelGGL(rt_gather, dim3(grid(n_cand)), dim3(kThreads), 0, s, (const Ev*)hull,
-                     (const uint32_t*)cval_b, n_cand, cend);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[5], s));
+  JOB_TRY(launch(rt_gather, grid(n_cand), kThreads, s, hull, cval_b, n_cand, cend));
+  HIP_TRY(A.clock.mark(RT_CANDIDATES_1, s));
   std::vector<uint64_t> h_start(NC);
   std::vector<int64_t> h_end(NC);
   std::vector<uint32_t> h_tid(NC);
@@ -529,17 +518,14 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
   // ---- the fold ----
   const auto f0 = std::chrono::steady_clock::now();
   rt_fold(h_start, h_end, h_tid, A.t_start, A.t_end, h_multi);
-  g_realign_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+  g_realign_ms[RT_FOLD_HOST] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
   const int64_t n_t = (int64_t)A.t_start.size();
   HIP_TRY(hipMemcpyAsync(tid, h_tid.data(), NC * 4, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(multi, h_multi.data(), (size_t)n_t, hipMemcpyHostToDevice, s));
   // ---- the sets of every target ----
-  HIP_TRY(hipEventRecord(A.ev[6], s));
-  hipLaunchKernelGGL(rt_rod2t, dim3(grid(n_cand)), dim3(kThreads), 0, s, (const int64_t*)candrod,
-                     (const uint32_t*)cval_b, (const uint32_t*)tid, n_cand, rod2t);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(rt_retarget, dim3(grid(n_ev)), dim3(kThreads), 0, s, ev_a, n_ev, (const uint32_t*)rod2t);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(A.clock.mark(RT_SETS_0, s));
+  JOB_TRY(launch(rt_rod2t, grid(n_cand), kThreads, s, candrod, cval_b, tid, n_cand, rod2t));
+  JOB_TRY(launch(rt_retarget, grid(n_ev), kThreads, s, ev_a, n_ev, rod2t));
   if ((e = prim([&](void* t, size_t& b) { return rocprim::merge_sort(t, b, ev_a, ev_b, NE, EvLess(), s); })))
     return e;
   // (ev_a is free: the unique keys go there; hull takes the survivors, candrod's last word their count)
@@ -559,27 +545,20 @@ bqsr_status rt_prepare(bqsr_context* ctx, RtState& A, const PileupView& V, hipSt
     return e;
   A.D = Result{res, res + NO, res + 2 * NO, res + 3 * NO, res + 4 * NO, res + 5 * NO, res + 6 * NO, res + 7 * NO,
                res + 7 * NO + NT + 1};
-  hipLaunchKernelGGL(rt_isindel, dim3(grid(n_out)), dim3(kThreads), 0, s, (const Ev*)hull, n_out, isi);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(rt_isindel, grid(n_out), kThreads, s, hull, n_out, isi));
   if ((e = prim([&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, isi, islot, (uint32_t)0, NO + 1, rocprim::plus<uint32_t>(), s);
        })))
     return e;
-  hipLaunchKernelGGL(rt_write, dim3(grid(n_out)), dim3(kThreads), 0, s, (const Ev*)hull, (const uint32_t*)islot,
-                     n_out, A.D);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(rt_offsets, dim3(grid(n_t + 1)), dim3(kThreads), 0, s, (const Ev*)hull,
-                     (const uint32_t*)islot, n_out, n_t, A.D);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(A.ev[7], s));
+  JOB_TRY(launch(rt_write, grid(n_out), kThreads, s, hull, islot, n_out, A.D));
+  JOB_TRY(launch(rt_offsets, grid(n_t + 1), kThreads, s, hull, islot, n_out, n_t, A.D));
+  HIP_TRY(A.clock.mark(RT_SETS_1, s));
   uint32_t n_indels = 0;
   HIP_TRY(hipMemcpyAsync(&n_indels, islot + n_out, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (hipEventElapsedTime(&ms, A.ev[1], A.ev[2]) == hipSuccess) g_realign_ms[1] = ms;
-  if (hipEventElapsedTime(&ms, A.ev[2], A.ev[3]) == hipSuccess) g_realign_ms[2] = ms;
-  if (hipEventElapsedTime(&ms, A.ev[3], A.ev[4]) == hipSuccess) g_realign_ms[3] = ms;
-  if (hipEventElapsedTime(&ms, A.ev[4], A.ev[5]) == hipSuccess) g_realign_ms[4] = ms;
-  if (hipEventElapsedTime(&ms, A.ev[6], A.ev[7]) == hipSuccess) g_realign_ms[6] = ms;
+  upto_rods();
+  A.clock.add(g_realign_ms[RT_CANDIDATES], RT_CANDIDATES_0, RT_CANDIDATES_1);
+  A.clock.add(g_realign_ms[RT_SETS], RT_SETS_0, RT_SETS_1);
   A.sizes.n_candidates = n_cand;
   A.sizes.n_targets = n_t;
   A.sizes.n_indels = n_indels;
@@ -655,7 +634,7 @@ bqsr_status bqsr_arrow_realign_targets_fetch(bqsr_context* ctx, bqsr_arrow* a, c
 
 bqsr_status bqsr_realign_targets_kernel_times(double* ms7) {
   if (!ms7) return fail(BQSR_ERR_INVALID_ARG, "bqsr_realign_targets_kernel_times: null");
-  for (int k = 0; k < 7; ++k) ms7[k] = g_realign_ms[k];
+  for (int k = 0; k < RT_STAGES; ++k) ms7[k] = g_realign_ms[k];
   return BQSR_OK;
 }
 

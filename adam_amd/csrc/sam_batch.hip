@@ -224,10 +224,8 @@ bqsr_status pack_batch_device(bqsr_context* ctx, const PackCols& C, const int32_
   HIP_TRY(hipMemsetAsync(span + n, 0, 8, st));
   const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)ctx->n_cu * 16));
   if (n) {
-    hipLaunchKernelGGL(sam_batch_spans, dim3(g), dim3(kThreads), 0, st, (const uint32_t*)s->flags,
-                       (const int32_t*)s->rg_id, (const uint64_t*)s->seq_off, (const uint64_t*)s->qual_off,
-                       (const uint64_t*)s->cig_off, (const uint64_t*)s->md_off, n, span, dl);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(sam_batch_spans, g, kThreads, st, s->flags, s->rg_id, s->seq_off, s->qual_off, s->cig_off, s->md_off,
+                   n, span, dl));
   }
   if ((e = with_temp(tmp, [&](void* t, size_t& b) {
          return rocprim::exclusive_scan(t, b, span, slot, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st);
@@ -263,17 +261,13 @@ bqsr_status pack_batch_device(bqsr_context* ctx, const PackCols& C, const int32_
   if (s->cig_ops) HIP_TRY(hipMemcpyAsync(cigar, s->cig, (size_t)s->cig_ops * 4, hipMemcpyDeviceToDevice, st));
   if (n) {
     const unsigned gw = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)ctx->n_cu * 8));
-    hipLaunchKernelGGL(sam_batch_pack, dim3(gw), dim3(kThreads), 0, st, (const uint32_t*)s->flags,
-                       (const int32_t*)s->rg_id, (const int32_t*)s->ref, (const int64_t*)s->start,
-                       (const uint64_t*)s->seq_off, (const uint8_t*)s->seq, (const uint64_t*)s->qual_off,
-                       (const uint8_t*)s->qual, (const uint64_t*)s->cig_off, (const uint64_t*)s->md_off,
-                       (const int32_t*)d_map, n_ref, (const uint64_t*)slot, n, meta, align, qual, bases, rgh, n_rgh);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(sam_batch_pack, gw, kThreads, st, s->flags, s->rg_id, s->ref, s->start, s->seq_off, s->seq,
+                   s->qual_off, s->qual, s->cig_off, s->md_off, d_map, n_ref, slot, n, meta, align, qual, bases, rgh,
+                   n_rgh));
     const int64_t n16 = (int64_t)n_slots / 16;  // (16-aligned slots: the column's whole slot range)
     const unsigned gh = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n16 + kHistThreads - 1) / kHistThreads,
                                                                           (int64_t)ctx->n_cu * 2));
-    hipLaunchKernelGGL(sam_batch_qhist, dim3(gh), dim3(kHistThreads), 0, st, (const uint4*)qual, n16, qh);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(sam_batch_qhist, gh, kHistThreads, st, (const uint4*)qual, n16, qh));
   }
   std::vector<unsigned long long> hq(256), hrg((size_t)n_rgh);
   HIP_TRY(hipMemcpyAsync(hq.data(), qh, 256 * 8, hipMemcpyDeviceToHost, st));

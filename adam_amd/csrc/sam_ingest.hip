@@ -971,11 +971,9 @@ bqsr_status sam_names_upload(std::vector<void*>& keep, const HostNames& h, samk:
 // exclusive scan of n u64 into out[0..n]
 bqsr_status sam_scan(const uint64_t* in, int64_t n, uint64_t* out, uint64_t* part, hipStream_t s) {
   const int64_t nb = std::max<int64_t>(1, (n + samk::kScanChunk - 1) / samk::kScanChunk);
-  hipLaunchKernelGGL(samk::scan_partials, dim3((unsigned)nb), dim3(samk::kScanThreads), 0, s, in, n, part);
-  hipLaunchKernelGGL(samk::scan_top, dim3(1), dim3(1024), 0, s, part, nb);
-  hipLaunchKernelGGL(samk::scan_apply, dim3((unsigned)nb), dim3(samk::kScanThreads), 0, s, in, n, (const uint64_t*)part,
-                     out);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(samk::scan_partials, (unsigned)nb, samk::kScanThreads, s, in, n, part));
+  JOB_TRY(launch(samk::scan_top, 1, 1024, s, part, nb));
+  JOB_TRY(launch(samk::scan_apply, (unsigned)nb, samk::kScanThreads, s, in, n, part, out));
   return BQSR_OK;
 }
 const char* kSamErrors[] = {"ok", "fewer than 11 fields", "optional field without two ':'", "FLAG is not an integer",
@@ -1113,17 +1111,14 @@ bqsr_status sam_parse_device(bqsr_context* ctx, SamHeader& H, const char* header
   const int64_t nb = std::max<int64_t>(1, (n - body + samk::kNlChunk - 1) / samk::kNlChunk);
   uint64_t* cnt;
   if ((st = sam_alloc(tmp, &cnt, (size_t)nb + 1)) != BQSR_OK) return st;
-  hipLaunchKernelGGL(samk::sam_nl_count, dim3((unsigned)nb), dim3(samk::kNlThreads), 0, s, (const uint8_t*)o->d_text,
-                     body, n, cnt);
-  hipLaunchKernelGGL(samk::scan_top, dim3(1), dim3(1024), 0, s, cnt, nb);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(samk::sam_nl_count, (unsigned)nb, samk::kNlThreads, s, o->d_text, body, n, cnt));
+  JOB_TRY(launch(samk::scan_top, 1, 1024, s, cnt, nb));
   uint64_t n_nl = 0;
   HIP_TRY(hipMemcpyAsync(&n_nl, cnt + nb, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   uint64_t* nl;
   if ((st = sam_alloc(tmp, &nl, (size_t)n_nl)) != BQSR_OK) return st;
-  hipLaunchKernelGGL(samk::sam_nl_write, dim3((unsigned)nb), dim3(samk::kNlThreads), 0, s, (const uint8_t*)o->d_text,
-                     body, n, (const uint64_t*)cnt, nl);
+  JOB_TRY(launch(samk::sam_nl_write, (unsigned)nb, samk::kNlThreads, s, o->d_text, body, n, cnt, nl));
   P.nl = nl;
   P.n_nl = (int64_t)n_nl;
   const int64_t L = n > body ? (int64_t)n_nl + 1 : 0;  // the last "line" may be empty
@@ -1136,8 +1131,7 @@ bqsr_status sam_parse_device(bqsr_context* ctx, SamHeader& H, const char* header
   if ((st = sam_alloc(tmp, &P.len, (size_t)(5 * L))) != BQSR_OK) return st;
   if ((st = sam_alloc(tmp, &P.off, (size_t)(5 * (L + 1)))) != BQSR_OK) return st;
   const unsigned lg = sam_grid(L, 256, ctx->n_cu * 16);  // sam_lines_write: whole wavefronts per stride step
-  if (L > 0) hipLaunchKernelGGL(samk::sam_lines_len, dim3(lg), dim3(256), 0, s, P);
-  HIP_TRY(hipGetLastError());
+  if (L > 0) JOB_TRY(launch(samk::sam_lines_len, lg, 256, s, P));
   unsigned long long e_word = ~0ull;
   HIP_TRY(hipMemcpyAsync(&e_word, err, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1199,15 +1193,14 @@ bqsr_status sam_parse_device(bqsr_context* ctx, SamHeader& H, const char* header
   P.qual_span = o->qual_span;
   // ---- pass 2: the columns ----
   if (L > 0) {
-    hipLaunchKernelGGL(samk::sam_lines_write, dim3(lg), dim3(256), 0, s, P);
-    hipLaunchKernelGGL(samk::sam_offsets_close, dim3(1), dim3(1), 0, s, P, o->n_reads);
+    JOB_TRY(launch(samk::sam_lines_write, lg, 256, s, P));
+    JOB_TRY(launch(samk::sam_offsets_close, 1, 1, s, P, o->n_reads));
   } else {
     HIP_TRY(hipMemsetAsync(o->seq_off, 0, 8, s));
     HIP_TRY(hipMemsetAsync(o->qual_off, 0, 8, s));
     HIP_TRY(hipMemsetAsync(o->cig_off, 0, 8, s));
     HIP_TRY(hipMemsetAsync(o->md_off, 0, 8, s));
   }
-  HIP_TRY(hipGetLastError());
   // ---- referenceName ids: first appearance order ----
   const size_t nsq = sq_names.size();
   if (nsq > 0 && nr > 0) {
@@ -1216,7 +1209,7 @@ bqsr_status sam_parse_device(bqsr_context* ctx, SamHeader& H, const char* header
     if ((st = sam_alloc(tmp, &first, nsq)) != BQSR_OK) return st;
     HIP_TRY(hipMemsetAsync(first, 0xFF, nsq * 8, s));
     const unsigned rgd = sam_grid((int64_t)nr, 256, ctx->n_cu * 16);
-    hipLaunchKernelGGL(samk::sam_ref_first, dim3(rgd), dim3(256), 0, s, (const int32_t*)o->ref, (int64_t)nr, first);
+    JOB_TRY(launch(samk::sam_ref_first, rgd, 256, s, o->ref, (int64_t)nr, first));
     std::vector<unsigned long long> fh(nsq);
     HIP_TRY(hipMemcpyAsync(fh.data(), first, nsq * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1230,8 +1223,7 @@ bqsr_status sam_parse_device(bqsr_context* ctx, SamHeader& H, const char* header
       o->ref_names.push_back(sq_names[order[k]]);
     }
     if ((st = sam_upload(tmp, &rank_d, rank, s)) != BQSR_OK) return st;
-    hipLaunchKernelGGL(samk::sam_ref_remap, dim3(rgd), dim3(256), 0, s, o->ref, (int64_t)nr, (const int32_t*)rank_d);
-    HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(samk::sam_ref_remap, rgd, 256, s, o->ref, (int64_t)nr, rank_d));
   }
   HIP_TRY(hipStreamSynchronize(s));
   *out = S_.release();
@@ -1350,7 +1342,7 @@ bqsr_status bqsr_sam_rewrite_quals(bqsr_context* ctx, bqsr_sam* sm, const bqsr_b
   }
   const unsigned g = sam_grid(n, 256, ctx->n_cu * 16);
   if (n > 0 && b)
-    hipLaunchKernelGGL(samk::sam_pass_flags, dim3(g), dim3(256), 0, s, (const ReadInfo*)b->d_info, n, pass);
+    JOB_TRY(launch(samk::sam_pass_flags, g, 256, s, b->d_info, n, pass));
   R.text = sm->d_text;
   R.line_span = sm->line_span;
   R.qual_span = sm->qual_span;
@@ -1368,7 +1360,7 @@ bqsr_status bqsr_sam_rewrite_quals(bqsr_context* ctx, bqsr_sam* sm, const bqsr_b
   R.new_off = new_off;
   R.pass = pass;
   R.span_out = span_out;
-  if (n > 0) hipLaunchKernelGGL(samk::sam_rewrite_len, dim3(g), dim3(256), 0, s, R);
+  if (n > 0) JOB_TRY(launch(samk::sam_rewrite_len, g, 256, s, R));
   if ((st = sam_scan(new_len, n, new_off, part, s)) != BQSR_OK) return st;
   uint64_t body = 0;
   if (n > 0) HIP_TRY(hipMemcpyAsync(&body, new_off + n, 8, hipMemcpyDeviceToHost, s));
@@ -1379,12 +1371,11 @@ bqsr_status bqsr_sam_rewrite_quals(bqsr_context* ctx, bqsr_sam* sm, const bqsr_b
   HIP_TRY(hipMemsetAsync(nt + total, 0, 64, s));
   if (sm->header > 0) HIP_TRY(hipMemcpyAsync(nt, sm->d_text, (size_t)sm->header, hipMemcpyDeviceToDevice, s));
   R.out = nt;
+  hipError_t e = hipSuccess;
   if (n > 0) {
-    hipLaunchKernelGGL(samk::sam_rewrite_write, dim3(g), dim3(256), 0, s, R);
-    hipLaunchKernelGGL(samk::sam_spans_update, dim3(g), dim3(256), 0, s, (const uint64_t*)span_out, n,
-                       sm->line_span, sm->qual_span);
+    e = launch_err(samk::sam_rewrite_write, g, 256, s, R);
+    if (e == hipSuccess) e = launch_err(samk::sam_spans_update, g, 256, s, span_out, n, sm->line_span, sm->qual_span);
   }
-  hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
     (void)hipFree(nt);

@@ -250,8 +250,7 @@ bqsr_status sort_order_device(bqsr_context* ctx, int64_t n, const uint32_t* flag
   HIP_TRY(hipMemsetAsync(st, 0xFF, 16, s));  // first null, first unsupported: none
   HIP_TRY(hipMemsetAsync(st + 2, 0, (sortk::kStatWords - 2) * 8, s));
   const unsigned g = sam_grid(n, sortk::kThreads, ctx->n_cu * 16);
-  hipLaunchKernelGGL(sortk::sort_classify, dim3(g), dim3(sortk::kThreads), 0, s, flags, ref, start, n, unm, st);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(sortk::sort_classify, g, sortk::kThreads, s, flags, ref, start, n, unm, st));
   if ((e = sam_scan(unm, n, before, part, s)) != BQSR_OK) return e;
   unsigned long long h[4] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(h, st, sizeof h, hipMemcpyDeviceToHost, s));
@@ -275,9 +274,7 @@ bqsr_status sort_order_device(bqsr_context* ctx, int64_t n, const uint32_t* flag
   const uint64_t first_unmapped = h[sortk::kMaxRefP1];  // just above the largest mapped referenceId
   const int sb = bits_of(h[sortk::kMaxStartW]);
   const int end_bit = std::max(1, sb + bits_of(first_unmapped + sortk::kWrap - 1));
-  hipLaunchKernelGGL(sortk::sort_keys, dim3(g), dim3(sortk::kThreads), 0, s, flags, ref, start,
-                     (const uint64_t*)before, n, first_unmapped, sb, key, idx);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(sortk::sort_keys, g, sortk::kThreads, s, flags, ref, start, before, n, first_unmapped, sb, key, idx));
   if ((e = with_temp(T.v, [&](void* t, size_t& b) {
          return rocprim::radix_sort_pairs(t, b, key, key2, idx, order, N, 0, end_bit, s);
        })))
@@ -327,9 +324,7 @@ bqsr_status bqsr_sam_sort(bqsr_context* ctx, bqsr_sam* sm, void* stream) {
   HIP_TRY(hipMemsetAsync(st, 0, sortk::kStatWords * 8, s));
   const unsigned g = sam_grid(n, sortk::kThreads, ctx->n_cu * 16);
   if (n > 0)
-    hipLaunchKernelGGL(sortk::sort_lens, dim3(g), dim3(sortk::kThreads), 0, s, (const uint32_t*)order,
-                       (const uint64_t*)sm->line_span, n, len, long_list, st);
-  HIP_TRY(hipGetLastError());
+    JOB_TRY(launch(sortk::sort_lens, g, sortk::kThreads, s, order, sm->line_span, n, len, long_list, st));
   if ((e = sam_scan(len, n, off, part, s)) != BQSR_OK) return e;
   uint64_t body = 0;
   unsigned long long n_long = 0;
@@ -345,16 +340,13 @@ bqsr_status bqsr_sam_sort(bqsr_context* ctx, bqsr_sam* sm, void* stream) {
   if (he == hipSuccess && n > 0) {
     // a wavefront per 64 records: whole workgroups of four
     const unsigned gg = sam_grid((n + 63) / 64 * 64, sortk::kThreads, ctx->n_cu * 8);
-    hipLaunchKernelGGL(sortk::sort_gather, dim3(gg), dim3(sortk::kThreads), 0, s, (const uint8_t*)sm->d_text,
-                       sm->n_text, nt + sm->header, (const uint32_t*)order, (const uint64_t*)sm->line_span,
-                       (const uint64_t*)off, n);
-    if (n_long > 0) {
+    he = launch_err(sortk::sort_gather, gg, sortk::kThreads, s, sm->d_text, sm->n_text, nt + sm->header, order,
+                    sm->line_span, off, n);
+    if (he == hipSuccess && n_long > 0) {
       const unsigned gl = (unsigned)std::min<int64_t>((int64_t)n_long, (int64_t)ctx->n_cu * 8);
-      hipLaunchKernelGGL(sortk::sort_gather_long, dim3(gl), dim3(sortk::kThreads), 0, s, (const uint8_t*)sm->d_text,
-                         sm->n_text, nt + sm->header, (const uint32_t*)order, (const uint64_t*)sm->line_span,
-                         (const uint64_t*)off, (const uint32_t*)long_list, (int64_t)n_long);
+      he = launch_err(sortk::sort_gather_long, gl, sortk::kThreads, s, sm->d_text, sm->n_text, nt + sm->header, order,
+                      sm->line_span, off, long_list, (int64_t)n_long);
     }
-    he = hipGetLastError();
   }
   if (he == hipSuccess) he = hipStreamSynchronize(s);
   if (he != hipSuccess) {

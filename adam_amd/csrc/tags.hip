@@ -495,7 +495,11 @@ extern "C" __global__ void __launch_bounds__(kThreads) tag_value_text(const uint
 
 namespace {
 
-thread_local double g_tags_ms[2] = {0.0, 0.0};  // the scan kernels, the value kernels (with their sorts and scans)
+// the scan kernels of the calling thread's last counts call, the value kernels (with their sorts and scans) of its
+// last values call; either call times its work between the two marks of a clock of its own
+enum { TAGS_SCAN, TAGS_VALUES, TAGS_STAGES };
+thread_local double g_tags_ms[TAGS_STAGES] = {0.0, 0.0};
+typedef StageClock<2> TagClock;
 
 // the runs of the last bqsr_*_tag_values call of this thread
 struct TagRuns {
@@ -510,22 +514,6 @@ struct TagRuns {
   }
 };
 thread_local TagRuns g_tag_runs;
-
-struct TagEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~TagEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  hipError_t make() {
-    const hipError_t e = hipEventCreate(&a);
-    return e != hipSuccess ? e : hipEventCreate(&b);
-  }
-  double ms() const {
-    float v = 0.f;
-    return hipEventElapsedTime(&v, a, b) == hipSuccess ? (double)v : 0.0;
-  }
-};
 
 // at most four workgroups a CU (their LDS tables), or BQSR_TUNE_FLAGSTAT_GRID in all
 unsigned tags_grid(const bqsr_context* ctx, int64_t n) {
@@ -565,11 +553,11 @@ bqsr_status tags_error(unsigned long long w) {
   }
 }
 
-bqsr_status tags_finish(unsigned long long* d, hipStream_t s, TagEvents& ev, bqsr_tag_counts* out) {
+bqsr_status tags_finish(unsigned long long* d, hipStream_t s, TagClock& clock, bqsr_tag_counts* out) {
   std::vector<unsigned long long> h((size_t)tagk::kWords);
   HIP_TRY(hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  g_tags_ms[0] = ev.ms();
+  clock.add(g_tags_ms[TAGS_SCAN], 0, 1);
   if (h[tagk::kErr] != ~0ull) return tags_error(h[tagk::kErr]);
   for (int k = 0; k < tagk::kTable; ++k) out->counts[k] = (int64_t)h[k];
   out->total = (int64_t)h[tagk::kTotal];
@@ -638,8 +626,7 @@ bqsr_status tag_values_run(bqsr_context* ctx, tagk::Values V, hipStream_t s) {
     return e;
   HIP_TRY(hipMemsetAsync(err, 0xFF, 8, s));
   const unsigned g = sam_grid(n, tagk::kThreads, ctx->n_cu * 8);
-  hipLaunchKernelGGL(tagk::tag_value_keys, dim3(g), dim3(tagk::kThreads), 0, s, V, key, has, va, vlen, err);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(tagk::tag_value_keys, g, tagk::kThreads, s, V, key, has, va, vlen, err));
   if ((e = sam_scan(has, n, off, part, s)) != BQSR_OK) return e;
   unsigned long long ew = ~0ull;
   uint64_t m64 = 0;
@@ -655,17 +642,13 @@ bqsr_status tag_values_run(bqsr_context* ctx, tagk::Values V, hipStream_t s) {
   if ((e = sam_alloc(T.v, &ck, M)) || (e = sam_alloc(T.v, &ck2, M)) || (e = sam_alloc(T.v, &ci, M)) ||
       (e = sam_alloc(T.v, &ci2, M)) || (e = sam_alloc(T.v, &head, M)) || (e = sam_alloc(T.v, &rid, M + 1)))
     return e;
-  hipLaunchKernelGGL(tagk::tag_value_compact, dim3(g), dim3(tagk::kThreads), 0, s, (const uint64_t*)key,
-                     (const uint64_t*)has, (const uint64_t*)off, n, ck, ci);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(tagk::tag_value_compact, g, tagk::kThreads, s, key, has, off, n, ck, ci));
   if ((e = with_temp(T.v, [&](void* t, size_t& b) {
          return rocprim::radix_sort_pairs(t, b, ck, ck2, ci, ci2, M, 0, 64, s);
        })))
     return e;
   const unsigned gm = sam_grid(m, tagk::kThreads, ctx->n_cu * 8);
-  hipLaunchKernelGGL(tagk::tag_value_heads, dim3(gm), dim3(tagk::kThreads), 0, s, V.text, (const uint64_t*)ck2,
-                     (const uint32_t*)ci2, (const int64_t*)va, (const uint32_t*)vlen, m, head);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(tagk::tag_value_heads, gm, tagk::kThreads, s, V.text, ck2, ci2, va, vlen, m, head));
   if ((e = sam_scan(head, m, rid, part, s)) != BQSR_OK) return e;
   uint64_t nr64 = 0;
   HIP_TRY(hipMemcpyAsync(&nr64, rid + m, 8, hipMemcpyDeviceToHost, s));
@@ -677,21 +660,15 @@ bqsr_status tag_values_run(bqsr_context* ctx, tagk::Values V, hipStream_t s) {
   if ((e = sam_alloc(T.v, &rpos, R)) || (e = sam_alloc(T.v, &rlen, R)) || (e = sam_alloc(T.v, &toff, R + 1)) ||
       (e = sam_alloc(T.v, &rtype, R)) || (e = sam_alloc(T.v, &rcount, R)) || (e = sam_alloc(T.v, &rfirst, R)))
     return e;
-  hipLaunchKernelGGL(tagk::tag_value_runs, dim3(gm), dim3(tagk::kThreads), 0, s, V.text, (const uint64_t*)ck2,
-                     (const uint32_t*)ci2, (const int64_t*)va, (const uint32_t*)vlen, (const uint64_t*)head,
-                     (const uint64_t*)rid, m, rpos, rlen);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(tagk::tag_value_runs, gm, tagk::kThreads, s, V.text, ck2, ci2, va, vlen, head, rid, m, rpos, rlen));
   if ((e = sam_scan(rlen, nr, toff, part, s)) != BQSR_OK) return e;  // (nr <= m <= n: part is large enough)
   uint64_t tb64 = 0;
   HIP_TRY(hipMemcpyAsync(&tb64, toff + nr, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   uint8_t* d_text;
   if ((e = sam_alloc(T.v, &d_text, (size_t)tb64)) != BQSR_OK) return e;
-  hipLaunchKernelGGL(tagk::tag_value_text, dim3(sam_grid(nr, tagk::kThreads, ctx->n_cu * 8)), dim3(tagk::kThreads), 0,
-                     s, V.text, (const uint64_t*)ck2, (const uint32_t*)ci2, (const int64_t*)va,
-                     (const uint32_t*)vlen, (const uint64_t*)rpos, (const uint64_t*)toff, nr, m, V.C.base, rtype,
-                     rcount, rfirst, d_text);
-  HIP_TRY(hipGetLastError());
+  JOB_TRY(launch(tagk::tag_value_text, sam_grid(nr, tagk::kThreads, ctx->n_cu * 8), tagk::kThreads, s, V.text, ck2, ci2,
+                 va, vlen, rpos, toff, nr, m, V.C.base, rtype, rcount, rfirst, d_text));
   TagRuns& G = g_tag_runs;
   const size_t r0 = G.type.size(), t0 = G.text.size();
   std::vector<uint64_t> ho(R + 1);
@@ -725,22 +702,19 @@ bqsr_status bqsr_sam_tag_counts(bqsr_context* ctx, const bqsr_sam* sm, void* str
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
   memset(out, 0, sizeof *out);
-  g_tags_ms[0] = 0.0;
+  g_tags_ms[TAGS_SCAN] = 0.0;
   const int64_t n = sm->n_reads;
   if (n == 0) return ok();
   SortTmp T;
-  TagEvents ev;
+  TagClock clock;
   unsigned long long* d;
   bqsr_status e;
   if ((e = tags_block(T, &d, s)) != BQSR_OK) return e;
-  HIP_TRY(ev.make());
-  HIP_TRY(hipEventRecord(ev.a, s));
-  hipLaunchKernelGGL(tagk::tags_scan_sam, dim3(tags_grid(ctx, n)), dim3(tagk::kThreads), 0, s,
-                     (const uint8_t*)sm->d_text, (const uint64_t*)sm->line_span, (const uint64_t*)sm->qual_span,
-                     (const uint32_t*)sm->raw_flag, n, d);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev.b, s));
-  return tags_finish(d, s, ev, out);
+  HIP_TRY(clock.mark(0, s));
+  JOB_TRY(launch(tagk::tags_scan_sam, tags_grid(ctx, n), tagk::kThreads, s, sm->d_text, sm->line_span, sm->qual_span,
+                 sm->raw_flag, n, d));
+  HIP_TRY(clock.mark(1, s));
+  return tags_finish(d, s, clock, out);
 }
 
 bqsr_status bqsr_arrow_tag_counts(bqsr_context* ctx, const bqsr_tags_chunk* chunks, int32_t n_chunks, void* stream,
@@ -751,12 +725,11 @@ bqsr_status bqsr_arrow_tag_counts(bqsr_context* ctx, const bqsr_tags_chunk* chun
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
   memset(out, 0, sizeof *out);
-  g_tags_ms[0] = 0.0;
+  g_tags_ms[TAGS_SCAN] = 0.0;
   SortTmp T;
-  TagEvents ev;
+  TagClock clock;
   unsigned long long* d;
   if ((e = tags_block(T, &d, s)) != BQSR_OK) return e;
-  HIP_TRY(ev.make());
   double ms = 0.0;
   int64_t base = 0;
   for (int32_t c = 0; c < n_chunks; ++c) {
@@ -765,18 +738,17 @@ bqsr_status bqsr_arrow_tag_counts(bqsr_context* ctx, const bqsr_tags_chunk* chun
     SortTmp stage;
     tagk::ArrowTags C;
     if ((e = tags_stage(stage, chunks[c], base, s, &C)) != BQSR_OK) return e;
-    HIP_TRY(hipEventRecord(ev.a, s));
-    hipLaunchKernelGGL(tagk::tags_scan_arrow, dim3(tags_grid(ctx, m)), dim3(tagk::kThreads), 0, s, C, d);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.b, s));
+    HIP_TRY(clock.mark(0, s));
+    JOB_TRY(launch(tagk::tags_scan_arrow, tags_grid(ctx, m), tagk::kThreads, s, C, d));
+    HIP_TRY(clock.mark(1, s));
     HIP_TRY(hipStreamSynchronize(s));  // (the staging goes)
-    ms += ev.ms();
+    clock.add(ms, 0, 1);
     base += m;
   }
-  HIP_TRY(hipEventRecord(ev.a, s));
-  HIP_TRY(hipEventRecord(ev.b, s));
-  e = tags_finish(d, s, ev, out);
-  g_tags_ms[0] = ms;
+  HIP_TRY(clock.mark(0, s));
+  HIP_TRY(clock.mark(1, s));
+  e = tags_finish(d, s, clock, out);
+  g_tags_ms[TAGS_SCAN] = ms;  // the chunks' sum, without the empty span tags_finish read
   return e;
 }
 
@@ -787,7 +759,7 @@ bqsr_status bqsr_sam_tag_values(bqsr_context* ctx, const bqsr_sam* sm, const cha
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
   g_tag_runs.clear();
-  g_tags_ms[1] = 0.0;
+  g_tags_ms[TAGS_VALUES] = 0.0;
   tag_sizes(out);
   tagk::Values V{};
   V.text = sm->d_text;
@@ -798,17 +770,16 @@ bqsr_status bqsr_sam_tag_values(bqsr_context* ctx, const bqsr_sam* sm, const cha
   V.tag = (uint32_t)(uint8_t)tag[0] | ((uint32_t)(uint8_t)tag[1] << 8);
   V.bits = hash_bits;
   if (V.n == 0) return ok();
-  TagEvents ev;
-  HIP_TRY(ev.make());
-  HIP_TRY(hipEventRecord(ev.a, s));
+  TagClock clock;
+  HIP_TRY(clock.mark(0, s));
   const bqsr_status e = tag_values_run(ctx, V, s);
   if (e != BQSR_OK) {
     g_tag_runs.clear();
     return e;
   }
-  HIP_TRY(hipEventRecord(ev.b, s));
+  HIP_TRY(clock.mark(1, s));
   HIP_TRY(hipStreamSynchronize(s));
-  g_tags_ms[1] = ev.ms();
+  clock.add(g_tags_ms[TAGS_VALUES], 0, 1);
   tag_sizes(out);
   return ok();
 }
@@ -822,10 +793,9 @@ bqsr_status bqsr_arrow_tag_values(bqsr_context* ctx, const bqsr_tags_chunk* chun
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
   g_tag_runs.clear();
-  g_tags_ms[1] = 0.0;
+  g_tags_ms[TAGS_VALUES] = 0.0;
   tag_sizes(out);
-  TagEvents ev;
-  HIP_TRY(ev.make());
+  TagClock clock;
   double ms = 0.0;
   int64_t base = 0;
   for (int32_t c = 0; c < n_chunks; ++c) {
@@ -841,17 +811,17 @@ bqsr_status bqsr_arrow_tag_values(bqsr_context* ctx, const bqsr_tags_chunk* chun
     V.n = m;
     V.tag = (uint32_t)(uint8_t)tag[0] | ((uint32_t)(uint8_t)tag[1] << 8);
     V.bits = hash_bits;
-    HIP_TRY(hipEventRecord(ev.a, s));
+    HIP_TRY(clock.mark(0, s));
     if ((e = tag_values_run(ctx, V, s)) != BQSR_OK) {
       g_tag_runs.clear();
       return e;
     }
-    HIP_TRY(hipEventRecord(ev.b, s));
+    HIP_TRY(clock.mark(1, s));
     HIP_TRY(hipStreamSynchronize(s));
-    ms += ev.ms();
+    clock.add(ms, 0, 1);
     base += m;
   }
-  g_tags_ms[1] = ms;
+  g_tags_ms[TAGS_VALUES] = ms;
   tag_sizes(out);
   return ok();
 }
@@ -876,8 +846,8 @@ bqsr_status bqsr_tag_values_fetch(const bqsr_tag_value_host* dst) {
  * of this thread's last counts call (its scan kernels) and last values call
  * (the value kernels with their sorts and scans) */
 bqsr_status bqsr_tags_kernel_times(double* scan_ms, double* values_ms) {
-  if (scan_ms) *scan_ms = g_tags_ms[0];
-  if (values_ms) *values_ms = g_tags_ms[1];
+  if (scan_ms) *scan_ms = g_tags_ms[TAGS_SCAN];
+  if (values_ms) *values_ms = g_tags_ms[TAGS_VALUES];
   return BQSR_OK;
 }
 

@@ -29,7 +29,7 @@ import time
 from typing import Dict, Optional, Tuple
 
 from . import _capi, bqsr
-from ._capi import check
+from ._capi import check, i32, vp
 from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
 
 # the command's projection (cli/FlagStat.scala:50-57), booleans in bqsr_flagstat_chunk's order
@@ -85,23 +85,15 @@ class FlagStatChunk(ctypes.Structure):
                 ("mapq", ctypes.c_void_p), ("mapq_validity", ctypes.c_void_p)]
 
 
-_bound = False
+_SIG = {
+    "bqsr_sam_flagstat": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(_FlagStat)]),
+    "bqsr_flagstat_arrow": (ctypes.c_int, [vp, ctypes.POINTER(FlagStatChunk), i32, vp, ctypes.POINTER(_FlagStat)]),
+    "bqsr_flagstat_arrow_device": (ctypes.c_int, [vp, ctypes.POINTER(FlagStatChunk), vp, vp]),
+}
 
 
 def _lib():
-    global _bound
-    L = _capi.lib()
-    if not _bound:
-        vp = ctypes.c_void_p
-        L.bqsr_sam_flagstat.restype = ctypes.c_int
-        L.bqsr_sam_flagstat.argtypes = [vp, vp, vp, ctypes.POINTER(_FlagStat)]
-        L.bqsr_flagstat_arrow.restype = ctypes.c_int
-        L.bqsr_flagstat_arrow.argtypes = [vp, ctypes.POINTER(FlagStatChunk), ctypes.c_int32, vp,
-                                          ctypes.POINTER(_FlagStat)]
-        L.bqsr_flagstat_arrow_device.restype = ctypes.c_int
-        L.bqsr_flagstat_arrow_device.argtypes = [vp, ctypes.POINTER(FlagStatChunk), vp, vp]
-        _bound = True
-    return L
+    return _capi.bind(_capi.lib(), _SIG)
 
 
 def _result(r: _FlagStat) -> Tuple[FlagStatMetrics, FlagStatMetrics]:

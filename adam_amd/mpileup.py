@@ -58,7 +58,7 @@ from typing import Dict, Iterator, Optional, Sequence
 import numpy as np
 
 from . import _capi, bqsr
-from ._capi import check
+from ._capi import check, dblp, i32, i64, i64p, vp
 from .inputs import Phases, SamInput, is_parquet, report, text_output
 
 # Text per window.  A window's bytes exist once on the device and once in
@@ -78,37 +78,24 @@ class MpileupSizes(ctypes.Structure):
                 ("text_bytes", ctypes.c_int64)]
 
 
-_bound = False
+_SIG = {
+    "bqsr_sam_mpileup_prepare": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(MpileupSizes)]),
+    "bqsr_arrow_mpileup_prepare": (ctypes.c_int, [vp, vp, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_char_p), i32, vp,
+                                                  ctypes.POINTER(MpileupSizes)]),
+    "bqsr_sam_mpileup_text": (ctypes.c_int, [vp, vp, i64, i64, vp, vp, i64p, i64p]),
+    "bqsr_arrow_mpileup_text": (ctypes.c_int, [vp, vp, i64, i64, vp, vp, i64p, i64p]),
+    "bqsr_mpileup_kernel_times": (ctypes.c_int, [dblp]),
+}
 
 
 def _lib():
-    global _bound
-    from . import reads2ref
-    L = reads2ref._lib()
-    if not _bound:
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        pi64 = ctypes.POINTER(ctypes.c_int64)
-        L.bqsr_sam_mpileup_prepare.restype = ctypes.c_int
-        L.bqsr_sam_mpileup_prepare.argtypes = [vp, vp, vp, ctypes.POINTER(MpileupSizes)]
-        L.bqsr_arrow_mpileup_prepare.restype = ctypes.c_int
-        L.bqsr_arrow_mpileup_prepare.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_char_p), i32, vp,
-                                                 ctypes.POINTER(MpileupSizes)]
-        for name in ("bqsr_sam_mpileup_text", "bqsr_arrow_mpileup_text"):
-            f = getattr(L, name)
-            f.restype = ctypes.c_int
-            f.argtypes = [vp, vp, i64, i64, vp, vp, pi64, pi64]
-        L.bqsr_mpileup_kernel_times.restype = ctypes.c_int
-        L.bqsr_mpileup_kernel_times.argtypes = [ctypes.POINTER(ctypes.c_double)]
-        _bound = True
-    return L
+    return _capi.bind(_capi.lib(), _SIG)
 
 
 def kernel_times() -> Dict[str, float]:
     """ms by device events of this thread's last prepare (walk, emit, sort,
     group) and last text call (text) (measurement only)"""
-    a = (ctypes.c_double * 5)()
-    _lib().bqsr_mpileup_kernel_times(a)
-    return dict(zip(KERNELS, a))
+    return _capi.stage_times(_lib().bqsr_mpileup_kernel_times, KERNELS, array=True)
 
 
 def _windows(text_call, handle, ctx, sizes: MpileupSizes, window_bytes: int, stream=None) -> Iterator[bytes]:

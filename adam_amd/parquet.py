@@ -34,6 +34,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import _capi
+from ._capi import i32, i64, i64p, pp, vp
 from .records import (CigarParseError, F_DUPLICATE, F_HAS_CIGAR, F_HAS_MD, F_HAS_QUAL, F_HAS_REFNAME, F_HAS_RG,
                       F_HAS_SEQ, F_HAS_START, F_MAPPED, F_NEG_STRAND, F_PAIRED, F_PRIMARY, F_SECOND_OF_PAIR,
                       RecordBatch, cigar_to_text)
@@ -190,32 +192,20 @@ class _Chunk(ctypes.Structure):
                 ("reference_id_validity", ctypes.c_void_p), ("library", ctypes.c_void_p)]
 
 
-_arrow_bound = False
+_ARROW_SIG = {
+    "bqsr_arrow_load": (ctypes.c_int, [vp, ctypes.POINTER(_Chunk), i32, vp, pp]),
+    "bqsr_arrow_destroy": (None, [vp]),
+    "bqsr_arrow_reads": (i64, [vp]),
+    "bqsr_arrow_batch_create": (ctypes.c_int, [vp, vp, vp, i32, vp, pp]),
+    "bqsr_arrow_qual_prepare": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64p]),
+    "bqsr_arrow_qual_column": (ctypes.c_int, [vp, vp, vp, vp]),
+    "bqsr_arrow_mark_duplicates": (ctypes.c_int, [vp, vp, i64p]),
+    "bqsr_arrow_flag_bitmap": (ctypes.c_int, [vp, ctypes.c_uint32, vp]),
+}
 
 
 def _arrow_lib():
-    global _arrow_bound
-    from . import _capi
-    L = _capi.lib()
-    if not _arrow_bound:
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        pp = ctypes.POINTER(ctypes.c_void_p)
-        sig = {
-            "bqsr_arrow_load": (ctypes.c_int, [vp, ctypes.POINTER(_Chunk), i32, vp, pp]),
-            "bqsr_arrow_destroy": (None, [vp]),
-            "bqsr_arrow_reads": (i64, [vp]),
-            "bqsr_arrow_batch_create": (ctypes.c_int, [vp, vp, vp, i32, vp, pp]),
-            "bqsr_arrow_qual_prepare": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(i64)]),
-            "bqsr_arrow_qual_column": (ctypes.c_int, [vp, vp, vp, vp]),
-            "bqsr_arrow_mark_duplicates": (ctypes.c_int, [vp, vp, ctypes.POINTER(i64)]),
-            "bqsr_arrow_flag_bitmap": (ctypes.c_int, [vp, ctypes.c_uint32, vp]),
-        }
-        for name, (res, args) in sig.items():
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
-        _arrow_bound = True
-    return L
+    return _capi.bind(_capi.lib(), _ARROW_SIG)
 
 
 class ArrowReads:

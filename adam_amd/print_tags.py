@@ -40,7 +40,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, bqsr
-from ._capi import check
+from ._capi import check, dblp, i32, vp
 from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
 
 # the command's projection (cli/PrintTags.scala:68)
@@ -71,36 +71,25 @@ class _ValueHost(ctypes.Structure):
                 ("text_offsets", ctypes.c_void_p), ("text", ctypes.c_void_p)]
 
 
-_bound = False
+KERNELS = ("scan", "values")
+_SIG = {
+    "bqsr_sam_tag_counts": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(_TagCounts)]),
+    "bqsr_arrow_tag_counts": (ctypes.c_int, [vp, ctypes.POINTER(TagsChunk), i32, vp, ctypes.POINTER(_TagCounts)]),
+    "bqsr_sam_tag_values": (ctypes.c_int, [vp, vp, ctypes.c_char_p, i32, vp, ctypes.POINTER(_ValueSizes)]),
+    "bqsr_arrow_tag_values": (ctypes.c_int, [vp, ctypes.POINTER(TagsChunk), i32, ctypes.c_char_p, i32, vp,
+                                             ctypes.POINTER(_ValueSizes)]),
+    "bqsr_tag_values_fetch": (ctypes.c_int, [ctypes.POINTER(_ValueHost)]),
+    "bqsr_tags_kernel_times": (ctypes.c_int, [dblp, dblp]),
+}
 
 
 def _lib():
-    global _bound
-    L = _capi.lib()
-    if not _bound:
-        vp, i32 = ctypes.c_void_p, ctypes.c_int32
-        L.bqsr_sam_tag_counts.restype = ctypes.c_int
-        L.bqsr_sam_tag_counts.argtypes = [vp, vp, vp, ctypes.POINTER(_TagCounts)]
-        L.bqsr_arrow_tag_counts.restype = ctypes.c_int
-        L.bqsr_arrow_tag_counts.argtypes = [vp, ctypes.POINTER(TagsChunk), i32, vp, ctypes.POINTER(_TagCounts)]
-        L.bqsr_sam_tag_values.restype = ctypes.c_int
-        L.bqsr_sam_tag_values.argtypes = [vp, vp, ctypes.c_char_p, i32, vp, ctypes.POINTER(_ValueSizes)]
-        L.bqsr_arrow_tag_values.restype = ctypes.c_int
-        L.bqsr_arrow_tag_values.argtypes = [vp, ctypes.POINTER(TagsChunk), i32, ctypes.c_char_p, i32, vp,
-                                            ctypes.POINTER(_ValueSizes)]
-        L.bqsr_tag_values_fetch.restype = ctypes.c_int
-        L.bqsr_tag_values_fetch.argtypes = [ctypes.POINTER(_ValueHost)]
-        L.bqsr_tags_kernel_times.restype = ctypes.c_int
-        L.bqsr_tags_kernel_times.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        _bound = True
-    return L
+    return _capi.bind(_capi.lib(), _SIG)
 
 
 def kernel_times() -> Tuple[float, float]:
     """(scan ms, values ms) of this thread's last calls (measurement only)"""
-    a, b = ctypes.c_double(), ctypes.c_double()
-    check(_lib().bqsr_tags_kernel_times(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return tuple(_capi.stage_times(_lib().bqsr_tags_kernel_times, KERNELS).values())
 
 
 def _tag_bytes(tag) -> bytes:

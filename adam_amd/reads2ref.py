@@ -44,8 +44,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import _capi, bqsr
-from ._capi import check
+from . import _capi, adam_save, bqsr
+from ._capi import check, dblp, i32, i64, vp
 from .adam_save import (BASES, PILEUP_DICT_COLS, PILEUP_FIELDS, PILEUP_STATS_COLS, RG_TAGS, AdamHost, AdamSizes,
                         AdamWriter, HeaderInfo, _pinned, check_out, header_info, pileup_schema)
 from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
@@ -86,37 +86,24 @@ class PileupHost(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n, _ in _HOST]
 
 
-_bound = False
+KERNELS = ("count", "emit")
+_SIG = {
+    "bqsr_sam_pileup_prepare": (ctypes.c_int, [vp, vp, i64, i64, vp, ctypes.POINTER(PileupSizes)]),
+    "bqsr_sam_pileup_columns": (ctypes.c_int, [vp, vp, ctypes.POINTER(PileupHost), vp]),
+    "bqsr_arrow_pileup_prepare": (ctypes.c_int, [vp, vp, i64, i64, vp, vp, vp, i32, vp, ctypes.POINTER(PileupSizes)]),
+    "bqsr_arrow_pileup_columns": (ctypes.c_int, [vp, vp, ctypes.POINTER(PileupHost), vp]),
+    "bqsr_pileup_kernel_times": (ctypes.c_int, [dblp, dblp]),
+}
 
 
 def _lib():
-    global _bound
-    from . import parquet as P
-    from . import adam_save
-    L = adam_save._lib()
-    P._arrow_lib()
-    if not _bound:
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        L.bqsr_sam_pileup_prepare.restype = ctypes.c_int
-        L.bqsr_sam_pileup_prepare.argtypes = [vp, vp, i64, i64, vp, ctypes.POINTER(PileupSizes)]
-        L.bqsr_sam_pileup_columns.restype = ctypes.c_int
-        L.bqsr_sam_pileup_columns.argtypes = [vp, vp, ctypes.POINTER(PileupHost), vp]
-        L.bqsr_arrow_pileup_prepare.restype = ctypes.c_int
-        L.bqsr_arrow_pileup_prepare.argtypes = [vp, vp, i64, i64, vp, vp, vp, i32, vp, ctypes.POINTER(PileupSizes)]
-        L.bqsr_arrow_pileup_columns.restype = ctypes.c_int
-        L.bqsr_arrow_pileup_columns.argtypes = [vp, vp, ctypes.POINTER(PileupHost), vp]
-        L.bqsr_pileup_kernel_times.restype = ctypes.c_int
-        L.bqsr_pileup_kernel_times.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        _bound = True
-    return L
+    return _capi.bind(_capi.lib(), _SIG)
 
 
 def kernel_times():
     """(count ms, emit ms): the two kernels of this thread's last prepare /
     columns calls, by device events (measurement only)"""
-    a, b = ctypes.c_double(), ctypes.c_double()
-    _lib().bqsr_pileup_kernel_times(ctypes.byref(a), ctypes.byref(b))
-    return a.value, b.value
+    return tuple(_capi.stage_times(_lib().bqsr_pileup_kernel_times, KERNELS).values())
 
 
 def _host_columns(n_rows: int):
@@ -209,7 +196,7 @@ def _sam_read_level(sam, r0: int, n: int, hdr: HeaderInfo, stream=None) -> _Read
     """readName, referenceId and recordGroupId of reads [r0, r0 + n) from the
     device's ADAM columns (bqsr_sam_adam_*); the rest by index from the header"""
     import pyarrow as pa
-    L = _lib()
+    L = adam_save._lib()
     sz = AdamSizes()
     check(L.bqsr_sam_adam_prepare(sam.ctx.handle, sam.h, r0, n, stream, ctypes.byref(sz)))
     W = sz.bitmap_words

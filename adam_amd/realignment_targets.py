@@ -52,8 +52,8 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from . import bqsr
-from ._capi import check
+from . import _capi, bqsr
+from ._capi import check, dblp, vp
 from .inputs import Phases, SamInput, is_parquet, report, text_output
 
 # the ADAMRecord columns read from Parquet: reads2ref's without the read-level
@@ -74,35 +74,23 @@ class RealignTargetsHost(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in COLUMNS]
 
 
-_bound = False
+_SIG = {
+    "bqsr_sam_realign_targets_prepare": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(RealignTargetsSizes)]),
+    "bqsr_arrow_realign_targets_prepare": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(RealignTargetsSizes)]),
+    "bqsr_sam_realign_targets_fetch": (ctypes.c_int, [vp, vp, ctypes.POINTER(RealignTargetsHost), vp]),
+    "bqsr_arrow_realign_targets_fetch": (ctypes.c_int, [vp, vp, ctypes.POINTER(RealignTargetsHost), vp]),
+    "bqsr_realign_targets_kernel_times": (ctypes.c_int, [dblp]),
+}
 
 
 def _lib():
-    global _bound
-    from . import reads2ref
-    L = reads2ref._lib()
-    if not _bound:
-        vp = ctypes.c_void_p
-        for name in ("bqsr_sam_realign_targets_prepare", "bqsr_arrow_realign_targets_prepare"):
-            f = getattr(L, name)
-            f.restype = ctypes.c_int
-            f.argtypes = [vp, vp, vp, ctypes.POINTER(RealignTargetsSizes)]
-        for name in ("bqsr_sam_realign_targets_fetch", "bqsr_arrow_realign_targets_fetch"):
-            f = getattr(L, name)
-            f.restype = ctypes.c_int
-            f.argtypes = [vp, vp, ctypes.POINTER(RealignTargetsHost), vp]
-        L.bqsr_realign_targets_kernel_times.restype = ctypes.c_int
-        L.bqsr_realign_targets_kernel_times.argtypes = [ctypes.POINTER(ctypes.c_double)]
-        _bound = True
-    return L
+    return _capi.bind(_capi.lib(), _SIG)
 
 
 def kernel_times() -> Dict[str, float]:
     """ms of this thread's last prepare, by device events except ``fold_host``
     (measurement only)"""
-    a = (ctypes.c_double * 7)()
-    _lib().bqsr_realign_targets_kernel_times(a)
-    return dict(zip(KERNELS, a))
+    return _capi.stage_times(_lib().bqsr_realign_targets_kernel_times, KERNELS, array=True)
 
 
 def _length(name: str, sz: RealignTargetsSizes) -> int:

@@ -24,7 +24,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _capi, bqsr
-from ._capi import check
+from ._capi import check, dblp, i32, i64, i64p, pp, vp
 from .inputs import is_bam
 from .records import RecordBatch
 
@@ -54,58 +54,46 @@ class DupReads(ctypes.Structure):
                 ("qual", ctypes.c_void_p), ("cigar_offset", ctypes.c_void_p), ("cigar", ctypes.c_void_p)]
 
 
-_bound = False
+_SIG = {
+    "bqsr_sam_parse": (ctypes.c_int, [vp, ctypes.c_char_p, i64, vp, pp]),
+    "bqsr_bam_parse": (ctypes.c_int, [vp, ctypes.c_char_p, i64, vp, pp]),
+    "bqsr_sam_destroy": (None, [vp]),
+    "bqsr_sam_get_counts": (ctypes.c_int, [vp, ctypes.POINTER(SamCounts)]),
+    "bqsr_sam_ref_name": (ctypes.c_char_p, [vp, i32]),
+    "bqsr_sam_device_columns": (ctypes.c_int, [vp, ctypes.POINTER(SamColumns)]),
+    "bqsr_sam_download": (ctypes.c_int, [vp, ctypes.POINTER(SamColumns)]),
+    "bqsr_sam_rewrite_quals": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "bqsr_sam_text_download": (ctypes.c_int, [vp, ctypes.c_char_p]),
+    "bqsr_mark_duplicates": (ctypes.c_int, [ctypes.POINTER(DupReads), vp]),
+    "bqsr_sam_mark_duplicates": (ctypes.c_int, [vp, i64p]),
+    "bqsr_sam_markdup_path": (ctypes.c_int, [vp]),
+    "bqsr_sam_batch_create": (ctypes.c_int, [vp, vp, vp, i32, vp, pp]),
+    "bqsr_dup_set_create": (ctypes.c_int, [vp, i64, pp]),
+    "bqsr_dup_set_add": (ctypes.c_int, [vp, vp]),
+    "bqsr_dup_set_finish": (ctypes.c_int, [vp, i64p]),
+    "bqsr_dup_set_apply": (ctypes.c_int, [vp, i64, vp, i64p]),
+    "bqsr_dup_set_destroy": (None, [vp]),
+    "bqsr_sort_order": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, vp]),
+    "bqsr_sam_sort": (ctypes.c_int, [vp, vp, vp]),
+    "bqsr_sam_bam_form": (i32, [vp]),
+    "bqsr_sam_bam_prepare": (ctypes.c_int, [vp, vp, i64, i64, vp, ctypes.POINTER(BamSizes)]),
+    "bqsr_sam_bam_records": (ctypes.c_int, [vp, vp, vp, vp]),
+    "bqsr_sam_bam_header": (ctypes.c_int, [vp, vp, i64, i64p]),
+    "bqsr_bgzf_compress": (ctypes.c_int, [vp, i64, i32, vp, i64, i64p]),
+    "bqsr_bam_kernel_times": (ctypes.c_int, [dblp, dblp]),
+    "bqsr_bgzf_inflate": (ctypes.c_int, [vp, ctypes.c_char_p, i64, vp, vp, i64, i64p, vp, i64, i64p]),
+    "bqsr_bgzf_deflate": (ctypes.c_int, [vp, vp, i64, vp, vp, i64, i64p, i64p]),
+    "bqsr_bgzf_deflate_host": (ctypes.c_int, [vp, i64, vp, i64, i64p, i64p]),
+    "bqsr_sam_bam_members": (ctypes.c_int, [vp, vp, vp, vp, i64, i64p]),
+    "bqsr_deflate_code_lengths": (ctypes.c_int, [vp, i32, i32, vp]),
+    "bqsr_bgzf_deflate_times": (ctypes.c_int, [dblp, dblp]),
+}
+BAM_KERNELS = ("len", "write")
+DEFLATE_KERNELS = ("deflate", "pack")
 
 
 def _lib():
-    global _bound
-    L = _capi.lib()
-    if not _bound:
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        pp = ctypes.POINTER(ctypes.c_void_p)
-        sig = {
-            "bqsr_sam_parse": (ctypes.c_int, [vp, ctypes.c_char_p, i64, vp, pp]),
-            "bqsr_bam_parse": (ctypes.c_int, [vp, ctypes.c_char_p, i64, vp, pp]),
-            "bqsr_sam_destroy": (None, [vp]),
-            "bqsr_sam_get_counts": (ctypes.c_int, [vp, ctypes.POINTER(SamCounts)]),
-            "bqsr_sam_ref_name": (ctypes.c_char_p, [vp, i32]),
-            "bqsr_sam_device_columns": (ctypes.c_int, [vp, ctypes.POINTER(SamColumns)]),
-            "bqsr_sam_download": (ctypes.c_int, [vp, ctypes.POINTER(SamColumns)]),
-            "bqsr_sam_rewrite_quals": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, vp]),
-            "bqsr_sam_text_download": (ctypes.c_int, [vp, ctypes.c_char_p]),
-            "bqsr_mark_duplicates": (ctypes.c_int, [ctypes.POINTER(DupReads), vp]),
-            "bqsr_sam_mark_duplicates": (ctypes.c_int, [vp, ctypes.POINTER(i64)]),
-            "bqsr_sam_markdup_path": (ctypes.c_int, [vp]),
-            "bqsr_sam_batch_create": (ctypes.c_int, [vp, vp, vp, i32, vp, pp]),
-            "bqsr_dup_set_create": (ctypes.c_int, [vp, i64, pp]),
-            "bqsr_dup_set_add": (ctypes.c_int, [vp, vp]),
-            "bqsr_dup_set_finish": (ctypes.c_int, [vp, ctypes.POINTER(i64)]),
-            "bqsr_dup_set_apply": (ctypes.c_int, [vp, i64, vp, ctypes.POINTER(i64)]),
-            "bqsr_dup_set_destroy": (None, [vp]),
-            "bqsr_sort_order": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, vp]),
-            "bqsr_sam_sort": (ctypes.c_int, [vp, vp, vp]),
-            "bqsr_sam_bam_form": (i32, [vp]),
-            "bqsr_sam_bam_prepare": (ctypes.c_int, [vp, vp, i64, i64, vp, ctypes.POINTER(BamSizes)]),
-            "bqsr_sam_bam_records": (ctypes.c_int, [vp, vp, vp, vp]),
-            "bqsr_sam_bam_header": (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i64)]),
-            "bqsr_bgzf_compress": (ctypes.c_int, [vp, i64, i32, vp, i64, ctypes.POINTER(i64)]),
-            "bqsr_bam_kernel_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double),
-                                                     ctypes.POINTER(ctypes.c_double)]),
-            "bqsr_bgzf_inflate": (ctypes.c_int, [vp, ctypes.c_char_p, i64, vp, vp, i64, ctypes.POINTER(i64), vp, i64,
-                                                 ctypes.POINTER(i64)]),
-            "bqsr_bgzf_deflate": (ctypes.c_int, [vp, vp, i64, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
-            "bqsr_bgzf_deflate_host": (ctypes.c_int, [vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
-            "bqsr_sam_bam_members": (ctypes.c_int, [vp, vp, vp, vp, i64, ctypes.POINTER(i64)]),
-            "bqsr_deflate_code_lengths": (ctypes.c_int, [vp, i32, i32, vp]),
-            "bqsr_bgzf_deflate_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double),
-                                                       ctypes.POINTER(ctypes.c_double)]),
-        }
-        for name, (res, args) in sig.items():
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
-        _bound = True
-    return L
+    return _capi.bind(_capi.lib(), _SIG)
 
 
 class SamText:
@@ -405,16 +393,12 @@ def deflate_code_lengths(freq, max_bits: int) -> np.ndarray:
 
 def bgzf_deflate_times():
     """(member kernel ms, pack kernel ms) of this thread's last device deflate (measurement only)"""
-    a, b = ctypes.c_double(), ctypes.c_double()
-    check(_lib().bqsr_bgzf_deflate_times(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return tuple(_capi.stage_times(_lib().bqsr_bgzf_deflate_times, DEFLATE_KERNELS).values())
 
 
 def bam_kernel_times():
     """(pass 1 ms, pass 2 ms) of this thread's last ``bam_records`` (measurement only)"""
-    a, b = ctypes.c_double(), ctypes.c_double()
-    check(_lib().bqsr_bam_kernel_times(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return tuple(_capi.stage_times(_lib().bqsr_bam_kernel_times, BAM_KERNELS).values())
 
 
 class DupSet:
