@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ADAM_BQSR_LIB") or os.path.join(_HERE, "libadam_bqsr.so")
 
 BQSR_OK = 0
-STAGE_RESET, STAGE_KERNEL, STAGE_FOLD, STAGE_PREP, STAGE_LUT, STAGE_NO_LUT = 1, 2, 4, 8, 16, 32
+STAGE_RESET, STAGE_KERNEL, STAGE_FOLD, STAGE_PREP, STAGE_LUT, STAGE_NO_LUT, STAGE_FORK = 1, 2, 4, 8, 16, 32, 64
 STATUS_NAMES = ["OK", "NULL_RG", "MD_PARSE", "CIGAR_SHORT", "BAD_REVCOMP_BASE", "EMPTY_TABLE", "MISSING_KEY",
                 "QUAL_RANGE", "NULL_FIELD", "SEQ_SHORT", "CIGAR_INVALID", "INVALID_ARG", "DEVICE", "UNSUPPORTED",
                 "SAM_PARSE", "PILEUP", "ATTRIBUTE"]
@@ -32,10 +32,10 @@ EXPORTS = [
     "bqsr_batch_reads", "bqsr_batch_bases", "bqsr_batch_dims", "bqsr_batch_relayout", "bqsr_batch_layout_times", "bqsr_batch_wrap_device", "bqsr_table_words",
     "bqsr_table_create", "bqsr_table_destroy", "bqsr_table_dims", "bqsr_table_device_ptr", "bqsr_table_download",
     "bqsr_table_upload", "bqsr_observe", "bqsr_observe_records", "bqsr_table_merge", "bqsr_finalize",
-    "bqsr_lut_destroy", "bqsr_lut_stats", "bqsr_lut_shifts", "bqsr_apply", "bqsr_apply_records",
+    "bqsr_lut_destroy", "bqsr_lut_stats", "bqsr_lut_tables", "bqsr_lut_shifts", "bqsr_apply", "bqsr_apply_records",
     "bqsr_stage_records", "bqsr_staged_destroy", "bqsr_staged_bytes", "bqsr_staged_reads", "bqsr_staged_bases",
     "bqsr_batch_create_staged", "bqsr_batch_upload_async", "bqsr_em_fold_async", "bqsr_batch_em_copy_async",
-    "bqsr_finalize_device", "bqsr_observe_stage", "bqsr_apply_stage", "bqsr_job_reset_async", "bqsr_job_result", "bqsr_copy_async",
+    "bqsr_finalize_device", "bqsr_observe_stage", "bqsr_apply_stage", "bqsr_job_reset_async", "bqsr_job_result", "bqsr_job_tail_async", "bqsr_job_tail_path", "bqsr_copy_async",
     "bqsr_job_errors_export_async", "bqsr_job_errors_import_async", "bqsr_job_status_async", "bqsr_job_status_get",
     "bqsr_copy_dyn_async", "bqsr_compact_outputs_async", "bqsr_batch_exception_count_ptr",
     "bqsr_batch_fold_stats",
@@ -193,6 +193,9 @@ def lib():
             "bqsr_apply_records": (ctypes.c_int, [vp, vp, vp, vp, vp]),
             "bqsr_job_reset_async": (ctypes.c_int, [vp, vp, vp]),
             "bqsr_job_result": (ctypes.c_int, [vp, vp, ctypes.POINTER(dbl), ctypes.POINTER(i64), vp]),
+            "bqsr_job_tail_async": (ctypes.c_int, [vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, vp, vp, i64, vp]),
+            "bqsr_job_tail_path": (i32, [vp]),
+            "bqsr_lut_tables": (ctypes.c_int, [vp, vp, vp, vp]),
             "bqsr_copy_async": (ctypes.c_int, [vp, vp, vp, i64, vp]),
             "bqsr_copy_dyn_async": (ctypes.c_int, [vp, vp, vp, vp, i32, i64, i64, vp]),
             "bqsr_compact_outputs_async": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]),

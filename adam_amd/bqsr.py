@@ -51,14 +51,18 @@ class Context:
 
     # bqsr_context_tune knobs (include/adam_bqsr.h): layout choices of the
     # batches created afterwards, for tests and A/B runs; None = leave as is
-    _KNOBS = {"order": 1, "fronts": 2, "key_major": 3, "bgzf": 5, "flagstat_grid": 6, "pileup_grid": 7}
-    _DEFAULTS = {"order": -1, "fronts": -1, "key_major": 0, "bgzf": 1, "flagstat_grid": 0, "pileup_grid": 0}
+    _KNOBS = {"order": 1, "fronts": 2, "key_major": 3, "bgzf": 5, "flagstat_grid": 6, "pileup_grid": 7,
+              "spec_tail": 8, "spec_reserve": 9}
+    _DEFAULTS = {"order": -1, "fronts": -1, "key_major": 0, "bgzf": 1, "flagstat_grid": 0, "pileup_grid": 0,
+                 "spec_tail": 1, "spec_reserve": 8}
 
     def tune(self, **knobs) -> Dict[str, int]:
         """Set layout knobs (order: -1 auto / 0 read / 1 read-group buckets;
         fronts: -1 auto / 0 none / f; key_major: 1 / 0; bgzf: 1 device / 0 host
         inflate of BAM input; flagstat_grid: 0 auto / at most g workgroups for
-        the flagstat kernels; pileup_grid: the same for the reads2ref and mpileup kernels);
+        the flagstat kernels; pileup_grid: the same for the reads2ref and mpileup kernels;
+        spec_tail: 1 speculative job tail / 0 serial / 2 redo forced / 3 estimate
+        x 1.5, spec_reserve: CUs its apply leaves to the fold -- both from the next job on);
         returns the settings they replace."""
         cur = getattr(self, "_tuned", dict(self._DEFAULTS))
         prev = {}

@@ -259,6 +259,8 @@ struct bqsr_context {
   int tune_bgzf = 1;  // BAM ingest: BGZF inflated on the device (BQSR_TUNE_BGZF), 0 by host threads
   int tune_flagstat_grid = 0;  // flagstat kernels: at most this many workgroups (BQSR_TUNE_FLAGSTAT_GRID), 0 auto
   int tune_pileup_grid = 0;    // pileup kernels: at most this many workgroups (BQSR_TUNE_PILEUP_GRID), 0 auto
+  int tune_spec_tail = 1;      // bqsr_job_tail_async: 0 serial, 1 speculative, 2 redo forced, 3 estimate x 1.5
+  int tune_spec_reserve = 8;   // CUs the speculative apply leaves to the fold's kernels (BQSR_TUNE_SPEC_RESERVE)
   // flagstat's counter block (flagstat.hip: 37 words, allocated on first use; one call at a time)
   std::mutex flagstat_mu;
   unsigned long long* d_flagstat = nullptr;
@@ -413,9 +415,17 @@ struct bqsr_batch {
   hipStream_t side = nullptr;
   hipEvent_t ev_obs = nullptr, ev_fold = nullptr;
   bool obs_pending = false;
+  // bqsr_job_tail_async on a read-order batch: the fork event after the
+  // observe kernel (BQSR_STAGE_FORK) and the fold's tiles done on the side
+  // stream; the tail's device words (kTailWords) and the estimate
+  hipEvent_t ev_tiles = nullptr;
+  bool tail_fork = false;   // ev_obs recorded by a KERNEL | FORK stage, not yet taken
+  bool tail_spec = false;   // the last tail speculated (bqsr_job_tail_path)
+  uint32_t* d_tail = nullptr;
+  double* d_em_spec = nullptr;
   ~bqsr_batch() {
     if (side) (void)hipStreamDestroy(side);
-    for (hipEvent_t e : {ev_obs, ev_fold})
+    for (hipEvent_t e : {ev_obs, ev_fold, ev_tiles})
       if (e) (void)hipEventDestroy(e);
     if (d_part) (void)hipFree(d_part);
     if (d_off64) (void)hipFree(d_off64);
@@ -447,6 +457,7 @@ struct bqsr_lut {
   int64_t *qk_obs = nullptr, *qk_mm = nullptr, *grp_obs = nullptr, *grp_mm = nullptr;
   uint8_t *grp_ok = nullptr, *key_ok = nullptr, *rq_ok = nullptr;
   double *a2 = nullptr, *s1 = nullptr, *d2 = nullptr;
+  double *a2s = nullptr, *s1s = nullptr, *d2s = nullptr;  // bqsr_job_tail_async: the speculative tables
   FinalOut* d_out = nullptr;
   FinalOut out{};
   bool out_pending = false;  // bqsr_finalize_device: `out` not copied back yet (bqsr_job_result / lut_out)
@@ -513,6 +524,14 @@ bqsr_status bqsr_context_tune(bqsr_context* ctx, int knob, int64_t value) {
       if (value < 0 || value > (1 << 20)) break;
       ctx->tune_pileup_grid = (int)value;
       return BQSR_OK;
+    case BQSR_TUNE_SPEC_TAIL:
+      if (value < 0 || value > 3) break;
+      ctx->tune_spec_tail = (int)value;
+      return BQSR_OK;
+    case BQSR_TUNE_SPEC_RESERVE:
+      if (value < 1 || value > 64) break;
+      ctx->tune_spec_reserve = (int)value;
+      return BQSR_OK;
     default:
       return fail(BQSR_ERR_INVALID_ARG, "bqsr_context_tune: unknown knob");
   }
@@ -535,7 +554,7 @@ bqsr_status bqsr_context_create(int device, bqsr_context** out) {
   if (e == hipSuccess) e = hipMalloc(&c->d_qbq, kQbN * sizeof(int16_t));
   if (e == hipSuccess) e = hipMemcpy(c->d_qbt, buckets().thr.data(), kQbN * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(c->d_qbq, buckets().q.data(), kQbN * sizeof(int16_t), hipMemcpyHostToDevice);
-  for (const void* f : {(const void*)bqsr_apply_kernel, (const void*)bqsr_observe_chunks,
+  for (const void* f : {(const void*)bqsr_apply_kernel, (const void*)bqsr_redo_apply, (const void*)bqsr_observe_chunks,
                         (const void*)bqsr_observe_lean<true, false>, (const void*)bqsr_observe_lean<true, true>})
     if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
   if (e == hipSuccess)
@@ -1485,6 +1504,19 @@ bqsr_status check_dims(const bqsr_batch* b, const bqsr_table* t) {
 //   BQSR_STAGE_FOLD    the expectedMismatch fold kernel
 // Exposed separately so a caller can bracket one kernel with HIP events.
 namespace {
+// the fold's parameters for this batch; qmask: bqsr_fold_plan writes the set of
+// folded qual bins (the speculative tail's estimate kernel writes it instead)
+FoldParams fold_params(const bqsr_context* ctx, const bqsr_batch* b, bool qmask) {
+  FoldParams F = b->fold;
+  F.rd = b->rd;
+  F.info = b->d_info;
+  F.hq_block = b->d_hq;
+  F.pow10 = ctx->d_pow10;
+  F.n_blocks = b->n_blocks;
+  F.em_out = b->d_em;
+  F.qmask = qmask ? b->d_qmask : nullptr;
+  return F;
+}
 bqsr_status launch_prep(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* sites, hipStream_t s) {
   if (!b->err_fresh) HIP_TRY(hipMemsetAsync(b->d_err + kErrAppPrep, 0xFF, 8, s));  // (else the job reset did)
   b->err_fresh = false;
@@ -1599,15 +1631,20 @@ bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_site
     // them).  In read order the histograms are the observe kernel's, and a
     // fork after it would only hide bqsr_window_reduce (17 us on cfg2) at
     // the price of two event records (~15 us each on this runtime)
+    // BQSR_STAGE_FORK (read order, speculative tail on): the fork event after
+    // the observe kernel, taken by bqsr_job_tail_async
+    const bool tail_fork = lean && (stages & BQSR_STAGE_FORK) && ctx->tune_spec_tail != 0;
+    if ((!lean || tail_fork) && !b->side) {
+      HIP_TRY(hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking));
+      HIP_TRY(hipEventCreateWithFlags(&b->ev_obs, hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&b->ev_fold, hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&b->ev_tiles, hipEventDisableTiming));
+    }
     if (!lean) {
-      if (!b->side) {
-        HIP_TRY(hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&b->ev_obs, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&b->ev_fold, hipEventDisableTiming));
-      }
       HIP_TRY(hipEventRecord(b->ev_obs, s));
       b->obs_pending = true;
     }
+    b->tail_fork = false;
     // slabs w + key
     const size_t need = (size_t)P.part_stride * (b->pass_blocks() + b->n_keys - 1);
     if (b->part_words < need) {  // grows with the table geometry; kept across calls
@@ -1634,6 +1671,10 @@ bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_site
       hipLaunchKernelGGL(bqsr_observe_chunks, dim3(P.n_blocks), dim3(kBlockThreads), lds, s, P);
     }
     HIP_TRY(hipGetLastError());
+    if (tail_fork) {
+      HIP_TRY(hipEventRecord(b->ev_obs, s));
+      b->tail_fork = true;
+    }
     const int rb = (int)std::min<int64_t>(4096, ((int64_t)P.part_stride * (b->bucketed ? b->n_base : 1) + 255) / 256);
     const unsigned ry = b->bucketed ? 1u : (unsigned)((b->n_blocks + kRedSlabs - 1) / kRedSlabs);
     hipLaunchKernelGGL(bqsr_window_reduce, dim3(rb, ry), dim3(256), 0, s, (const uint32_t*)b->d_part, b->rd, P.ord,
@@ -1659,14 +1700,9 @@ bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_site
                          b->n_blocks, lane_shift(b), b->d_hq);
       HIP_TRY(hipGetLastError());
     }
-    FoldParams F = b->fold;
-    F.rd = b->rd;
-    F.info = b->d_info;
-    F.hq_block = b->d_hq;
-    F.pow10 = ctx->d_pow10;
-    F.n_blocks = b->n_blocks;
-    F.em_out = b->d_em;
-    F.qmask = b->d_qmask;
+    b->tail_fork = false;  // (a fork event nobody took: the serial schedule)
+    b->tail_spec = false;
+    const FoldParams F = fold_params(ctx, b, true);
     hipLaunchKernelGGL(bqsr_fold_plan, dim3(1), dim3(1024), 0, s, F);
     const int64_t max_tpb = (b->rd.n_tiles + b->n_blocks - 1) / b->n_blocks + 1;
     hipLaunchKernelGGL(bqsr_fold_tiles, dim3(ctx->n_cu * 4), dim3(kFtWaves * 64), 0, s, F, max_tpb);
@@ -1739,11 +1775,9 @@ bqsr_status bqsr_observe_records(bqsr_context* ctx, const bqsr_records* recs, co
 // ------------------------------------------------------------- finalize ----
 
 namespace {
-bqsr_status finalize_impl(bqsr_context* ctx, const bqsr_table* t, double em, const double* em_dev, bqsr_lut** out,
-                          void* stream) {
-  if (!ctx || !t || !out) return fail(BQSR_ERR_INVALID_ARG, "null");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = S(stream);
+// the LUT a finalize of `t` writes: *out when it fits (reused), else a new one
+// in its place; *fresh: newly allocated (the caller deletes it on failure)
+bqsr_status lut_for(bqsr_context* ctx, const bqsr_table* t, bqsr_lut** out, hipStream_t s, bqsr_lut** Lp, bool* fresh) {
   const TableGeom g = geom(t->dims);
   const int n_rg = t->dims.n_rg;
   // *out is NULL or a LUT from an earlier finalize: one of the same dims and
@@ -1774,6 +1808,24 @@ bqsr_status finalize_impl(bqsr_context* ctx, const bqsr_table* t, double em, con
     delete L;
     return st;
   }
+  *Lp = L;
+  *fresh = !reuse;
+  return BQSR_OK;
+}
+bqsr_status finalize_impl(bqsr_context* ctx, const bqsr_table* t, double em, const double* em_dev, bqsr_lut** out,
+                          void* stream) {
+  if (!ctx || !t || !out) return fail(BQSR_ERR_INVALID_ARG, "null");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = S(stream);
+  const TableGeom g = geom(t->dims);
+  const int n_rg = t->dims.n_rg;
+  bqsr_lut* L = nullptr;
+  bool fresh = false;
+  {
+    const bqsr_status st = lut_for(ctx, t, out, s, &L, &fresh);
+    if (st != BQSR_OK) return st;
+  }
+  const bool reuse = !fresh;
   hipLaunchKernelGGL(bqsr_final_keys, dim3((g.K + 3) / 4), dim3(256), 0, s, t->touched(), t->obs(), t->mm(), g, L->qk_obs,
                      L->qk_mm);
   hipLaunchKernelGGL(bqsr_final_groups, dim3(1), dim3(256), 0, s, t->touched(), L->qk_obs, L->qk_mm, g, n_rg, em,
@@ -1897,6 +1949,18 @@ bqsr_status bqsr_lut_stats(const bqsr_lut* lc, bqsr_final_stats* out) {
   return ok();
 }
 
+// the device apply tables on the host, after waiting for the device (tests)
+bqsr_status bqsr_lut_tables(const bqsr_lut* L, double* a2, double* s1, double* d2) {
+  if (!L) return fail(BQSR_ERR_INVALID_ARG, "null");
+  HIP_TRY(hipSetDevice(L->ctx->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t rq = (size_t)L->dims.n_rg * kQBins;
+  if (a2) HIP_TRY(hipMemcpy(a2, L->a2, rq * 8, hipMemcpyDeviceToHost));
+  if (s1) HIP_TRY(hipMemcpy(s1, L->s1, rq * (size_t)geom(L->dims).C * 8, hipMemcpyDeviceToHost));
+  if (d2) HIP_TRY(hipMemcpy(d2, L->d2, rq * kCtxSlots * 8, hipMemcpyDeviceToHost));
+  return ok();
+}
+
 // per-group counts (index r + 1); returns 0 when the group does not exist
 int bqsr_lut_group(const bqsr_lut* lc, int32_t r, int64_t* obs, int64_t* mm) {
   bqsr_lut* L = const_cast<bqsr_lut*>(lc);
@@ -1952,31 +2016,14 @@ int32_t bqsr_phred_threshold_table(double* out, int32_t cap, int32_t* qmin) {
 
 // ---------------------------------------------------------------- apply ----
 
-// stages: BQSR_STAGE_RESET (apply-kernel error word, exception count),
-// BQSR_STAGE_KERNEL (apply kernel).  The prep kernel runs first when observe
-// has not run it on this batch.
-// bucketed batches: the per-read outputs by bqsr_apply_outs in read order
-// instead of the walk's scattered stores (cfg4: apply 3.95 -> 3.67 ms + 0.13
-// ms for the pass, profiles/r04aa_cfg4_apply_outs_ab.txt)
-
-bqsr_status bqsr_apply_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_lut* L, uint8_t* out_qual,
-                             uint32_t* out_start, uint32_t* out_len, uint64_t* exceptions, int64_t max_exceptions,
-                             int32_t stages, void* stream) {
-  if (!ctx || !b || !L || !out_qual || !out_start || !out_len) return fail(BQSR_ERR_INVALID_ARG, "null");
-  if (b->dims.n_rg > L->dims.n_rg || b->dims.max_len > L->dims.max_len)
-    return fail(BQSR_ERR_INVALID_ARG, "table dims smaller than the batch's");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = S(stream);
-  if (stages & BQSR_STAGE_RESET) {
-    HIP_TRY(hipMemsetAsync(b->d_err + kErrAppKern, 0xFF, 8, s));
-    HIP_TRY(hipMemsetAsync(b->d_err + kNExc, 0, 8, s));
-  }
-  if (!b->prepped || (stages & BQSR_STAGE_PREP)) {
-    bqsr_status st = launch_prep(ctx, b, nullptr, s);
-    if (st != BQSR_OK) return st;
-  }
-  if (b->rd.n_reads == 0 || !(stages & (BQSR_STAGE_KERNEL | BQSR_STAGE_LUT))) return ok();
+namespace {
+// apply's parameter block for this batch and LUT; the batch's char-table
+// buffer grows here when the window does
+bqsr_status apply_params(bqsr_context* ctx, bqsr_batch* b, const bqsr_lut* L, uint8_t* out_qual, uint32_t* out_start,
+                         uint32_t* out_len, uint64_t* exceptions, int64_t max_exceptions, void* stream,
+                         ApplyParams* out) {
   ApplyParams P{};
+  hipStream_t s = S(stream);
   P.rd = b->pass_rd();
   P.ord = b->order();
   P.info = b->d_info;
@@ -2006,7 +2053,7 @@ bqsr_status bqsr_apply_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_lut* L
   P.err = b->d_err + kErrAppKern;
   P.piece_stride = piece_bytes(P.w.qw, cw);
   // a char table per base key (fronts share their read group's)
-  const size_t need = (size_t)P.piece_stride * (size_t)b->n_base + (size_t)b->n_base * 16;  // + rowbad
+  const size_t need = (size_t)P.piece_stride * (size_t)b->n_base + (size_t)b->n_base * 32;  // + rowbad, and the speculative tail's redo's
   if (b->chars_bytes < need) {  // grows with the window; kept across calls
     if (b->d_chars) {
       HIP_TRY(hipStreamSynchronize(s));
@@ -2021,6 +2068,41 @@ bqsr_status bqsr_apply_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_lut* L
   P.chars = b->d_chars;
   P.rowbad = (uint32_t*)(b->d_chars + (size_t)P.piece_stride * (size_t)b->n_base);
   P.qmask = b->hq_valid ? b->d_qmask : nullptr;
+  *out = P;
+  return BQSR_OK;
+}
+}  // namespace
+
+// stages: BQSR_STAGE_RESET (apply-kernel error word, exception count),
+// BQSR_STAGE_KERNEL (apply kernel).  The prep kernel runs first when observe
+// has not run it on this batch.
+// bucketed batches: the per-read outputs by bqsr_apply_outs in read order
+// instead of the walk's scattered stores (cfg4: apply 3.95 -> 3.67 ms + 0.13
+// ms for the pass, profiles/r04aa_cfg4_apply_outs_ab.txt)
+bqsr_status bqsr_apply_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_lut* L, uint8_t* out_qual,
+                             uint32_t* out_start, uint32_t* out_len, uint64_t* exceptions, int64_t max_exceptions,
+                             int32_t stages, void* stream) {
+  if (!ctx || !b || !L || !out_qual || !out_start || !out_len) return fail(BQSR_ERR_INVALID_ARG, "null");
+  if (b->dims.n_rg > L->dims.n_rg || b->dims.max_len > L->dims.max_len)
+    return fail(BQSR_ERR_INVALID_ARG, "table dims smaller than the batch's");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = S(stream);
+  if (stages & BQSR_STAGE_RESET) {
+    HIP_TRY(hipMemsetAsync(b->d_err + kErrAppKern, 0xFF, 8, s));
+    HIP_TRY(hipMemsetAsync(b->d_err + kNExc, 0, 8, s));
+  }
+  if (!b->prepped || (stages & BQSR_STAGE_PREP)) {
+    bqsr_status st = launch_prep(ctx, b, nullptr, s);
+    if (st != BQSR_OK) return st;
+  }
+  if (b->rd.n_reads == 0 || !(stages & (BQSR_STAGE_KERNEL | BQSR_STAGE_LUT))) return ok();
+  ApplyParams P{};
+  {
+    const bqsr_status st = apply_params(ctx, b, L, out_qual, out_start, out_len, exceptions, max_exceptions, stream, &P);
+    if (st != BQSR_OK) return st;
+  }
+  const int cw = window_cw(b, P.g);
+  const size_t need = (size_t)P.piece_stride * (size_t)b->n_base + (size_t)b->n_base * 16;
   const bool lut_stage = (stages & BQSR_STAGE_LUT) || ((stages & BQSR_STAGE_KERNEL) && !(stages & BQSR_STAGE_NO_LUT));
   if (lut_stage) {
     HIP_TRY(hipMemsetAsync(P.rowbad, 0, (size_t)b->n_base * 16, s));
@@ -2148,6 +2230,7 @@ bqsr_status bqsr_job_reset_async(bqsr_batch* b, bqsr_table* t, void* stream) {
   hipLaunchKernelGGL(bqsr_job_reset_kernel, dim3(g), dim3(256), 0, S(stream), t->words, n, b->d_err);
   HIP_TRY(hipGetLastError());
   b->err_fresh = true;
+  b->tail_spec = false;  // a new job: serial until a speculative tail runs
   return ok();
 }
 
@@ -2178,7 +2261,8 @@ bqsr_status bqsr_job_status_async(bqsr_batch* b, bqsr_lut* L, int32_t slot, void
   if (!b->h_status)
     HIP_TRY(hipHostMalloc((void**)&b->h_status, kJobStatusWords * 8 * (1 + kStatusSlots), hipHostMallocDefault));
   hipLaunchKernelGGL(bqsr_job_status_kernel, dim3(1), dim3(64), 0, S(stream), (const unsigned long long*)b->d_err,
-                     (const double*)b->d_em, (const FinalOut*)L->d_out, b->h_status + kJobStatusWords * (1 + slot));
+                     (const double*)b->d_em, (const FinalOut*)L->d_out, (const uint32_t*)nullptr,
+                     b->h_status + kJobStatusWords * (1 + slot));
   HIP_TRY(hipGetLastError());
   return ok();
 }
@@ -2226,7 +2310,8 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
   if (!b->h_status)
     HIP_TRY(hipHostMalloc((void**)&b->h_status, kJobStatusWords * 8 * (1 + kStatusSlots), hipHostMallocDefault));
   hipLaunchKernelGGL(bqsr_job_status_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)b->d_err,
-                     (const double*)b->d_em, (const FinalOut*)L->d_out, b->h_status);
+                     (const double*)b->d_em, (const FinalOut*)L->d_out,
+                     (const uint32_t*)(b->tail_spec ? b->d_tail : nullptr), b->h_status);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s));
   const uint64_t* h = b->h_status;
@@ -2238,6 +2323,134 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
   if (st != BQSR_OK) return st;
   if (!L->out.any_key) return fail(BQSR_ERR_EMPTY_TABLE, "empty.reduceLeft: no usable base was observed");
   return from_err_key(std::min(h[kErrAppPrep], h[kErrAppKern]), 0);
+}
+
+// which schedule the job bqsr_job_result last fetched ran: 0 serial, 1
+// speculative and accepted, 2 speculative and apply run again
+int32_t bqsr_job_tail_path(const bqsr_batch* b) {
+  if (!b || !b->h_status || !b->tail_spec) return 0;
+  return b->h_status[kErrWords + 1 + sizeof(FinalOut) / 8] ? 2 : 1;
+}
+
+// The job's tail after the observe kernel (include/adam_bqsr.h).  Serial:
+// fold, finalize, apply, each waiting on the one before -- nine small kernels
+// between the two large ones.  Speculative (read order,
+// BQSR_TUNE_SPEC_TAIL): apply's tables depend on the exact expectedMismatch
+// almost only through rounding, so
+//   caller's stream: bqsr_window_reduce (the KERNEL stage), bqsr_tail_estimate,
+//     finalize with the estimate into the speculative a2 / s1 / d2, the char
+//     tables, bqsr_apply_kernel on CUs - k workgroups; then, the fold joined,
+//     the exact bqsr_final_groups / bqsr_final_tables into the LUT,
+//     bqsr_tail_compare, and the redo (bqsr_redo_chars + bqsr_redo_apply,
+//     guarded by the redo word: they exit at once when the tables agree);
+//   side stream, from the fork event after the observe kernel: the four fold
+//     kernels.  bqsr_fold_tiles wants the whole GPU, so apply waits for it
+//     (ev_tiles); bqsr_fold_segs and bqsr_fold_chain take the CUs apply leaves.
+// Workgroups are dealt round-robin over the XCDs, each XCD placing its own:
+// bqsr_fold_segs' workgroups on an XCD whose CUs apply holds would wait for
+// apply's end, hence k = 8 by default, one CU per XCD.
+bqsr_status bqsr_job_tail_async(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* sites, bqsr_table* t,
+                                bqsr_lut** lut, uint8_t* out_qual, uint32_t* out_start, uint32_t* out_len,
+                                uint64_t* exceptions, int64_t max_exceptions, void* stream) {
+  if (!ctx || !b || !t || !lut || !out_qual || !out_start || !out_len) return fail(BQSR_ERR_INVALID_ARG, "null");
+  const bool spec = ctx->tune_spec_tail != 0 && !b->bucketed && b->rd.n_reads > 0 && b->tail_fork;
+  b->tail_spec = false;
+  if (!spec) {
+    bqsr_status st = bqsr_observe_stage(ctx, b, sites, t, BQSR_STAGE_FOLD, stream);
+    if (st == BQSR_OK) st = bqsr_finalize_device(ctx, t, b->d_em, lut, stream);
+    if (st == BQSR_OK)
+      st = bqsr_apply_stage(ctx, b, *lut, out_qual, out_start, out_len, exceptions, max_exceptions, BQSR_STAGE_KERNEL, stream);
+    return st;
+  }
+  bqsr_status st = check_dims(b, t);
+  if (st != BQSR_OK) return st;
+  if (!b->prepped || b->prep_sites != sites)
+    return fail(BQSR_ERR_INVALID_ARG, "job tail before the prep and observe stages (or with other known sites)");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = S(stream);
+  b->tail_fork = false;
+  if (!b->d_tail && ((st = dalloc(b->allocs, &b->d_tail, kTailWords)) != BQSR_OK ||
+                     (st = dalloc(b->allocs, &b->d_em_spec, 1)) != BQSR_OK))
+    return st;
+  const TableGeom g = geom(t->dims);
+  const int n_rg = t->dims.n_rg;
+  bqsr_lut* L = nullptr;
+  bool fresh = false;
+  if ((st = lut_for(ctx, t, lut, s, &L, &fresh)) != BQSR_OK) return st;
+  *lut = L;
+  if (!L->a2s && ((st = dalloc(L->allocs, &L->a2s, (size_t)n_rg * kQBins)) != BQSR_OK ||
+                  (st = dalloc(L->allocs, &L->s1s, (size_t)n_rg * kQBins * g.C)) != BQSR_OK ||
+                  (st = dalloc(L->allocs, &L->d2s, (size_t)n_rg * kQBins * kCtxSlots)) != BQSR_OK))
+    return st;
+  ApplyParams P{};
+  if ((st = apply_params(ctx, b, L, out_qual, out_start, out_len, exceptions, max_exceptions, stream, &P)) != BQSR_OK) return st;
+  const int cw = window_cw(b, P.g);
+  const int rb_words = b->n_base * 4;  // rowbad words of one set of char tables
+  P.qmask = b->d_qmask;
+
+  // ---- side stream: the exact fold, from the fork event ----
+  HIP_TRY(hipStreamWaitEvent(b->side, b->ev_obs, 0));
+  const FoldParams F = fold_params(ctx, b, false);
+  hipLaunchKernelGGL(bqsr_fold_plan, dim3(1), dim3(1024), 0, b->side, F);
+  const int64_t max_tpb = (b->rd.n_tiles + b->n_blocks - 1) / b->n_blocks + 1;
+  hipLaunchKernelGGL(bqsr_fold_tiles, dim3(ctx->n_cu * 4), dim3(kFtWaves * 64), 0, b->side, F, max_tpb);
+  HIP_TRY(hipEventRecord(b->ev_tiles, b->side));
+  hipLaunchKernelGGL(bqsr_fold_segs, dim3(b->n_blocks), dim3(kSegThreads), 0, b->side, F);
+  hipLaunchKernelGGL(bqsr_fold_chain, dim3(1), dim3(1024), chain_lds(b->n_blocks), b->side, F);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev_fold, b->side));
+  b->hq_valid = true;
+
+  // ---- caller's stream: estimate, speculative tables, apply ----
+  const int mode = ctx->tune_spec_tail;
+  hipLaunchKernelGGL(bqsr_tail_estimate, dim3(1), dim3(1024), 0, s, (const uint32_t*)b->d_hq, b->n_blocks,
+                     (const double*)ctx->d_pow10, mode == 3 ? 1.5 : 1.0, b->d_em_spec, b->d_qmask, b->d_tail, P.rowbad,
+                     2 * rb_words);
+  hipLaunchKernelGGL(bqsr_final_keys, dim3((g.K + 3) / 4), dim3(256), 0, s, t->touched(), t->obs(), t->mm(), g, L->qk_obs,
+                     L->qk_mm);
+  const int64_t ncell = (int64_t)n_rg * kQBins * (g.C + kCtxSlots);
+  const unsigned tb = (unsigned)std::min<int64_t>(8192, (ncell + 255) / 256);
+  const double mre = pow10tab().v[kMaxQ];
+  hipLaunchKernelGGL(bqsr_final_groups, dim3(1), dim3(256), 0, s, t->touched(), L->qk_obs, L->qk_mm, g, n_rg, 0.0,
+                     (const double*)b->d_em_spec, ctx->d_pow10, L->n_groups, L->grp_obs, L->grp_mm, L->grp_ok, L->key_ok,
+                     L->a2s, L->rq_ok, L->d_out);
+  hipLaunchKernelGGL(bqsr_final_tables, dim3(tb), dim3(256), 0, s, t->obs(), t->mm(), g, n_rg, L->a2s, L->rq_ok, mre,
+                     L->s1s, L->d2s);
+  const size_t chars_n = (size_t)P.piece_stride * (size_t)b->n_base + (size_t)b->n_base * 16;
+  const unsigned cb = (unsigned)std::min<int64_t>(((int64_t)chars_n + 255) / 256, (int64_t)ctx->n_cu * 16);
+  ApplyParams Ps = P;
+  Ps.s1 = L->s1s;
+  Ps.d2 = L->d2s;
+  hipLaunchKernelGGL(bqsr_apply_chars, dim3(cb), dim3(256), 0, s, Ps, b->d_chars);
+  b->chars_lut = nullptr;  // (the tables are the speculative ones, or the redo's)
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamWaitEvent(s, b->ev_tiles, 0));
+  // static ranges on the smaller grid (ranges claimed from a device counter
+  // measured level with it: profiles/r08_spec_tail_ab.txt)
+  const int grid = std::max(1, b->pass_blocks() - ctx->tune_spec_reserve);
+  hipLaunchKernelGGL(bqsr_apply_kernel, dim3(grid), dim3(kBlockThreads), apply_lds(P.w.qw, cw), s, Ps);
+  HIP_TRY(hipGetLastError());
+
+  // ---- the exact tables, the verification, the guarded redo ----
+  HIP_TRY(hipStreamWaitEvent(s, b->ev_fold, 0));
+  hipLaunchKernelGGL(bqsr_final_groups, dim3(1), dim3(256), 0, s, t->touched(), L->qk_obs, L->qk_mm, g, n_rg, 0.0,
+                     (const double*)b->d_em, ctx->d_pow10, L->n_groups, L->grp_obs, L->grp_mm, L->grp_ok, L->key_ok, L->a2,
+                     L->rq_ok, L->d_out);
+  hipLaunchKernelGGL(bqsr_final_tables, dim3(tb), dim3(256), 0, s, t->obs(), t->mm(), g, n_rg, L->a2, L->rq_ok, mre, L->s1,
+                     L->d2);
+  hipLaunchKernelGGL(bqsr_tail_compare, dim3((unsigned)(n_rg * kQBins)), dim3(256), 0, s, P, (const double*)L->a2,
+                     (const double*)L->a2s, (const double*)L->s1s, (const double*)L->d2s, mode == 2 ? 1 : 0, b->d_tail);
+  ApplyParams Pr = P;  // the redo: exact tables, full grid, a bad-row set of its own
+  Pr.run_if = b->d_tail + kTailRedo;
+  Pr.rowbad = P.rowbad + rb_words;
+  Pr.redo_mark = b->d_tail + kTailRan;
+  hipLaunchKernelGGL(bqsr_redo_chars, dim3(cb), dim3(256), 0, s, Pr, b->d_chars);
+  hipLaunchKernelGGL(bqsr_redo_apply, dim3(b->pass_blocks()), dim3(kBlockThreads), apply_lds(P.w.qw, cw), s, Pr);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(BQSR_ERR_DEVICE, hipGetErrorString(e));
+  L->out_pending = true;
+  b->tail_spec = true;
+  return ok();
 }
 
 }  // extern "C"

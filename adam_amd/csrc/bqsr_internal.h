@@ -115,7 +115,7 @@ enum : uint32_t {
 };
 // error words of a batch
 enum { kErrObs = 0, kErrAppPrep = 1, kErrAppKern = 2, kNExc = 3, kErrWords = 4 };
-constexpr int kJobStatusWords = 16;  // bqsr_job_result: error words, em, FinalOut
+constexpr int kJobStatusWords = 16;  // bqsr_job_result: error words, em, FinalOut, the tail's redo word
 constexpr int kStatusSlots = 4;      // bqsr_job_status_async: snapshots of pipelined jobs
 
 // ---- known sites -------------------------------------------------------------
@@ -338,7 +338,12 @@ struct ApplyParams {
   int64_t piece_stride;   // bytes per piece: qw * cw * 21 rounded up to 16
   uint32_t* rowbad;       // [n_keys][4] rows of a piece's char table holding a 0 entry (bit per row)
   const uint32_t* qmask;  // [4] qual bins of the batch's folded bases (FoldParams::qmask), or null
+  // speculative job tail (bqsr_job_tail_async)
+  const uint32_t* run_if;  // bqsr_redo_chars and bqsr_redo_apply exit at once unless *run_if != 0
+  uint32_t* redo_mark;     // bqsr_redo_chars: set when the redo runs (after *err and *n_exc are reset)
 };
+// device words of a speculative job tail (bqsr_batch::d_tail)
+enum { kTailRedo = 0, kTailRan = 1, kTailWords = 2 };
 
 // finalize results read back by the host
 struct FinalOut {
@@ -348,7 +353,7 @@ struct FinalOut {
   int32_t pad;
 };
 // bqsr_job_status_kernel's host words: error words, expectedMismatch, FinalOut
-static_assert(kErrWords + 1 + sizeof(FinalOut) / 8 <= (size_t)kJobStatusWords, "job status words overflow");
+static_assert(kErrWords + 2 + sizeof(FinalOut) / 8 <= (size_t)kJobStatusWords, "job status words overflow");
 static_assert(sizeof(FinalOut) % 8 == 0, "FinalOut is whole words");
 
 // errorProbabilityToPhred step function: thr[i] = the largest p > 0 whose

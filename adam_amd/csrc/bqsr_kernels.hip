@@ -2566,7 +2566,7 @@ extern "C" __global__ void bqsr_apply_outs(ApplyParams P) {
   }
 }
 
-extern "C" __global__ void bqsr_apply_chars(ApplyParams P, uint8_t* chars) {
+__device__ __forceinline__ void apply_chars_body(const ApplyParams& P, uint8_t* chars) {
   const int nk = order_base_keys(P.ord), qw = P.w.qw, q_lo = P.w.q_lo;
   const int64_t total = (int64_t)nk * P.piece_stride;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
@@ -2597,7 +2597,7 @@ extern "C" __global__ void bqsr_apply_chars(ApplyParams P, uint8_t* chars) {
   }
 }
 
-extern "C" __global__ void __launch_bounds__(kBlockThreads) bqsr_apply_kernel(ApplyParams P) {
+__device__ __forceinline__ void apply_body(const ApplyParams& P) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int qw = P.w.qw, C = P.g.C, L = P.g.L;
   // LDS: [clean rows 16 B][walk markers][context table][char table]
@@ -2688,6 +2688,26 @@ extern "C" __global__ void __launch_bounds__(kBlockThreads) bqsr_apply_kernel(Ap
     }
   }  // pieces
 }
+extern "C" __global__ void bqsr_apply_chars(ApplyParams P, uint8_t* chars) { apply_chars_body(P, chars); }
+extern "C" __global__ void __launch_bounds__(kBlockThreads) bqsr_apply_kernel(ApplyParams P) { apply_body(P); }
+// The speculative tail's redo (bqsr_job_tail_async): the same two kernels
+// under names of their own (a profile's per-kernel averages keep their
+// meaning), launched always; they exit at once, before any LDS work, unless
+// the compare kernel raised *run_if.  The chars kernel first puts apply's
+// error word and exception count back to what the job reset left.
+extern "C" __global__ void bqsr_redo_chars(ApplyParams P, uint8_t* chars) {
+  if (!*P.run_if) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *P.err = kNoError;
+    *P.n_exc = 0ull;
+    *P.redo_mark = 1u;
+  }
+  apply_chars_body(P, chars);
+}
+extern "C" __global__ void __launch_bounds__(kBlockThreads) bqsr_redo_apply(ApplyParams P) {
+  if (!*P.run_if) return;
+  apply_body(P);
+}
 
 
 // RecalTable.++ over partitions in a declared order (RecalTable.scala:90-108):
@@ -2707,12 +2727,88 @@ extern "C" __global__ void bqsr_job_reset_kernel(int64_t* words, int64_t n, unsi
   if (blockIdx.x == 0 && threadIdx.x < kErrWords) err[threadIdx.x] = threadIdx.x == kNExc ? 0ull : ~0ull;
 }
 // [0, kErrWords) error words, [kErrWords] expectedMismatch bits, then FinalOut
+// then whether a speculative tail ran apply again (tail null: no such tail)
 extern "C" __global__ void bqsr_job_status_kernel(const unsigned long long* err, const double* em, const FinalOut* fo,
-                                                  uint64_t* host) {
+                                                  const uint32_t* tail, uint64_t* host) {
   const int t = threadIdx.x;
   if (t < kErrWords) host[t] = err[t];
   else if (t == kErrWords) host[t] = (uint64_t)__double_as_longlong(*em);
   else if (t < kErrWords + 1 + (int)(sizeof(FinalOut) / 8)) host[t] = ((const uint64_t*)fo)[t - kErrWords - 1];
+  else if (t == kErrWords + 1 + (int)(sizeof(FinalOut) / 8)) host[t] = tail ? tail[kTailRan] : 0u;
+}
+
+// ------------------------------------------------ speculative job tail ----
+// bqsr_job_tail_async (bqsr_capi.cpp): apply's tables depend on the job's
+// exact expectedMismatch almost only through rounding (a2 = a1 + (v_k - a1)
+// with avg = em / g_obs inside a1), so apply starts on tables finalized from
+// an estimate while the exact fold runs beside it.
+
+// One workgroup, before the speculative finalize: em_spec = scale * sum over
+// the fold blocks' qual histograms of count * pow10 (the real sum
+// bqsr_fold_plan bounds the exact one by), the set of bins holding a base
+// (FoldParams::qmask, which apply's prologue needs), and the tail's words and
+// the char tables' bad-row bits (rowbad: the speculative and the redo's) zeroed.
+extern "C" __global__ void __launch_bounds__(1024) bqsr_tail_estimate(const uint32_t* hq_block, int32_t n_blocks,
+                                                                       const double* pow10, double scale,
+                                                                       double* em_spec, uint32_t* qmask, uint32_t* tail,
+                                                                       uint32_t* rowbad, int32_t rowbad_words) {
+  __shared__ unsigned long long cnt[32][kQBins + 4];
+  __shared__ double wsum[16];
+  const int tid = threadIdx.x, part = tid & 31, row0 = tid >> 5;  // 32 threads a histogram row, 4 bins each
+  unsigned long long c[4] = {0, 0, 0, 0};
+  for (int b = row0; b < n_blocks; b += 32) {
+    const uint4 v = *(const uint4*)(hq_block + (int64_t)b * kQBins + part * 4);
+    c[0] += v.x;
+    c[1] += v.y;
+    c[2] += v.z;
+    c[3] += v.w;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) cnt[row0][part * 4 + i] = c[i];
+  if (tid < kTailWords) tail[tid] = 0u;
+  for (int i = tid; i < rowbad_words; i += blockDim.x) rowbad[i] = 0u;
+  __syncthreads();
+  double v = 0.0;
+  bool used = false;
+  if (tid < kQBins) {
+    unsigned long long n = 0;
+    for (int r = 0; r < 32; ++r) n += cnt[r][tid];
+    used = n != 0;
+    v = (double)n * pow10[tid];
+  }
+  const uint64_t um = __builtin_amdgcn_ballot_w64(used);
+  if (tid < kQBins && (tid & 63) == 0) {
+    qmask[tid >> 5] = (uint32_t)um;
+    qmask[(tid >> 5) + 1] = (uint32_t)(um >> 32);
+  }
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  if ((tid & 63) == 0) wsum[tid >> 6] = v;
+  __syncthreads();
+  if (tid == 0) *em_spec = (wsum[0] + wsum[1]) * scale;
+}
+
+// After the exact finalize: a workgroup per (rg, q) row whose exact a2 differs
+// in its bits from the speculative one (a NaN equals itself; a row not in the
+// table is 0.0 in both) checks that every char apply could have taken from the
+// row, errorProbabilityToPhred(s1[c] + d2[x]) over every cycle cell and
+// context, is the same in both versions, and raises the redo word if not.
+// key_ok, grp_ok, rq_ok and the threshold tables do not depend on
+// expectedMismatch.  force: the verification counts as failed (tests).
+extern "C" __global__ void __launch_bounds__(256) bqsr_tail_compare(ApplyParams P, const double* a2, const double* a2s,
+                                                                     const double* s1s, const double* d2s, int32_t force,
+                                                                     uint32_t* tail) {
+  const int64_t rq = blockIdx.x;
+  if (force && rq == 0 && threadIdx.x == 0) atomicOr(&tail[kTailRedo], 1u);
+  if (!P.rq_ok[rq] || __double_as_longlong(a2[rq]) == __double_as_longlong(a2s[rq])) return;
+  const int C = P.g.C;
+  bool diff = false;
+  for (int i = threadIdx.x; i < C * kCtxSlots; i += blockDim.x) {
+    const int c = i / kCtxSlots, x = i - c * kCtxSlots;
+    const int32_t qa = phred_q(P.s1[rq * C + c] + P.d2[rq * kCtxSlots + x], P.qb_thr, P.qb_q, P.thr, P.thr_qmin, P.thr_n);
+    const int32_t qb = phred_q(s1s[rq * C + c] + d2s[rq * kCtxSlots + x], P.qb_thr, P.qb_q, P.thr, P.thr_qmin, P.thr_n);
+    diff |= qa != qb;
+  }
+  if (__builtin_amdgcn_ballot_w64(diff) && (threadIdx.x & 63) == 0) atomicOr(&tail[kTailRedo], 1u);
 }
 
 // Multi-rank error exchange (every rank raises the job's first error in global

@@ -18,6 +18,13 @@ ranks' shards, in rank order).  One ``step``:
    on its first failing partition;
 7. the job's errors, in the order the reference raises them (one transfer, one sync).
 
+On one rank and without stage brackets, steps 2 (from the fold on) to 5 are
+one call, bqsr_job_tail_async: on a read-order batch apply starts on tables
+finalized from an estimate of expectedMismatch while the exact fold runs on
+a second stream, and is verified (and redone on the device if need be)
+afterwards -- the results are the serial schedule's bit for bit
+(``tail_path`` says which ran).
+
 Only the HIP library computes; this module orders launches.
 """
 from __future__ import annotations
@@ -90,6 +97,7 @@ class ResidentJob:
         self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         self.kt: Dict[str, List[float]] = {k: [] for k in self.STAGES}
         self.n_exc = 0
+        self.tail_path = 0
         self.em = None  # the job's expectedMismatch (device, 1 double) of the last step
         torch.cuda.synchronize(self.dev)
 
@@ -125,8 +133,44 @@ class ResidentJob:
         mark(5)
         check(L.bqsr_observe_stage(ctx, bh, self.sites_h, th, _capi.STAGE_PREP, sp))
         mark(0)
-        check(L.bqsr_observe_stage(ctx, bh, self.sites_h, th, _capi.STAGE_KERNEL, sp))
+        # one rank, no stage brackets: the observe kernel forks the fold off
+        # and bqsr_job_tail_async runs fold, finalize and apply -- apply at once
+        # on tables from an estimate of expectedMismatch beside the exact fold
+        # (a read-order batch; serial otherwise).  record=True keeps the serial
+        # stage calls below, so its brackets mean what they did.
+        tail = not record and self.world == 1
+        check(L.bqsr_observe_stage(ctx, bh, self.sites_h, th, _capi.STAGE_KERNEL | (_capi.STAGE_FORK if tail else 0), sp))
         mark(1)
+        args = (self._ptr(self.out_qual), self._ptr(self.out_start), self._ptr(self.out_len), self._ptr(self.exc),
+                self.max_exc)
+        if tail:
+            self.em = None
+            check(L.bqsr_job_tail_async(ctx, bh, self.sites_h, th, ctypes.byref(self.lut), *args, sp))
+        else:
+            self._serial_tail(record, mark, args)
+        if self.world > 1:
+            check(L.bqsr_job_errors_export_async(bh, self.read_base, self._ptr(self.err_keys), sp))
+            D.allreduce_error_keys(self.err_keys)
+            check(L.bqsr_job_errors_import_async(bh, self._ptr(self.err_keys), sp))
+        # the job's results and errors, in the order the reference raises them
+        # (one transfer and one sync)
+        em = ctypes.c_double()
+        nexc = ctypes.c_int64()
+        st = L.bqsr_job_result(bh, self.lut, ctypes.byref(em), ctypes.byref(nexc), sp)
+        self.tail_path = int(L.bqsr_job_tail_path(bh))  # 0 serial, 1 speculative, 2 speculative and apply redone
+        check(st)
+        self.n_exc = int(nexc.value)
+        if self.n_exc > self.max_exc:
+            raise _capi.BQSRError(_capi.UNSUPPORTED, "%d chars above 0xFF exceed the exception list" % self.n_exc)
+        if record:
+            self.kt["prep"].append(ev[5].elapsed_time(ev[0]))
+            self.kt["observe"].append(ev[0].elapsed_time(ev[1]))
+            self.kt["fold"].append(ev[1].elapsed_time(ev[2]))
+            self.kt["apply"].append(ev[3].elapsed_time(ev[4]))
+
+    def _serial_tail(self, record, mark, outs):
+        """fold, (N > 1: all-reduce,) finalize, apply as stage calls on the stream"""
+        L, ctx, bh, th, sp, stream = self.L, self.ctx.handle, self.bh, self.th, self.sp, self.stream
         check(L.bqsr_observe_stage(ctx, bh, self.sites_h, th, _capi.STAGE_FOLD, sp))
         mark(2)
         if self.world > 1:
@@ -141,8 +185,7 @@ class ResidentJob:
             self.em = None
             em_ptr = ctypes.c_void_p(L.bqsr_batch_em_device_ptr(bh))
         check(L.bqsr_finalize_device(ctx, th, em_ptr, ctypes.byref(self.lut), sp))
-        args = (ctx, bh, self.lut, self._ptr(self.out_qual), self._ptr(self.out_start), self._ptr(self.out_len),
-                self._ptr(self.exc), self.max_exc)
+        args = (ctx, bh, self.lut) + outs
         if record:  # the char tables first, so the bracket holds the apply kernel alone
             check(L.bqsr_apply_stage(*args, _capi.STAGE_LUT, sp))
             mark(3)
@@ -150,23 +193,6 @@ class ResidentJob:
             mark(4)
         else:
             check(L.bqsr_apply_stage(*args, _capi.STAGE_KERNEL, sp))
-        if self.world > 1:
-            check(L.bqsr_job_errors_export_async(bh, self.read_base, self._ptr(self.err_keys), sp))
-            D.allreduce_error_keys(self.err_keys)
-            check(L.bqsr_job_errors_import_async(bh, self._ptr(self.err_keys), sp))
-        # the job's results and errors, in the order the reference raises them
-        # (one transfer and one sync)
-        em = ctypes.c_double()
-        nexc = ctypes.c_int64()
-        check(L.bqsr_job_result(bh, self.lut, ctypes.byref(em), ctypes.byref(nexc), sp))
-        self.n_exc = int(nexc.value)
-        if self.n_exc > self.max_exc:
-            raise _capi.BQSRError(_capi.UNSUPPORTED, "%d chars above 0xFF exceed the exception list" % self.n_exc)
-        if record:
-            self.kt["prep"].append(ev[5].elapsed_time(ev[0]))
-            self.kt["observe"].append(ev[0].elapsed_time(ev[1]))
-            self.kt["fold"].append(ev[1].elapsed_time(ev[2]))
-            self.kt["apply"].append(ev[3].elapsed_time(ev[4]))
 
     def kernel_ms(self) -> Dict[str, float]:
         return {k: float(np.mean(v)) if v else float("nan") for k, v in self.kt.items()}

@@ -164,7 +164,19 @@ void bqsr_context_destroy(bqsr_context* ctx);
  *   BQSR_TUNE_PILEUP_GRID 0 auto, g > 0: at most g workgroups for the two
  *                        pileup kernels (adam_sam.h bqsr_sam_pileup_*) and for
  *                        every mpileup kernel (bqsr_sam_mpileup_*), as
- *                        BQSR_TUNE_FLAGSTAT_GRID */
+ *                        BQSR_TUNE_FLAGSTAT_GRID
+ *   BQSR_TUNE_SPEC_TAIL  bqsr_job_tail_async on a read-order batch:
+ *                        1 (default) apply starts on tables built from an
+ *                        estimate of expectedMismatch while the exact fold
+ *                        runs beside it, and is verified afterwards;
+ *                        0 the serial schedule (fold, finalize, apply);
+ *                        2 as 1 with the verification treated as failed, so
+ *                        apply always runs again on the exact tables (tests);
+ *                        3 as 1 with the estimate multiplied by 1.5 (tests).
+ *                        Takes effect on the next job.
+ *   BQSR_TUNE_SPEC_RESERVE k in 1..64 (default 8, one per XCD): the
+ *                        speculative apply runs on (CUs - k) workgroups, so
+ *                        the fold's kernels find a CU beside it */
 enum {
   BQSR_TUNE_ORDER = 1,
   BQSR_TUNE_FRONTS = 2,
@@ -172,7 +184,9 @@ enum {
   BQSR_TUNE_FUSED_PREP = 4,
   BQSR_TUNE_BGZF = 5,
   BQSR_TUNE_FLAGSTAT_GRID = 6,
-  BQSR_TUNE_PILEUP_GRID = 7
+  BQSR_TUNE_PILEUP_GRID = 7,
+  BQSR_TUNE_SPEC_TAIL = 8,
+  BQSR_TUNE_SPEC_RESERVE = 9
 };
 bqsr_status bqsr_context_tune(bqsr_context* ctx, int knob, int64_t value);
 
@@ -323,7 +337,7 @@ bqsr_status bqsr_apply_records(bqsr_context* ctx, const bqsr_records* recs, cons
  * so a driver can keep a whole BQSR job on the device (the benchmark and the
  * multi-GPU path use them; RCCL collectives go between the stages). */
 enum { BQSR_STAGE_RESET = 1, BQSR_STAGE_KERNEL = 2, BQSR_STAGE_FOLD = 4, BQSR_STAGE_PREP = 8,
-       BQSR_STAGE_LUT = 16, BQSR_STAGE_NO_LUT = 32 };
+       BQSR_STAGE_LUT = 16, BQSR_STAGE_NO_LUT = 32, BQSR_STAGE_FORK = 64 };
 /* apply stages: RESET clears its error words, KERNEL builds the pieces' char
  * tables (bqsr_apply_chars) and runs the apply kernel; LUT builds the char
  * tables only, KERNEL | NO_LUT runs the kernel on tables an earlier LUT
@@ -331,7 +345,10 @@ enum { BQSR_STAGE_RESET = 1, BQSR_STAGE_KERNEL = 2, BQSR_STAGE_FOLD = 4, BQSR_ST
 /* observe stages: RESET clears the error word, PREP is the per-read prep
  * kernel (trimming, CIGAR/MD/known-site masks, validation), KERNEL the
  * observe kernel, FOLD the expectedMismatch fold (result at
- * bqsr_batch_em_device_ptr). */
+ * bqsr_batch_em_device_ptr).  KERNEL | FORK (read-order batches, with
+ * BQSR_TUNE_SPEC_TAIL on; ignored otherwise) records the batch's fork event
+ * between the observe kernel and its window reduce, for a
+ * bqsr_job_tail_async that follows on the same stream. */
 bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* sites, bqsr_table* t,
                                int32_t stages, void* stream);
 bqsr_status bqsr_observe_async(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* sites, bqsr_table* t,
@@ -409,6 +426,10 @@ bqsr_status bqsr_batch_fold_stats(bqsr_batch* b, bqsr_fold_stats* out, void* str
 int64_t bqsr_batch_slots(const bqsr_batch* b);
 /* read-group counts of a finalized table, group r at (r >= -1): 1 found, 0 absent, -1 error */
 int bqsr_lut_group(const bqsr_lut* l, int32_t r, int64_t* obs, int64_t* mm);
+/* the device apply tables of a finalized table copied to the host, after
+ * waiting for the device (no reference counterpart: for tests): a2 [n_rg * 128],
+ * s1 [n_rg * 128][2 * max_len + 1], d2 [n_rg * 128][21]; any may be NULL */
+bqsr_status bqsr_lut_tables(const bqsr_lut* l, double* a2, double* s1, double* d2);
 /* the errorProbabilityToPhred threshold table the apply kernel uses:
  * out[i] = largest p with phred(p) >= qmin + i; returns the entry count */
 int32_t bqsr_phred_threshold_table(double* out, int32_t cap, int32_t* qmin);
@@ -450,6 +471,23 @@ const void* bqsr_batch_exception_count_ptr(const bqsr_batch* b);
 bqsr_status bqsr_job_reset_async(bqsr_batch* b, bqsr_table* t, void* stream);
 bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* l, double* expected_mismatch, int64_t* n_exceptions,
                             void* stream);
+/* The job's tail after the PREP and KERNEL (| FORK) observe stages of a
+ * one-rank resident job: the expectedMismatch fold, finalize into *lut (as
+ * bqsr_finalize_device with the batch's own expectedMismatch) and apply, on
+ * `stream` without a host round trip.  On a read-order batch with
+ * BQSR_TUNE_SPEC_TAIL on, apply starts at once on tables finalized from a
+ * real-sum estimate of expectedMismatch while the exact fold runs on the
+ * batch's side stream; afterwards the exact tables are built (*lut is exactly
+ * what the serial schedule leaves), compared with the speculative ones, and
+ * apply runs again on the device if any recalibrated char could differ.
+ * Results are those of the serial schedule bit for bit.  Bucketed batches,
+ * empty batches and BQSR_TUNE_SPEC_TAIL 0 take the serial schedule.
+ * bqsr_job_tail_path, after bqsr_job_result: 0 the serial schedule, 1
+ * speculative and accepted, 2 speculative and apply run again. */
+bqsr_status bqsr_job_tail_async(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* sites, bqsr_table* t,
+                                bqsr_lut** lut, uint8_t* out_qual, uint32_t* out_start, uint32_t* out_len,
+                                uint64_t* exceptions, int64_t max_exceptions, void* stream);
+int32_t bqsr_job_tail_path(const bqsr_batch* b);
 /* Multi-rank jobs (one partition per rank, in rank order): the reference's
  * job fails with the first error of the first failing partition
  * (RecalibrateBaseQualities.scala:63,75 -- a Spark job aborts on its first
