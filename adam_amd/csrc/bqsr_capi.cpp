@@ -57,6 +57,8 @@ bqsr_status ok() {
       return fail(BQSR_ERR_DEVICE, std::string(#expr " failed: ") + hipGetErrorString(e_));    \
   } while (0)
 
+// readGroupCounts.values.reduce on an empty map (RecalTable.scala:123)
+bqsr_status empty_table() { return fail(BQSR_ERR_EMPTY_TABLE, "empty.reduceLeft: no usable base was observed"); }
 hipStream_t S(void* s) { return s ? (hipStream_t)s : hipStreamPerThread; }
 
 const char* kStatusNames[] = {"OK",          "NULL_RG",      "MD_PARSE",       "CIGAR_SHORT", "BAD_REVCOMP_BASE",
@@ -312,6 +314,25 @@ bqsr_status upload_staged(bqsr_context* ctx, void* dst, const void* src, size_t 
   HIP_TRY(hipStreamSynchronize(s));
   return BQSR_OK;
 }
+// a device buffer that only grows: the commands' with dev_need (device_job.h), the core's with grow, which drains
+// `s` before it frees, because work queued there may still read the old buffer
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+bqsr_status grow(DevBuf& buf, size_t bytes, hipStream_t s) {
+  if (buf.cap >= bytes) return BQSR_OK;
+  if (buf.p) {
+    HIP_TRY(hipStreamSynchronize(s));
+    (void)hipFree(buf.p);
+    buf.p = nullptr;
+    buf.cap = 0;
+  }
+  HIP_TRY(hipMalloc(&buf.p, bytes));
+  buf.cap = bytes;
+  return BQSR_OK;
+}
 }  // namespace
 
 struct bqsr_sites {
@@ -362,13 +383,10 @@ struct bqsr_batch {
   uint32_t* d_qmask = nullptr;     // [4] their bins holding a base (bqsr_fold_plan)
   bool hq_valid = false;           // d_qmask written by a fold of this batch (its quals and trims are fixed)
   FoldParams fold{};               // the fold's device buffers (FoldParams)
-  uint32_t* d_part = nullptr;      // per-block window counts
-  size_t part_words = 0;
-  uint8_t* d_chars = nullptr;      // apply: the pieces' char tables (ApplyParams::chars)
+  DevBuf part;                     // u32 per-block window counts (grow: with the table geometry)
+  DevBuf chars;                    // apply: the pieces' char tables (ApplyParams::chars) and the bad-row words
   const bqsr_lut* chars_lut = nullptr;  // the LUT they were built from (BQSR_STAGE_LUT)
-  uint64_t* d_off64 = nullptr;     // bqsr_compact_outputs_async scratch (lengths, scan)
-  int64_t off64_n = -1;
-  size_t chars_bytes = 0;
+  DevBuf off64;                    // bqsr_compact_outputs_async scratch (u64 lengths, scan)
   unsigned long long* d_err = nullptr;  // [kErrWords]: observe, apply-prep, apply-kernel errors, exception count
   double* d_em = nullptr;
   int32_t n_blocks = 0;
@@ -427,9 +445,6 @@ struct bqsr_batch {
     if (side) (void)hipStreamDestroy(side);
     for (hipEvent_t e : {ev_obs, ev_fold, ev_tiles})
       if (e) (void)hipEventDestroy(e);
-    if (d_part) (void)hipFree(d_part);
-    if (d_off64) (void)hipFree(d_off64);
-    if (d_chars) (void)hipFree(d_chars);
     if (h_status) (void)hipHostFree(h_status);
     for (void* p : allocs) (void)hipFree(p);
   }
@@ -1504,6 +1519,9 @@ bqsr_status check_dims(const bqsr_batch* b, const bqsr_table* t) {
 //   BQSR_STAGE_FOLD    the expectedMismatch fold kernel
 // Exposed separately so a caller can bracket one kernel with HIP events.
 namespace {
+// Each stage's launch sequence once, on the stream it is given; the stage functions and bqsr_job_tail_async
+// compose them.  static: inside extern "C" this namespace's names are exported (launch_prep,
+// fold_params), and that list stays as it was.
 // the fold's parameters for this batch; qmask: bqsr_fold_plan writes the set of
 // folded qual bins (the speculative tail's estimate kernel writes it instead)
 FoldParams fold_params(const bqsr_context* ctx, const bqsr_batch* b, bool qmask) {
@@ -1516,6 +1534,19 @@ FoldParams fold_params(const bqsr_context* ctx, const bqsr_batch* b, bool qmask)
   F.em_out = b->d_em;
   F.qmask = qmask ? b->d_qmask : nullptr;
   return F;
+}
+// the four fold kernels; ev_tiles, when given, is recorded after bqsr_fold_tiles
+static bqsr_status launch_fold(const bqsr_context* ctx, bqsr_batch* b, hipStream_t s, bool qmask, hipEvent_t ev_tiles) {
+  const FoldParams F = fold_params(ctx, b, qmask);
+  hipLaunchKernelGGL(bqsr_fold_plan, dim3(1), dim3(1024), 0, s, F);
+  const int64_t max_tpb = (b->rd.n_tiles + b->n_blocks - 1) / b->n_blocks + 1;
+  hipLaunchKernelGGL(bqsr_fold_tiles, dim3(ctx->n_cu * 4), dim3(kFtWaves * 64), 0, s, F, max_tpb);
+  if (ev_tiles) HIP_TRY(hipEventRecord(ev_tiles, s));
+  hipLaunchKernelGGL(bqsr_fold_segs, dim3(b->n_blocks), dim3(kSegThreads), 0, s, F);
+  hipLaunchKernelGGL(bqsr_fold_chain, dim3(1), dim3(1024), chain_lds(b->n_blocks), s, F);
+  HIP_TRY(hipGetLastError());
+  b->hq_valid = true;
+  return BQSR_OK;
 }
 bqsr_status launch_prep(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* sites, hipStream_t s) {
   if (!b->err_fresh) HIP_TRY(hipMemsetAsync(b->d_err + kErrAppPrep, 0xFF, 8, s));  // (else the job reset did)
@@ -1561,6 +1592,78 @@ bqsr_status launch_prep(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* site
   b->prep_sites = sites;
   return BQSR_OK;
 }
+// the observe kernel's parameters (all but the slabs, launch_observe): the choice of the window geometry
+static ObserveParams observe_params(const bqsr_batch* b, const bqsr_table* t) {
+  ObserveParams P{};
+  P.rd = b->pass_rd();
+  P.ord = b->order();
+  P.info = b->d_info;
+  P.sbits = b->d_sbits;
+  P.g = geom(t->dims);
+  // window row length padded to 2 mod 4 words: the lanes of a wavefront add
+  // to one cycle cell of many rows at once, which a row length sharing a
+  // factor 4 or more with the 32 banks folds onto few banks (cfg3, 224
+  // words: 7.6 ms observe; 225: 5.8; cfg2 222 against 223 / 224: 0.94 /
+  // 1.00 / 1.25 ms).  Pad words stay 0.
+  // Read order: the lean lane per read (bqsr_observe_lean.hip); bucketed
+  // batches: the lane-per-chunk walk (cfg4 observe 4.51 ms against the lean
+  // form's 6.42, profiles/r03w_cfg4_lean_bucketed_ab.txt).  Measured and
+  // removed (round 3, in git history): the round-2 lane per read, lanes per
+  // super-chunk and the lane-per-offset rows kernel (SALU-bound, 6.0 ms cfg2).
+  const bool lean = !b->bucketed;
+  P.wcells = window_cw(b, P.g) + (lean ? kCtxCells : kCtxSlots);
+  while ((P.wcells & 3) != 2) ++P.wcells;  // (chunk walk, cfg4: 0 mod 4 5.72 ms, 1 mod 4 4.32, 2 mod 4 4.34)
+  if (lean) {
+    const int cw = window_cw(b, P.g), span = qual_span(b);
+    int best_rows = 0;
+    for (int nc = kLeanCopiesMax; nc >= 1 && best_rows < span; --nc) {
+      const int orow = lean_orow(nc, cw);
+      int qw = kQBins;
+      while (qw > 1 && lean_lds(qw, orow, P.wcells) > kLdsMax) --qw;
+      if (qw > best_rows) {
+        best_rows = qw;
+        P.nc = nc;
+        P.orow = orow;
+      }
+    }
+    P.w = window_rows(b, best_rows);
+    // every qual of the batch a window row: the kernel skips the per-chunk row test
+    P.rows_all = b->have_qhist && b->qhigh == 0;
+    for (int q = 0; q < kQBins && P.rows_all; ++q)
+      if (b->qhist[q] && (q < P.w.q_lo || q >= P.w.q_lo + P.w.qw)) P.rows_all = 0;
+  } else {
+    P.w = window_rows(b, observe_rows(P.wcells, true));
+  }
+  P.touched = t->touched();
+  P.obs = t->obs();
+  P.mm = t->mm();
+  P.part_stride = 2 * P.w.qw * P.wcells + P.w.qw;
+  P.hq_block = b->d_hq;
+  P.err = b->d_err + kErrObs;
+  P.n_blocks = lean ? b->n_blocks : b->pass_blocks();  // (fronts: a chunk-walk workgroup per piece)
+  return P;
+}
+// the observe kernel into the batch's slabs (w + key) and bqsr_window_reduce from
+// them into the table; ev_fork, when given, is recorded between the two
+static bqsr_status launch_observe(bqsr_batch* b, ObserveParams P, hipEvent_t ev_fork, hipStream_t s) {
+  const bool lean = !b->bucketed;
+  const size_t lds = lean ? lean_lds(P.w.qw, P.orow, P.wcells) : observe_lds(P.w.qw, P.wcells, true);
+  const bqsr_status st = grow(b->part, (size_t)P.part_stride * (b->pass_blocks() + b->n_keys - 1) * sizeof(uint32_t), s);
+  if (st != BQSR_OK) return st;
+  P.part = (uint32_t*)b->part.p;
+  void (*kernel)(ObserveParams) = !lean                 ? bqsr_observe_chunks
+                                  : P.rd.slots_aligned ? bqsr_observe_lean<true, true>
+                                                       : bqsr_observe_lean<true, false>;
+  hipLaunchKernelGGL(kernel, dim3(P.n_blocks), dim3(kBlockThreads), lds, s, P);
+  HIP_TRY(hipGetLastError());
+  if (ev_fork) HIP_TRY(hipEventRecord(ev_fork, s));
+  const int rb = (int)std::min<int64_t>(4096, ((int64_t)P.part_stride * (b->bucketed ? b->n_base : 1) + 255) / 256);
+  const unsigned ry = b->bucketed ? 1u : (unsigned)((b->n_blocks + kRedSlabs - 1) / kRedSlabs);
+  hipLaunchKernelGGL(bqsr_window_reduce, dim3(rb, ry), dim3(256), 0, s, (const uint32_t*)P.part, b->rd, P.ord,
+                     P.n_blocks, P.part_stride, P.wcells, P.w, P.g, P.touched, P.obs, P.mm, lean ? kCtxJunk : 0);
+  HIP_TRY(hipGetLastError());
+  return BQSR_OK;
+}
 }  // namespace
 
 bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_sites* sites, bqsr_table* t,
@@ -1571,9 +1674,7 @@ bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_site
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
   if (stages & BQSR_STAGE_RESET) HIP_TRY(hipMemsetAsync(b->d_err + kErrObs, 0xFF, 8, s));
-  if (stages & BQSR_STAGE_PREP) {
-    if ((st = launch_prep(ctx, b, sites, s)) != BQSR_OK) return st;
-  }
+  if ((stages & BQSR_STAGE_PREP) && (st = launch_prep(ctx, b, sites, s)) != BQSR_OK) return st;
   if (b->rd.n_reads == 0) {
     if (stages & BQSR_STAGE_FOLD) HIP_TRY(hipMemsetAsync(b->d_em, 0, 8, s));
     return ok();
@@ -1581,50 +1682,7 @@ bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_site
   if ((stages & BQSR_STAGE_KERNEL) && (!b->prepped || b->prep_sites != sites))
     return fail(BQSR_ERR_INVALID_ARG, "observe kernel before the prep stage (or with other known sites)");
   if (stages & BQSR_STAGE_KERNEL) {
-    ObserveParams P{};
-    P.rd = b->pass_rd();
-    P.ord = b->order();
-    P.info = b->d_info;
-    P.sbits = b->d_sbits;
-    P.g = geom(t->dims);
-    // window row length padded to 2 mod 4 words: the lanes of a wavefront add
-    // to one cycle cell of many rows at once, which a row length sharing a
-    // factor 4 or more with the 32 banks folds onto few banks (cfg3, 224
-    // words: 7.6 ms observe; 225: 5.8; cfg2 222 against 223 / 224: 0.94 /
-    // 1.00 / 1.25 ms).  Pad words stay 0.
-    // Read order: the lean lane per read (bqsr_observe_lean.hip); bucketed
-    // batches: the lane-per-chunk walk (cfg4 observe 4.51 ms against the lean
-    // form's 6.42, profiles/r03w_cfg4_lean_bucketed_ab.txt).  Measured and
-    // removed (round 3, in git history): the round-2 lane per read, lanes per
-    // super-chunk and the lane-per-offset rows kernel (SALU-bound, 6.0 ms cfg2).
-    const bool lean = !b->bucketed;
-    P.wcells = window_cw(b, P.g) + (lean ? kCtxCells : kCtxSlots);
-    while ((P.wcells & 3) != 2) ++P.wcells;  // (chunk walk, cfg4: 0 mod 4 5.72 ms, 1 mod 4 4.32, 2 mod 4 4.34)
-    if (lean) {
-      const int cw = window_cw(b, P.g), span = qual_span(b);
-      int best_rows = 0;
-      for (int nc = kLeanCopiesMax; nc >= 1 && best_rows < span; --nc) {
-        const int orow = lean_orow(nc, cw);
-        int qw = kQBins;
-        while (qw > 1 && lean_lds(qw, orow, P.wcells) > kLdsMax) --qw;
-        if (qw > best_rows) {
-          best_rows = qw;
-          P.nc = nc;
-          P.orow = orow;
-        }
-      }
-      P.w = window_rows(b, best_rows);
-      // every qual of the batch a window row: the kernel skips the per-chunk row test
-      P.rows_all = b->have_qhist && b->qhigh == 0;
-      for (int q = 0; q < kQBins && P.rows_all; ++q)
-        if (b->qhist[q] && (q < P.w.q_lo || q >= P.w.q_lo + P.w.qw)) P.rows_all = 0;
-    } else {
-      P.w = window_rows(b, observe_rows(P.wcells, true));
-    }
-    P.touched = t->touched();
-    P.obs = t->obs();
-    P.mm = t->mm();
-    P.part_stride = 2 * P.w.qw * P.wcells + P.w.qw;
+    const ObserveParams P = observe_params(b, t);
     // bucketed: bqsr_fold_hist makes the fold's histograms from prep's trims,
     // so the fold runs beside the observe kernel (cfg4: 1.4 ms of fold_hist
     // and 0.8 ms of fold hidden, the observe kernel 1.6 ms slower beside
@@ -1633,53 +1691,19 @@ bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_site
     // the price of two event records (~15 us each on this runtime)
     // BQSR_STAGE_FORK (read order, speculative tail on): the fork event after
     // the observe kernel, taken by bqsr_job_tail_async
-    const bool tail_fork = lean && (stages & BQSR_STAGE_FORK) && ctx->tune_spec_tail != 0;
-    if ((!lean || tail_fork) && !b->side) {
+    const bool tail_fork = !b->bucketed && (stages & BQSR_STAGE_FORK) && ctx->tune_spec_tail != 0;
+    if ((b->bucketed || tail_fork) && !b->side) {  // either schedule's side stream and events
       HIP_TRY(hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&b->ev_obs, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&b->ev_fold, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&b->ev_tiles, hipEventDisableTiming));
+      for (hipEvent_t* e : {&b->ev_obs, &b->ev_fold, &b->ev_tiles})
+        HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
-    if (!lean) {
+    if (b->bucketed) {
       HIP_TRY(hipEventRecord(b->ev_obs, s));
       b->obs_pending = true;
     }
     b->tail_fork = false;
-    // slabs w + key
-    const size_t need = (size_t)P.part_stride * (b->pass_blocks() + b->n_keys - 1);
-    if (b->part_words < need) {  // grows with the table geometry; kept across calls
-      if (b->d_part) {
-        HIP_TRY(hipStreamSynchronize(s));
-        (void)hipFree(b->d_part);
-        b->d_part = nullptr;
-        b->part_words = 0;
-      }
-      HIP_TRY(hipMalloc((void**)&b->d_part, need * sizeof(uint32_t)));
-      b->part_words = need;
-    }
-    P.part = b->d_part;
-    P.hq_block = b->d_hq;
-    P.err = b->d_err + kErrObs;
-    P.n_blocks = lean ? b->n_blocks : b->pass_blocks();  // (fronts: a chunk-walk workgroup per piece)
-    const size_t lds = lean ? lean_lds(P.w.qw, P.orow, P.wcells) : observe_lds(P.w.qw, P.wcells, true);
-    if (lean) {
-      if (P.rd.slots_aligned)
-        hipLaunchKernelGGL((bqsr_observe_lean<true, true>), dim3(P.n_blocks), dim3(kBlockThreads), lds, s, P);
-      else
-        hipLaunchKernelGGL((bqsr_observe_lean<true, false>), dim3(P.n_blocks), dim3(kBlockThreads), lds, s, P);
-    } else {
-      hipLaunchKernelGGL(bqsr_observe_chunks, dim3(P.n_blocks), dim3(kBlockThreads), lds, s, P);
-    }
-    HIP_TRY(hipGetLastError());
-    if (tail_fork) {
-      HIP_TRY(hipEventRecord(b->ev_obs, s));
-      b->tail_fork = true;
-    }
-    const int rb = (int)std::min<int64_t>(4096, ((int64_t)P.part_stride * (b->bucketed ? b->n_base : 1) + 255) / 256);
-    const unsigned ry = b->bucketed ? 1u : (unsigned)((b->n_blocks + kRedSlabs - 1) / kRedSlabs);
-    hipLaunchKernelGGL(bqsr_window_reduce, dim3(rb, ry), dim3(256), 0, s, (const uint32_t*)b->d_part, b->rd, P.ord,
-                       P.n_blocks, P.part_stride, P.wcells, P.w, P.g, P.touched, P.obs, P.mm, lean ? kCtxJunk : 0);
-    HIP_TRY(hipGetLastError());
+    if ((st = launch_observe(b, P, tail_fork ? b->ev_obs : nullptr, s)) != BQSR_OK) return st;
+    b->tail_fork = tail_fork;
   }
   if (stages & BQSR_STAGE_FOLD) {
     // bucketed: on the side stream after prep, concurrent with the observe
@@ -1702,14 +1726,7 @@ bqsr_status bqsr_observe_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_site
     }
     b->tail_fork = false;  // (a fork event nobody took: the serial schedule)
     b->tail_spec = false;
-    const FoldParams F = fold_params(ctx, b, true);
-    hipLaunchKernelGGL(bqsr_fold_plan, dim3(1), dim3(1024), 0, s, F);
-    const int64_t max_tpb = (b->rd.n_tiles + b->n_blocks - 1) / b->n_blocks + 1;
-    hipLaunchKernelGGL(bqsr_fold_tiles, dim3(ctx->n_cu * 4), dim3(kFtWaves * 64), 0, s, F, max_tpb);
-    hipLaunchKernelGGL(bqsr_fold_segs, dim3(b->n_blocks), dim3(kSegThreads), 0, s, F);
-    hipLaunchKernelGGL(bqsr_fold_chain, dim3(1), dim3(1024), chain_lds(b->n_blocks), s, F);
-    HIP_TRY(hipGetLastError());
-    b->hq_valid = true;
+    if ((st = launch_fold(ctx, b, s, true, nullptr)) != BQSR_OK) return st;
     if (fork) {
       HIP_TRY(hipEventRecord(b->ev_fold, s));
       HIP_TRY(hipStreamWaitEvent(caller, b->ev_fold, 0));
@@ -1812,34 +1829,40 @@ bqsr_status lut_for(bqsr_context* ctx, const bqsr_table* t, bqsr_lut** out, hipS
   *fresh = !reuse;
   return BQSR_OK;
 }
+// finalize's launches (their callers query the launch error): the table's per-key sums into the LUT,
+static void launch_final_keys(const bqsr_table* t, bqsr_lut* L, hipStream_t s) {
+  const TableGeom g = geom(t->dims);
+  hipLaunchKernelGGL(bqsr_final_keys, dim3((g.K + 3) / 4), dim3(256), 0, s, t->touched(), t->obs(), t->mm(), g, L->qk_obs, L->qk_mm);
+}
+// and the groups and tables a2 / s1 / d2 (the LUT's own or its speculative set) for em, or *em_dev when given
+static void launch_final_tables(const bqsr_context* ctx, const bqsr_table* t, bqsr_lut* L, double em, const double* em_dev,
+                                double* a2, double* s1, double* d2, hipStream_t s) {
+  const TableGeom g = geom(t->dims);
+  const int n_rg = t->dims.n_rg;
+  hipLaunchKernelGGL(bqsr_final_groups, dim3(1), dim3(256), 0, s, t->touched(), L->qk_obs, L->qk_mm, g, n_rg, em,
+                     em_dev, ctx->d_pow10, L->n_groups, L->grp_obs, L->grp_mm, L->grp_ok, L->key_ok, a2, L->rq_ok, L->d_out);
+  const int64_t ncell = (int64_t)n_rg * kQBins * (g.C + kCtxSlots);
+  hipLaunchKernelGGL(bqsr_final_tables, dim3((unsigned)std::min<int64_t>(8192, (ncell + 255) / 256)), dim3(256), 0, s,
+                     t->obs(), t->mm(), g, n_rg, a2, L->rq_ok, pow10tab().v[kMaxQ], s1, d2);
+}
 bqsr_status finalize_impl(bqsr_context* ctx, const bqsr_table* t, double em, const double* em_dev, bqsr_lut** out,
                           void* stream) {
   if (!ctx || !t || !out) return fail(BQSR_ERR_INVALID_ARG, "null");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
-  const TableGeom g = geom(t->dims);
-  const int n_rg = t->dims.n_rg;
   bqsr_lut* L = nullptr;
   bool fresh = false;
-  {
-    const bqsr_status st = lut_for(ctx, t, out, s, &L, &fresh);
-    if (st != BQSR_OK) return st;
-  }
-  const bool reuse = !fresh;
-  hipLaunchKernelGGL(bqsr_final_keys, dim3((g.K + 3) / 4), dim3(256), 0, s, t->touched(), t->obs(), t->mm(), g, L->qk_obs,
-                     L->qk_mm);
-  hipLaunchKernelGGL(bqsr_final_groups, dim3(1), dim3(256), 0, s, t->touched(), L->qk_obs, L->qk_mm, g, n_rg, em,
-                     em_dev, ctx->d_pow10, L->n_groups, L->grp_obs, L->grp_mm, L->grp_ok, L->key_ok, L->a2, L->rq_ok, L->d_out);
-  const int64_t ncell = (int64_t)n_rg * kQBins * (g.C + kCtxSlots);
-  hipLaunchKernelGGL(bqsr_final_tables, dim3((unsigned)std::min<int64_t>(8192, (ncell + 255) / 256)), dim3(256), 0, s,
-                     t->obs(), t->mm(), g, n_rg, L->a2, L->rq_ok, pow10tab().v[kMaxQ], L->s1, L->d2);
+  const bqsr_status st = lut_for(ctx, t, out, s, &L, &fresh);
+  if (st != BQSR_OK) return st;
+  launch_final_keys(t, L, s);
+  launch_final_tables(ctx, t, L, em, em_dev, L->a2, L->s1, L->d2, s);
   hipError_t e = hipGetLastError();
   // the device path (em in HBM) leaves `out` on the device: bqsr_job_result
   // fetches it with the job's other status words in one transfer
   L->out_pending = em_dev != nullptr;
   if (e == hipSuccess && !em_dev) e = hipMemcpyAsync(&L->out, L->d_out, sizeof(FinalOut), hipMemcpyDeviceToHost, s);
   if (e != hipSuccess) {
-    if (!reuse) delete L;
+    if (fresh) delete L;
     return fail(BQSR_ERR_DEVICE, hipGetErrorString(e));
   }
   *out = L;
@@ -1879,9 +1902,7 @@ bqsr_status bqsr_finalize_result(bqsr_lut* L, void* stream) {
     HIP_TRY(hipMemcpy(&L->out, L->d_out, sizeof(FinalOut), hipMemcpyDeviceToHost));
     L->out_pending = false;
   }
-  if (!L->out.any_key)  // readGroupCounts.values.reduce on an empty map (RecalTable.scala:123)
-    return fail(BQSR_ERR_EMPTY_TABLE, "empty.reduceLeft: no usable base was observed");
-  return ok();
+  return L->out.any_key ? ok() : empty_table();
 }
 
 bqsr_status bqsr_finalize(bqsr_context* ctx, const bqsr_table* t, double em, bqsr_lut** out) {
@@ -2017,13 +2038,17 @@ int32_t bqsr_phred_threshold_table(double* out, int32_t cap, int32_t* qmin) {
 // ---------------------------------------------------------------- apply ----
 
 namespace {
+// The batch's char-table buffer: a char table per base key (fronts share their read group's), tables_bytes; then
+// two sets of bad-row words, rowbad_bytes each, apply's and the speculative tail's redo's.  chars_extent: what
+// the chars kernels walk, the tables and the first set.
+static size_t tables_bytes(const ApplyParams& P, const bqsr_batch* b) { return (size_t)P.piece_stride * (size_t)b->n_base; }
+static size_t rowbad_bytes(const bqsr_batch* b) { return (size_t)b->n_base * 16; }
+static size_t chars_extent(const ApplyParams& P, const bqsr_batch* b) { return tables_bytes(P, b) + rowbad_bytes(b); }
 // apply's parameter block for this batch and LUT; the batch's char-table
 // buffer grows here when the window does
 bqsr_status apply_params(bqsr_context* ctx, bqsr_batch* b, const bqsr_lut* L, uint8_t* out_qual, uint32_t* out_start,
-                         uint32_t* out_len, uint64_t* exceptions, int64_t max_exceptions, void* stream,
-                         ApplyParams* out) {
+                         uint32_t* out_len, uint64_t* exceptions, int64_t max_exceptions, hipStream_t s, ApplyParams* out) {
   ApplyParams P{};
-  hipStream_t s = S(stream);
   P.rd = b->pass_rd();
   P.ord = b->order();
   P.info = b->d_info;
@@ -2052,24 +2077,32 @@ bqsr_status apply_params(bqsr_context* ctx, bqsr_batch* b, const bqsr_lut* L, ui
   P.n_exc = b->d_err + kNExc;
   P.err = b->d_err + kErrAppKern;
   P.piece_stride = piece_bytes(P.w.qw, cw);
-  // a char table per base key (fronts share their read group's)
-  const size_t need = (size_t)P.piece_stride * (size_t)b->n_base + (size_t)b->n_base * 32;  // + rowbad, and the speculative tail's redo's
-  if (b->chars_bytes < need) {  // grows with the window; kept across calls
-    if (b->d_chars) {
-      HIP_TRY(hipStreamSynchronize(s));
-      (void)hipFree(b->d_chars);
-      b->d_chars = nullptr;
-      b->chars_bytes = 0;
-    }
-    HIP_TRY(hipMalloc((void**)&b->d_chars, need));
-    b->chars_bytes = need;
-    b->chars_lut = nullptr;
-  }
-  P.chars = b->d_chars;
-  P.rowbad = (uint32_t*)(b->d_chars + (size_t)P.piece_stride * (size_t)b->n_base);
+  const size_t need = chars_extent(P, b) + rowbad_bytes(b);  // grows with the window
+  if (b->chars.cap < need) b->chars_lut = nullptr;          // (the tables move)
+  const bqsr_status st = grow(b->chars, need, s);
+  if (st != BQSR_OK) return st;
+  P.chars = (uint8_t*)b->chars.p;
+  P.rowbad = (uint32_t*)((uint8_t*)b->chars.p + tables_bytes(P, b));  // (the first set)
   P.qmask = b->hq_valid ? b->d_qmask : nullptr;
   *out = P;
   return BQSR_OK;
+}
+// the char tables of P's s1 / d2 (bqsr_apply_chars, or the redo's bqsr_redo_chars)
+static void launch_chars(const bqsr_context* ctx, const bqsr_batch* b, const ApplyParams& P,
+                         void (*kernel)(ApplyParams, uint8_t*), hipStream_t s) {
+  const unsigned cb = (unsigned)std::min<int64_t>(((int64_t)chars_extent(P, b) + 255) / 256, (int64_t)ctx->n_cu * 16);
+  hipLaunchKernelGGL(kernel, dim3(cb), dim3(256), 0, s, P, (uint8_t*)b->chars.p);
+}
+// the apply walk on `grid` workgroups (bqsr_apply_kernel, or the redo's bqsr_redo_apply); P.outs_apart: bqsr_apply_outs too
+static void launch_apply(const bqsr_context* ctx, const bqsr_batch* b, const ApplyParams& P, void (*kernel)(ApplyParams),
+                         int grid, hipStream_t s) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), apply_lds(P.w.qw, window_cw(b, P.g)), s, P);
+  if (P.outs_apart) {
+    ApplyParams Q = P;
+    Q.rd = b->rd;  // (read order: the batch's own qual column, where a read not yet trimmed is)
+    hipLaunchKernelGGL(bqsr_apply_outs, dim3((unsigned)std::min<int64_t>((b->rd.n_reads + 255) / 256, (int64_t)ctx->n_cu * 8)),
+                       dim3(256), 0, s, Q);
+  }
 }
 }  // namespace
 
@@ -2097,29 +2130,18 @@ bqsr_status bqsr_apply_stage(bqsr_context* ctx, bqsr_batch* b, const bqsr_lut* L
   }
   if (b->rd.n_reads == 0 || !(stages & (BQSR_STAGE_KERNEL | BQSR_STAGE_LUT))) return ok();
   ApplyParams P{};
-  {
-    const bqsr_status st = apply_params(ctx, b, L, out_qual, out_start, out_len, exceptions, max_exceptions, stream, &P);
-    if (st != BQSR_OK) return st;
-  }
-  const int cw = window_cw(b, P.g);
-  const size_t need = (size_t)P.piece_stride * (size_t)b->n_base + (size_t)b->n_base * 16;
+  const bqsr_status st = apply_params(ctx, b, L, out_qual, out_start, out_len, exceptions, max_exceptions, s, &P);
+  if (st != BQSR_OK) return st;
   const bool lut_stage = (stages & BQSR_STAGE_LUT) || ((stages & BQSR_STAGE_KERNEL) && !(stages & BQSR_STAGE_NO_LUT));
   if (lut_stage) {
-    HIP_TRY(hipMemsetAsync(P.rowbad, 0, (size_t)b->n_base * 16, s));
-    const unsigned cb = (unsigned)std::min<int64_t>(((int64_t)need + 255) / 256, (int64_t)ctx->n_cu * 16);
-    hipLaunchKernelGGL(bqsr_apply_chars, dim3(cb), dim3(256), 0, s, P, b->d_chars);
+    HIP_TRY(hipMemsetAsync(P.rowbad, 0, rowbad_bytes(b), s));
+    launch_chars(ctx, b, P, bqsr_apply_chars, s);
     b->chars_lut = L;
   }
   if (stages & BQSR_STAGE_KERNEL) {
     if (b->chars_lut != L) return fail(BQSR_ERR_INVALID_ARG, "apply kernel before the LUT stage of this LUT");
     P.outs_apart = b->bucketed;
-    hipLaunchKernelGGL(bqsr_apply_kernel, dim3(b->pass_blocks()), dim3(kBlockThreads), apply_lds(P.w.qw, cw), s, P);
-    if (P.outs_apart) {
-      ApplyParams Q = P;
-      Q.rd = b->rd;  // (read order: the batch's own qual column, where a read not yet trimmed is)
-      hipLaunchKernelGGL(bqsr_apply_outs, dim3((unsigned)std::min<int64_t>((b->rd.n_reads + 255) / 256, (int64_t)ctx->n_cu * 8)),
-                         dim3(256), 0, s, Q);
-    }
+    launch_apply(ctx, b, P, bqsr_apply_kernel, b->pass_blocks(), s);
   }
   HIP_TRY(hipGetLastError());
   return ok();
@@ -2251,6 +2273,27 @@ bqsr_status bqsr_job_errors_import_async(bqsr_batch* b, const int64_t* src_devic
   return ok();
 }
 
+// the job's status words written by one kernel into the batch's pinned buffer (made on first use: the live set,
+// then kStatusSlots snapshots), into snapshot `slot` or the live set (-1)
+static bqsr_status launch_status(bqsr_batch* b, const bqsr_lut* L, const uint32_t* tail_words, int32_t slot, hipStream_t s) {
+  if (!b->h_status)
+    HIP_TRY(hipHostMalloc((void**)&b->h_status, kJobStatusWords * 8 * (1 + kStatusSlots), hipHostMallocDefault));
+  hipLaunchKernelGGL(bqsr_job_status_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)b->d_err,
+                     (const double*)b->d_em, (const FinalOut*)L->d_out, tail_words,
+                     b->h_status + kJobStatusWords * (1 + slot));
+  HIP_TRY(hipGetLastError());
+  return BQSR_OK;
+}
+// one error of a job from its status words, the parts numbered in the order
+// the reference raises them: observe (0), EMPTY_TABLE at finalize (1), apply (2)
+static bqsr_status job_error(const uint64_t* h, int32_t part) {
+  FinalOut fo;
+  std::memcpy(&fo, h + kErrWords + 1, sizeof(FinalOut));
+  if (part == 0) return from_err_key(h[kErrObs], 0);
+  if (part == 1) return fo.any_key ? ok() : empty_table();
+  return from_err_key(std::min(h[kErrAppPrep], h[kErrAppKern]), 0);
+}
+
 // Snapshots for pipelined jobs (adam_amd/stream.py): the batch's status words
 // of a job copied on `stream` into pinned slot `slot`, read after the caller
 // has waited for the stream past that point; the next job may already reset
@@ -2258,13 +2301,8 @@ bqsr_status bqsr_job_errors_import_async(bqsr_batch* b, const int64_t* src_devic
 bqsr_status bqsr_job_status_async(bqsr_batch* b, bqsr_lut* L, int32_t slot, void* stream) {
   if (!b || !L || slot < 0 || slot >= kStatusSlots) return fail(BQSR_ERR_INVALID_ARG, "null / bad slot");
   HIP_TRY(hipSetDevice(b->ctx->device));
-  if (!b->h_status)
-    HIP_TRY(hipHostMalloc((void**)&b->h_status, kJobStatusWords * 8 * (1 + kStatusSlots), hipHostMallocDefault));
-  hipLaunchKernelGGL(bqsr_job_status_kernel, dim3(1), dim3(64), 0, S(stream), (const unsigned long long*)b->d_err,
-                     (const double*)b->d_em, (const FinalOut*)L->d_out, (const uint32_t*)nullptr,
-                     b->h_status + kJobStatusWords * (1 + slot));
-  HIP_TRY(hipGetLastError());
-  return ok();
+  const bqsr_status st = launch_status(b, L, nullptr, slot, S(stream));
+  return st != BQSR_OK ? st : ok();
 }
 
 bqsr_status bqsr_job_status_get(const bqsr_batch* b, int32_t slot, int32_t part, double* em, int64_t* n_exceptions) {
@@ -2273,13 +2311,7 @@ bqsr_status bqsr_job_status_get(const bqsr_batch* b, int32_t slot, int32_t part,
   const uint64_t* h = b->h_status + kJobStatusWords * (1 + slot);
   if (em) std::memcpy(em, h + kErrWords, 8);
   if (n_exceptions) *n_exceptions = (int64_t)h[kNExc];
-  if (part == 0) return from_err_key(h[kErrObs], 0);
-  if (part == 1) {
-    FinalOut fo;
-    std::memcpy(&fo, h + kErrWords + 1, sizeof(FinalOut));
-    return fo.any_key ? ok() : fail(BQSR_ERR_EMPTY_TABLE, "empty.reduceLeft: no usable base was observed");
-  }
-  return from_err_key(std::min(h[kErrAppPrep], h[kErrAppKern]), 0);
+  return job_error(h, part);
 }
 
 // workgroups of a kernel copy: enough stores in flight for the link, few
@@ -2307,22 +2339,17 @@ bqsr_status bqsr_job_result(bqsr_batch* b, bqsr_lut* L, double* em, int64_t* n_e
   if (!b || !L) return fail(BQSR_ERR_INVALID_ARG, "null");
   HIP_TRY(hipSetDevice(b->ctx->device));
   hipStream_t s = S(stream);
-  if (!b->h_status)
-    HIP_TRY(hipHostMalloc((void**)&b->h_status, kJobStatusWords * 8 * (1 + kStatusSlots), hipHostMallocDefault));
-  hipLaunchKernelGGL(bqsr_job_status_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)b->d_err,
-                     (const double*)b->d_em, (const FinalOut*)L->d_out,
-                     (const uint32_t*)(b->tail_spec ? b->d_tail : nullptr), b->h_status);
-  HIP_TRY(hipGetLastError());
+  bqsr_status st = launch_status(b, L, b->tail_spec ? b->d_tail : nullptr, -1, s);
+  if (st != BQSR_OK) return st;
   HIP_TRY(hipStreamSynchronize(s));
   const uint64_t* h = b->h_status;
   std::memcpy(&L->out, h + kErrWords + 1, sizeof(FinalOut));
   L->out_pending = false;
   if (em) std::memcpy(em, h + kErrWords, 8);
   if (n_exceptions) *n_exceptions = (int64_t)h[kNExc];
-  bqsr_status st = from_err_key(h[kErrObs], 0);
-  if (st != BQSR_OK) return st;
-  if (!L->out.any_key) return fail(BQSR_ERR_EMPTY_TABLE, "empty.reduceLeft: no usable base was observed");
-  return from_err_key(std::min(h[kErrAppPrep], h[kErrAppKern]), 0);
+  for (int32_t part = 0; part < 2; ++part)  // the first of the job's errors
+    if ((st = job_error(h, part)) != BQSR_OK) return st;
+  return job_error(h, 2);
 }
 
 // which schedule the job bqsr_job_result last fetched ran: 0 serial, 1
@@ -2383,69 +2410,45 @@ bqsr_status bqsr_job_tail_async(bqsr_context* ctx, bqsr_batch* b, const bqsr_sit
                   (st = dalloc(L->allocs, &L->d2s, (size_t)n_rg * kQBins * kCtxSlots)) != BQSR_OK))
     return st;
   ApplyParams P{};
-  if ((st = apply_params(ctx, b, L, out_qual, out_start, out_len, exceptions, max_exceptions, stream, &P)) != BQSR_OK) return st;
-  const int cw = window_cw(b, P.g);
-  const int rb_words = b->n_base * 4;  // rowbad words of one set of char tables
+  if ((st = apply_params(ctx, b, L, out_qual, out_start, out_len, exceptions, max_exceptions, s, &P)) != BQSR_OK) return st;
+  const int rb_words = (int)(rowbad_bytes(b) / 4);  // of one set of char tables
   P.qmask = b->d_qmask;
 
   // ---- side stream: the exact fold, from the fork event ----
   HIP_TRY(hipStreamWaitEvent(b->side, b->ev_obs, 0));
-  const FoldParams F = fold_params(ctx, b, false);
-  hipLaunchKernelGGL(bqsr_fold_plan, dim3(1), dim3(1024), 0, b->side, F);
-  const int64_t max_tpb = (b->rd.n_tiles + b->n_blocks - 1) / b->n_blocks + 1;
-  hipLaunchKernelGGL(bqsr_fold_tiles, dim3(ctx->n_cu * 4), dim3(kFtWaves * 64), 0, b->side, F, max_tpb);
-  HIP_TRY(hipEventRecord(b->ev_tiles, b->side));
-  hipLaunchKernelGGL(bqsr_fold_segs, dim3(b->n_blocks), dim3(kSegThreads), 0, b->side, F);
-  hipLaunchKernelGGL(bqsr_fold_chain, dim3(1), dim3(1024), chain_lds(b->n_blocks), b->side, F);
-  HIP_TRY(hipGetLastError());
+  if ((st = launch_fold(ctx, b, b->side, false, b->ev_tiles)) != BQSR_OK) return st;
   HIP_TRY(hipEventRecord(b->ev_fold, b->side));
-  b->hq_valid = true;
 
   // ---- caller's stream: estimate, speculative tables, apply ----
   const int mode = ctx->tune_spec_tail;
   hipLaunchKernelGGL(bqsr_tail_estimate, dim3(1), dim3(1024), 0, s, (const uint32_t*)b->d_hq, b->n_blocks,
                      (const double*)ctx->d_pow10, mode == 3 ? 1.5 : 1.0, b->d_em_spec, b->d_qmask, b->d_tail, P.rowbad,
                      2 * rb_words);
-  hipLaunchKernelGGL(bqsr_final_keys, dim3((g.K + 3) / 4), dim3(256), 0, s, t->touched(), t->obs(), t->mm(), g, L->qk_obs,
-                     L->qk_mm);
-  const int64_t ncell = (int64_t)n_rg * kQBins * (g.C + kCtxSlots);
-  const unsigned tb = (unsigned)std::min<int64_t>(8192, (ncell + 255) / 256);
-  const double mre = pow10tab().v[kMaxQ];
-  hipLaunchKernelGGL(bqsr_final_groups, dim3(1), dim3(256), 0, s, t->touched(), L->qk_obs, L->qk_mm, g, n_rg, 0.0,
-                     (const double*)b->d_em_spec, ctx->d_pow10, L->n_groups, L->grp_obs, L->grp_mm, L->grp_ok, L->key_ok,
-                     L->a2s, L->rq_ok, L->d_out);
-  hipLaunchKernelGGL(bqsr_final_tables, dim3(tb), dim3(256), 0, s, t->obs(), t->mm(), g, n_rg, L->a2s, L->rq_ok, mre,
-                     L->s1s, L->d2s);
-  const size_t chars_n = (size_t)P.piece_stride * (size_t)b->n_base + (size_t)b->n_base * 16;
-  const unsigned cb = (unsigned)std::min<int64_t>(((int64_t)chars_n + 255) / 256, (int64_t)ctx->n_cu * 16);
+  launch_final_keys(t, L, s);
+  launch_final_tables(ctx, t, L, 0.0, b->d_em_spec, L->a2s, L->s1s, L->d2s, s);
   ApplyParams Ps = P;
   Ps.s1 = L->s1s;
   Ps.d2 = L->d2s;
-  hipLaunchKernelGGL(bqsr_apply_chars, dim3(cb), dim3(256), 0, s, Ps, b->d_chars);
+  launch_chars(ctx, b, Ps, bqsr_apply_chars, s);
   b->chars_lut = nullptr;  // (the tables are the speculative ones, or the redo's)
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamWaitEvent(s, b->ev_tiles, 0));
   // static ranges on the smaller grid (ranges claimed from a device counter
   // measured level with it: profiles/r08_spec_tail_ab.txt)
-  const int grid = std::max(1, b->pass_blocks() - ctx->tune_spec_reserve);
-  hipLaunchKernelGGL(bqsr_apply_kernel, dim3(grid), dim3(kBlockThreads), apply_lds(P.w.qw, cw), s, Ps);
+  launch_apply(ctx, b, Ps, bqsr_apply_kernel, std::max(1, b->pass_blocks() - ctx->tune_spec_reserve), s);
   HIP_TRY(hipGetLastError());
 
-  // ---- the exact tables, the verification, the guarded redo ----
+  // ---- the fold joined: the exact tables, the verification, the guarded redo ----
   HIP_TRY(hipStreamWaitEvent(s, b->ev_fold, 0));
-  hipLaunchKernelGGL(bqsr_final_groups, dim3(1), dim3(256), 0, s, t->touched(), L->qk_obs, L->qk_mm, g, n_rg, 0.0,
-                     (const double*)b->d_em, ctx->d_pow10, L->n_groups, L->grp_obs, L->grp_mm, L->grp_ok, L->key_ok, L->a2,
-                     L->rq_ok, L->d_out);
-  hipLaunchKernelGGL(bqsr_final_tables, dim3(tb), dim3(256), 0, s, t->obs(), t->mm(), g, n_rg, L->a2, L->rq_ok, mre, L->s1,
-                     L->d2);
+  launch_final_tables(ctx, t, L, 0.0, b->d_em, L->a2, L->s1, L->d2, s);
   hipLaunchKernelGGL(bqsr_tail_compare, dim3((unsigned)(n_rg * kQBins)), dim3(256), 0, s, P, (const double*)L->a2,
                      (const double*)L->a2s, (const double*)L->s1s, (const double*)L->d2s, mode == 2 ? 1 : 0, b->d_tail);
   ApplyParams Pr = P;  // the redo: exact tables, full grid, a bad-row set of its own
   Pr.run_if = b->d_tail + kTailRedo;
   Pr.rowbad = P.rowbad + rb_words;
   Pr.redo_mark = b->d_tail + kTailRan;
-  hipLaunchKernelGGL(bqsr_redo_chars, dim3(cb), dim3(256), 0, s, Pr, b->d_chars);
-  hipLaunchKernelGGL(bqsr_redo_apply, dim3(b->pass_blocks()), dim3(kBlockThreads), apply_lds(P.w.qw, cw), s, Pr);
+  launch_chars(ctx, b, Pr, bqsr_redo_chars, s);
+  launch_apply(ctx, b, Pr, bqsr_redo_apply, b->pass_blocks(), s);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(BQSR_ERR_DEVICE, hipGetErrorString(e));
   L->out_pending = true;
@@ -2490,17 +2493,10 @@ bqsr_status bqsr_compact_outputs_async(bqsr_context* ctx, bqsr_batch* b, const u
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = S(stream);
   const int64_t n = b->rd.n_reads;
-  if (!b->d_off64 || b->off64_n < n) {  // scratch: u64 lengths and their scan (kept on the batch)
-    if (b->d_off64) {
-      HIP_TRY(hipStreamSynchronize(s));
-      (void)hipFree(b->d_off64);
-      b->d_off64 = nullptr;
-    }
-    const size_t words = 2 * ((size_t)n + 1) + (size_t)n / samk::kScanChunk + 2;
-    HIP_TRY(hipMalloc((void**)&b->d_off64, words * 8));
-    b->off64_n = n;
-  }
-  uint64_t* len64 = b->d_off64;
+  // scratch: u64 lengths and their scan (kept on the batch)
+  const bqsr_status gs = grow(b->off64, (2 * ((size_t)n + 1) + (size_t)n / samk::kScanChunk + 2) * 8, s);
+  if (gs != BQSR_OK) return gs;
+  uint64_t* len64 = (uint64_t*)b->off64.p;
   uint64_t* off64 = len64 + n + 1;
   uint64_t* part = off64 + n + 1;
   const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cu * 8));

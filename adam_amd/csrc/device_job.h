@@ -4,7 +4,7 @@
 // dev_need / dev_prim for memory, launch for every kernel, a StageClock in the
 // state struct with an enum of its stages, and on the Python side one `sig`
 // table bound with _capi.bind and _capi.stage_times over the stage names.
-// Included by bqsr_capi.cpp once, after fail / HIP_TRY and bqsr_context, before
+// Included by bqsr_capi.cpp once, after fail / HIP_TRY, DevBuf and bqsr_context, before
 // sam_ingest.hip.  (The one-shot form of dev_prim, with_temp, sits next to
 // sam_alloc in sam_ingest.hip.)
 #pragma once
@@ -69,17 +69,9 @@ struct StageClock {
   }
 };
 
-// a device buffer that only grows
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-// b grown to count elements of T; a job keeps its whole input's rows on the
-// device, so what does not fit is refused, naming the job and what the bytes were for
+// b (a DevBuf, the device buffer that only grows: bqsr_capi.cpp, where the core's batches hold three) grown to
+// count elements of T; a job keeps its whole input's rows on the device, so what does not fit is refused,
+// naming the job and what the bytes were for
 template <class T>
 bqsr_status dev_need(DevBuf& b, T** p, size_t count, const char* job, const char* what) {
   const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
