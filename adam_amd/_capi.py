@@ -54,6 +54,8 @@ EXPORTS = [
     "bqsr_bam_kernel_times",
     "bqsr_bgzf_deflate", "bqsr_bgzf_deflate_host", "bqsr_sam_bam_members", "bqsr_deflate_code_lengths",
     "bqsr_bgzf_deflate_times",
+    "bqsr_bam_index_create", "bqsr_bam_index_destroy", "bqsr_bam_index_add", "bqsr_bam_index_set_members",
+    "bqsr_bam_index_finish", "bqsr_bam_index_size", "bqsr_bam_index_bytes",
     "bqsr_compare_create", "bqsr_compare_destroy", "bqsr_compare_check_terms", "bqsr_compare_sam", "bqsr_compare_sides",
     "bqsr_compare_values", "bqsr_compare_baseqs", "bqsr_compare_rows", "bqsr_compare_kernel_times",
     "bqsr_sam_tag_counts", "bqsr_arrow_tag_counts", "bqsr_sam_tag_values", "bqsr_arrow_tag_values",

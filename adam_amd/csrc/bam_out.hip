@@ -258,6 +258,7 @@ struct BamRec {
   int32_t ref, nref;
   int64_t n_ops, l_seq;
   bool qual_star;
+  int64_t end;  // one past the record's last reference base: pos + the CIGAR's reference length, pos + 1 without one
   uint32_t bin;
   uint32_t code;
 };
@@ -317,7 +318,8 @@ __device__ void bam_fields(const BamParams& P, int64_t r, BamRec& x) {
     const uint32_t op = cg[k] & 15u;
     if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += (int64_t)(cg[k] >> 4);
   }
-  x.bin = reg2bin(x.pos, x.pos + (ref_len > 0 ? ref_len : 1)) & 0xFFFFu;
+  x.end = x.pos + (ref_len > 0 ? ref_len : 1);
+  x.bin = reg2bin(x.pos, x.end) & 0xFFFFu;
 }
 
 // QUAL of a validated record that is not "*": SEQ's length, every byte in '!'..'~'

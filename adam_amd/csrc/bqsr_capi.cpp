@@ -2466,6 +2466,7 @@ bqsr_status bqsr_job_tail_async(bqsr_context* ctx, bqsr_batch* b, const bqsr_sit
 #include "mark_duplicates.cpp"
 #include "adam_out.hip"
 #include "bam_out.hip"
+#include "bam_index.hip"
 #include "bgzf_deflate.hip"
 #include "sam_sort.hip"
 #include "flagstat.hip"

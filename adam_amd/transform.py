@@ -5,7 +5,7 @@
         [-recalibrate_base_qualities] [-dbsnp_sites SITES.vcf]
     python -m adam_amd.transform INPUT.{adam,parquet,sam} OUTPUT.{adam,parquet} [...]
     python -m adam_amd.transform INPUT.{sam,bam} OUTPUT.bam [-bam_compression_level N]
-        [-bam_compressor {host,device}] [...]
+        [-bam_compressor {host,device}] [-bam_index] [...]
 
 SAM or BAM in goes through the device path described below, out as SAM text,
 as BAM (an output name ending in .bam: the records encoded on the device,
@@ -373,6 +373,48 @@ DEVICE_LEVEL_REFUSAL = ("-bam_compressor device has one level: it cannot be comb
                         "-bam_compression_level")
 
 
+BAM_INDEX_KERNELS = ("rows", "locate", "windows", "sort", "chunks", "serialize_host")
+BAM_INDEX_REFUSAL = "-bam_index applies to BAM output only (an output name ending in .bam)"
+
+
+class BamIndexSizes(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("n_records", "n_chunks", "n_bins", "n_windows", "bytes",
+                                              "device_bytes")]
+
+
+_INDEX_SIG = {
+    "bqsr_bam_index_create": (ctypes.c_int, [_capi.vp, _capi.i32, _capi.pp]),
+    "bqsr_bam_index_destroy": (None, [_capi.vp]),
+    "bqsr_bam_index_add": (ctypes.c_int, [_capi.vp, _capi.vp, _capi.i64, _capi.vp]),
+    "bqsr_bam_index_set_members": (ctypes.c_int, [_capi.vp, _capi.vp, _capi.i64, _capi.vp]),
+    "bqsr_bam_index_finish": (ctypes.c_int, [_capi.vp, _capi.vp]),
+    "bqsr_bam_index_size": (ctypes.c_int, [_capi.vp, ctypes.POINTER(BamIndexSizes)]),
+    "bqsr_bam_index_bytes": (ctypes.c_int, [_capi.vp, _capi.vp, _capi.i64]),
+    "bqsr_bam_index_kernel_times": (ctypes.c_int, [_capi.vp, _capi.dblp]),
+}
+
+
+def _index_lib():
+    return _capi.bind(_capi.lib(), _INDEX_SIG)
+
+
+def bgzf_member_table(data, stream_pos: int, file_pos: int, table: List[int]) -> Tuple[int, int]:
+    """The BGZF members of `data` (whole members, as the BAM sink writes
+    them) appended to `table` as (stream start, file offset) pairs, walking
+    their BSIZE fields; ISIZE advances the stream.  Returns the stream and
+    file positions after them."""
+    import struct
+    p, n = 0, len(data)
+    while p < n:
+        size = struct.unpack_from("<H", data, p + 16)[0] + 1 if p + 18 <= n else n + 1
+        if p + size > n:
+            raise ValueError("BAM index: the bytes written do not end on a BGZF member")
+        table += (stream_pos, file_pos + p)
+        stream_pos += struct.unpack_from("<I", data, p + size - 4)[0]
+        p += size
+    return stream_pos, file_pos + n
+
+
 class _BamOut:
     """BAM output with _SamOut's contract (records appended partition by
     partition; the file appears when the job succeeds): the header once,
@@ -384,10 +426,21 @@ class _BamOut:
     from the device (SamText.bam_members: the record stream is not downloaded)
     and are written as they arrive, no compressor thread; the header member
     stays on the host path; the device form has one level, so `level` must be
-    None."""
+    None.
+
+    index: OUT.bam.bai is written beside the BAM (SAM spec §5.2; the rules are
+    in include/adam_sam.h at bqsr_bam_index_create).  Every piece's records
+    leave a row each on the device after its prepare (bqsr_bam_index_add);
+    the members of every byte written are walked here into the table of
+    (stream start, file offset); at close(ok=True) the table goes up, the
+    device builds the index (bqsr_bam_index_finish), the host serialises it.
+    An output that is not in coordinate order, or a record that ends above
+    2^29, raises BQSRError naming the read, and neither file appears.  The
+    index goes to OUT.bam.bai.partial and is renamed after the BAM.  Without
+    `index` nothing of this is launched or allocated."""
 
     def __init__(self, path: str, level: Optional[int] = None, piece_reads: int = BAM_PIECE_READS,
-                 overwrite: bool = False, compressor: str = "host"):
+                 overwrite: bool = False, compressor: str = "host", index: bool = False):
         from concurrent.futures import ThreadPoolExecutor
         if compressor not in BAM_COMPRESSORS:
             raise ValueError("-bam_compressor must be one of %s" % ", ".join(BAM_COMPRESSORS))
@@ -397,8 +450,15 @@ class _BamOut:
         if not 0 <= int(level) <= 9:
             raise ValueError("-bam_compression_level must be 0..9")
         _check_out(path, overwrite, False)
+        if index:
+            _check_out(path + ".bai", overwrite, False)
         self.path = path
         self.tmp = path + ".partial"
+        self.index = bool(index)
+        self.idx = None            # the device index (made at the first emit: it needs the header's n_ref)
+        self.members: List[int] = []  # (stream start, file offset) of every member written
+        self.stream_pos = 0        # of the record stream: where the next member's bytes start
+        self.record_pos = 0        # of the record stream: where the next piece's records start
         self.level = int(level)
         self.compressor = compressor
         self.piece_reads = max(1, int(piece_reads))
@@ -411,6 +471,8 @@ class _BamOut:
         self.stats = {"len_ms": 0.0, "write_ms": 0.0, "record_bytes": 0, "text_bytes": 0, "file_bytes": 0,
                       "compress_s": 0.0, "compressor": compressor, "deflate_ms": 0.0, "pack_ms": 0.0,
                       "downloaded_bytes": 0}
+        if index:  # the host's member walk, the .bai file's bytes (the stage times arrive at close)
+            self.stats.update(index_walk_s=0.0, index_bytes=0)
 
     def _compress(self, data):
         from .sam import bgzf_compress
@@ -419,12 +481,44 @@ class _BamOut:
         self.stats["compress_s"] += time.perf_counter() - t0
         return out
 
+    def _write(self, out):
+        self.fh.write(out)
+        if self.index:
+            t0 = time.perf_counter()
+            self.stream_pos, _ = bgzf_member_table(out, self.stream_pos, self.stats["file_bytes"], self.members)
+            self.stats["index_walk_s"] += time.perf_counter() - t0
+        self.stats["file_bytes"] += len(out)
+
     def _drain(self):
         if self.pending is not None:
             f, self.pending = self.pending, None
-            out = f.result()
-            self.fh.write(out)
-            self.stats["file_bytes"] += len(out)
+            self._write(f.result())
+
+    def _index_add(self, sam, stream_bytes: int):
+        """after the piece's prepare: its records' rows appended on the device"""
+        if self.index:
+            check(_index_lib().bqsr_bam_index_add(self.idx, sam.h, self.record_pos, None))
+            self.record_pos += int(stream_bytes)
+
+    def _index_finish(self) -> bytes:
+        """the member table up, the index built on the device, its bytes"""
+        L = _index_lib()
+        if self.idx is None:  # no emit: a BAM of the EOF marker alone has no references
+            return b"BAI\1" + bytes(12)
+        table = np.array(self.members + [self.stream_pos, self.stats["file_bytes"]], np.uint64)
+        check(L.bqsr_bam_index_set_members(self.idx, table.ctypes.data, len(self.members) // 2, None))
+        check(L.bqsr_bam_index_finish(self.idx, None))
+        sz = BamIndexSizes()
+        check(L.bqsr_bam_index_size(self.idx, ctypes.byref(sz)))
+        buf = np.empty(max(1, sz.bytes), np.uint8)
+        check(L.bqsr_bam_index_bytes(self.idx, buf.ctypes.data, sz.bytes))
+        self.stats["index_bytes"] = int(sz.bytes)
+        self.stats["index_chunks"] = int(sz.n_chunks)
+        self.stats["index_bins"] = int(sz.n_bins)
+        self.stats["index_device_bytes"] = int(sz.device_bytes)
+        self.stats["index_ms"] = _capi.stage_times(L.bqsr_bam_index_kernel_times, BAM_INDEX_KERNELS, self.idx,
+                                                   array=True)
+        return buf[:sz.bytes].tobytes()
 
     def _submit(self, data):
         self._drain()  # one piece compressing while the next is encoded
@@ -439,7 +533,14 @@ class _BamOut:
         else:
             check(_capi.lib().bqsr_sam_rewrite_quals(sam.ctx.handle, sam.h, *quals))
         if self.first:
-            self._submit(sam.bam_header())
+            head = sam.bam_header()
+            if self.index:
+                import struct
+                self.idx = ctypes.c_void_p()
+                n_ref = struct.unpack_from("<i", head, 8 + struct.unpack_from("<i", head, 4)[0])[0]
+                check(_index_lib().bqsr_bam_index_create(sam.ctx.handle, n_ref, ctypes.byref(self.idx)))
+                self.record_pos = len(head)
+            self._submit(head)
             self.first = False
         c = sam.counts()
         self.stats["text_bytes"] += c.text_bytes
@@ -449,6 +550,7 @@ class _BamOut:
                 self._emit_device(sam, r0, n)
                 continue
             rec = sam.bam_records(r0, n)
+            self._index_add(sam, rec.size)
             a, b = bam_kernel_times()
             self.stats["len_ms"] += a
             self.stats["write_ms"] += b
@@ -461,6 +563,7 @@ class _BamOut:
         from .sam import BamSizes, bam_kernel_times, bgzf_deflate_times
         sz = BamSizes()
         check(sam.L.bqsr_sam_bam_prepare(sam.ctx.handle, sam.h, int(r0), int(n), None, ctypes.byref(sz)))
+        self._index_add(sam, sz.bytes)
         t0 = time.perf_counter()
         out = sam._members(sz.bytes)
         self.stats["compress_s"] += time.perf_counter() - t0
@@ -473,25 +576,35 @@ class _BamOut:
         self.stats["record_bytes"] += int(sz.bytes)
         self.stats["downloaded_bytes"] += len(out)
         self._drain()  # (the header member goes first)
-        self.fh.write(out)
-        self.stats["file_bytes"] += len(out)
+        self._write(out)
 
     def close(self, ok: bool = True):
         from .sam import BGZF_EOF
+        bai_tmp = self.path + ".bai.partial"
         try:
             if ok:
                 ok = False
                 self._drain()
-                self.fh.write(BGZF_EOF)
-                self.stats["file_bytes"] += len(BGZF_EOF)
+                self._write(BGZF_EOF)
+                if self.index:  # (a refusal leaves through here: neither file appears)
+                    bai = self._index_finish()
+                    with open(bai_tmp, "wb") as fh:
+                        fh.write(bai)
                 ok = True
         finally:
             self.pool.shutdown(wait=True)
             self.fh.close()
+            if self.idx is not None:
+                _index_lib().bqsr_bam_index_destroy(self.idx)
+                self.idx = None
             if ok:
                 os.replace(self.tmp, self.path)
-            elif os.path.exists(self.tmp):
-                os.remove(self.tmp)
+                if self.index:
+                    os.replace(bai_tmp, self.path + ".bai")
+            else:
+                for p in (self.tmp, bai_tmp):
+                    if os.path.exists(p):
+                        os.remove(p)
 
 
 class _AdamOut:
@@ -517,18 +630,22 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
               dbsnp: Optional[str] = None, device: int = 0, partition_bytes: int = DEFAULT_PARTITION_BYTES,
               compression: str = "gzip", part_reads: int = 1 << 19, overwrite: bool = False,
               sort_reads: bool = False, bam_level: Optional[int] = None,
-              bam_piece_reads: int = BAM_PIECE_READS, bam_compressor: Optional[str] = None) -> Dict[str, float]:
+              bam_piece_reads: int = BAM_PIECE_READS, bam_compressor: Optional[str] = None,
+              bam_index: bool = False) -> Dict[str, float]:
     """Transform.run (cli/Transform.scala:62-97) over SAM or BAM input: the
     records parsed on the device (a BAM's records become SAM lines there),
     MarkDuplicates, BQSR, then adamSave (OUT.adam / .parquet / a directory:
     ADAMRecord Parquet part files, adam_save.py), BAM (OUT.bam, _BamOut:
     bam_level 0-9 (None: 6), records per encoded piece bam_piece_reads,
     bam_compressor "host" (None) or "device": the BGZF members deflated on
-    the device, one level) or SAM text.
+    the device, one level; bam_index: OUT.bam.bai beside it, built on the
+    device, see _BamOut) or SAM text.
     ADAM Parquet input goes through transform_parquet (Arrow reads it on the
     host).  sort_reads: the records sorted on the device before the save (see
     the module doc); the input must be one partition."""
     bam_out = out.endswith(".bam")
+    if bam_index and not bam_out:  # before anything is read
+        raise ValueError(BAM_INDEX_REFUSAL)
     if bam_compressor is not None and not bam_out:  # before anything is read
         raise ValueError("-bam_compressor applies to BAM output only (an output name ending in .bam)")
     if bam_compressor is not None and bam_compressor not in BAM_COMPRESSORS:
@@ -549,7 +666,7 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
     # because `out` is some existing directory: the sinks refuse that)
     from .adam_save import is_adam_output
     adam_out = not bam_out and (out.endswith((".adam", ".parquet")) or is_adam_output(out))
-    sink = (_BamOut(out, bam_level, bam_piece_reads, overwrite, bam_compressor or "host") if bam_out
+    sink = (_BamOut(out, bam_level, bam_piece_reads, overwrite, bam_compressor or "host", bam_index) if bam_out
             else _AdamOut(out, compression, part_reads, overwrite) if adam_out else _SamOut(out, overwrite))
     try:
         ctx = bqsr.Context.get(device)
@@ -633,6 +750,9 @@ def main(argv=None) -> int:
     ap.add_argument("-bam_compressor", default=None, choices=BAM_COMPRESSORS,
                     help="BAM output: who deflates the BGZF members: host threads (default) or the device "
                          "(one level: not together with -bam_compression_level)")
+    ap.add_argument("-bam_index", action="store_true",
+                    help="BAM output: write OUTPUT.bam.bai beside it, built on the device (the output must be in "
+                         "coordinate order)")
     ap.add_argument("-overwrite", action="store_true",
                     help="replace an existing output (a file, or a directory of ADAM part files only)")
     a = ap.parse_args(argv)
@@ -642,11 +762,13 @@ def main(argv=None) -> int:
         ap.error("-bam_compressor applies to BAM output only (an output name ending in .bam)")
     if a.bam_compressor == "device" and a.bam_compression_level is not None:
         ap.error(DEVICE_LEVEL_REFUSAL)
+    if a.bam_index and not a.output.endswith(".bam"):
+        ap.error(BAM_INDEX_REFUSAL)
     t0 = time.perf_counter()
     st = transform(a.input, a.output, a.mark_duplicate_reads, a.recalibrate_base_qualities, a.dbsnp_sites,
                    partition_bytes=a.partition_bytes, compression=a.parquet_compression, part_reads=a.part_reads,
                    overwrite=a.overwrite, sort_reads=a.sort_reads, bam_level=a.bam_compression_level,
-                   bam_compressor=a.bam_compressor)
+                   bam_compressor=a.bam_compressor, bam_index=a.bam_index)
     report(st, t0)
     return 0
 

@@ -366,6 +366,87 @@ bqsr_status bqsr_deflate_code_lengths(const uint32_t* freq, int32_t n_syms, int3
  * milliseconds. */
 bqsr_status bqsr_bgzf_deflate_times(double* deflate_ms, double* pack_ms);
 
+/* The .bai index of a BAM while it is written (`transform OUT.bam -bam_index`;
+ * SAM spec §5.2, bam_index.hip): one object across the pieces and partitions
+ * of one output, fed from the device buffers of every bqsr_sam_bam_prepare.
+ * No htslib is consulted; the index is the spec plus these declarations.
+ *
+ * Interval of a record.  [beg, end) is the interval the record's bin field
+ *   comes from (bqsr_sam_bam_prepare above: beg = POS - 1, end = beg + the
+ *   CIGAR's reference length over M D N = X, beg + 1 when that is 0 or CIGAR
+ *   is "*"; one routine computes both).  For the index a negative beg (POS 0
+ *   with an RNAME) is clamped to 0 and end is at least beg + 1; the order
+ *   checks below use the clamped beg.  A record with refID >= 0 is indexed
+ *   whether or not FLAG 0x4 is set.
+ * Virtual offsets.  The record stream is the BAM header followed by every
+ *   record; position p lies in the BGZF member m with start[m] <= p <
+ *   start[m + 1] and its virtual offset is file_offset[m] << 16 | (p -
+ *   start[m]).  A record's u is the offset of its block_size word, its v that
+ *   of the position one past its last byte: when that falls on a member
+ *   boundary it is expressed in the next member with offset 0, for the last
+ *   record of the file in the EOF marker.  A piece ends in a short member, so
+ *   the caller builds the member table from the BSIZE and ISIZE fields of the
+ *   bytes it writes (header members, every piece, the EOF marker) and hands it
+ *   over as (stream start, file offset) per member plus a terminal entry (the
+ *   stream's length, the file's size).
+ * Binning index.  bin = reg2bin(beg, end).  Within one (refID, bin) records
+ *   are taken in file order; a record joins the chunk before it when prev.v
+ *   >> 16 >= u >> 16 (prev: the record before it in the bin) and the chunk's
+ *   end becomes the record's v, otherwise it starts a chunk.  Bins ascend by
+ *   number; small bins are not folded into their parents.
+ * Pseudo-bin 37450, last for every reference with records and counted in
+ *   n_bin: chunk (u of the reference's first record, v of its last), chunk
+ *   (records without FLAG 0x4, records with it); FLAG is the one written
+ *   (after MarkDuplicates), not BQSR_F_MAPPED.
+ * Linear index.  n_intv = 1 + ((max end - 1) >> 14) over the reference's
+ *   records; window w holds the smallest u among records with beg >> 14 <= w
+ *   <= (end - 1) >> 14; an empty window takes the value of the window before
+ *   it, empty windows before the first filled one hold 0.
+ * A reference without records has n_bin = 0 and n_intv = 0.  n_no_coor, the
+ *   number of records with refID -1, is always written.
+ * Refusals at bqsr_bam_index_finish, each naming the first offending record
+ *   by its ordinal in the whole output (bqsr_last_error_read); when one record
+ *   earns both, the first one listed:
+ *   BQSR_ERR_UNSORTED     among records with refID >= 0 the refID decreases or
+ *                         beg decreases inside one reference, or such a record
+ *                         follows one with refID -1.  (bqsr_sam_sort puts
+ *                         every read with FLAG 0x4 after the mapped ones: its
+ *                         output is refused when such a read has an RNAME.)
+ *   BQSR_ERR_UNSUPPORTED  end > 2^29, BAI's limit; more than 2^32 - 1 records
+ *                         (at bqsr_bam_index_add).
+ * Device memory: 24 bytes per record from the add on; during finish 56 more
+ * per record (80 in all), 16 per chunk, 12 per bin, 8 per window, and
+ * rocprim's workspace.  What does not fit is BQSR_ERR_UNSUPPORTED.
+ *
+ * create (n_ref: the BAM header's reference count); add after every
+ * bqsr_sam_bam_prepare of the output, in output order (stream_base: the
+ * stream position of the piece's first byte; one kernel, nothing downloaded);
+ * set_members ([2 (n_members + 1)] uint64: the table above, terminal entry
+ * last); finish (the work listed in bam_index.hip; only the chunks, bins,
+ * windows and per-reference words come back); size and bytes (the file);
+ * destroy. */
+typedef struct bqsr_bam_index bqsr_bam_index;
+typedef struct bqsr_bam_index_sizes {
+  int64_t n_records;
+  int64_t n_chunks;     /* pseudo-bins' not counted */
+  int64_t n_bins;       /* pseudo-bins not counted */
+  int64_t n_windows;
+  int64_t bytes;        /* of the .bai file */
+  int64_t device_bytes; /* held on the device when finish returned */
+} bqsr_bam_index_sizes;
+bqsr_status bqsr_bam_index_create(bqsr_context* ctx, int32_t n_ref, bqsr_bam_index** out);
+void bqsr_bam_index_destroy(bqsr_bam_index* x);
+bqsr_status bqsr_bam_index_add(bqsr_bam_index* x, bqsr_sam* s, int64_t stream_base, void* stream);
+bqsr_status bqsr_bam_index_set_members(bqsr_bam_index* x, const uint64_t* members, int64_t n_members, void* stream);
+bqsr_status bqsr_bam_index_finish(bqsr_bam_index* x, void* stream);
+bqsr_status bqsr_bam_index_size(const bqsr_bam_index* x, bqsr_bam_index_sizes* out);
+bqsr_status bqsr_bam_index_bytes(const bqsr_bam_index* x, uint8_t* dst, int64_t cap);
+/* MEASUREMENT ONLY, not part of the stable interface: ms6 receives the stages
+ * of this index in transform.BAM_INDEX_KERNELS' order, in milliseconds: the
+ * rows kernels of every add, locate, windows, sort and chunks by device
+ * events, the serialisation by the host clock. */
+bqsr_status bqsr_bam_index_kernel_times(const bqsr_bam_index* x, double* ms6);
+
 /* MarkDuplicates (§8 f3): adam-core/.../rdd/MarkDuplicates.scala:24-111 over
  * SingleReadBucket (models/SingleReadBucket.scala:27-37: reads grouped by
  * (recordGroupId, readName)) and ReferencePositionPair

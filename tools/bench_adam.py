@@ -61,6 +61,20 @@ device-event ms, GB/s of stream, the bytes downloaded, the file's size);
 every leg's --reps timed runs are all reported (seconds_all) with their
 spread.  One JSON line.
 
+    python tools/bench_adam.py --bam-out --bam-index [--reads 2000000] [--bam-level 6]
+
+--bam-out --bam-index measures `transform IN.sam OUT.bam -bam_index`
+(transform._BamOut, bam_index.hip) over the same synthetic reads sorted by
+position on the host, MarkDuplicates, no BQSR: with the host compressor at
+--bam-level and with the device compressor, a leg without the index and a leg
+with it, all in this process, three timed runs each after a warm-up (all
+reported, with their spread).  Per index leg the stages by device events, the
+host's member walk and serialisation by the host clock, the index's bytes and
+chunk and bin counts; then tests/_bai_ref.bai_of_bam on the finished file --
+the external pass the flag replaces -- timed, its bytes required to equal the
+device's.  On a tree whose transform has no bam_index argument the no-index
+legs alone are run: the same tool measures the parent commit.  One JSON line.
+
     python tools/bench_adam.py --print-tags [--reads 2000000] [--variant-lib LIB.so]
 
 --mpileup measures `adam mpileup` (adam_amd/mpileup.py) over the same
@@ -953,8 +967,106 @@ def bench_bam_out(a):
                 "reads_per_s": a.reads / sdt, "output_bytes": sam_bytes, "phases_s": sst.get("phases")}}))
 
 
+def sorted_by_position(data: bytes) -> bytes:
+    """a SAM text's records in (@SQ index, POS) order, reads without an RNAME last, ties in input order"""
+    head, recs = [], []
+    for l in data.split(b"\n"):
+        if l.startswith(b"@"):
+            head.append(l)
+        elif l:
+            recs.append(l)
+    ref = {l.split(b"\t")[1][3:]: i for i, l in enumerate(h for h in head if h.startswith(b"@SQ"))}
+
+    def key(l):
+        f = l.split(b"\t", 4)
+        return (ref[f[2]], int(f[3])) if f[2] in ref else (len(ref), 0)
+    recs.sort(key=key)
+    return b"\n".join(head + recs) + b"\n"
+
+
+def bench_bam_index(a):
+    """--bam-out --bam-index: see the module doc"""
+    import inspect
+    t0 = time.perf_counter()
+    data = sorted_by_position(synthetic_sam(a.reads, a.len, p_q2tail=0.0))
+    log("generated and sorted %d bytes in %.1f s" % (len(data), time.perf_counter() - t0))
+    import torch
+    from adam_amd import transform as T
+    torch.zeros(1, device="cuda")
+    has_index = "bam_index" in inspect.signature(T.transform).parameters
+    work = a.dir or tempfile.mkdtemp(prefix="bench_adam_")
+    os.makedirs(work, exist_ok=True)
+    src, out = os.path.join(work, "in.sam"), os.path.join(work, "out.bam")
+    with open(src, "wb") as fh:
+        fh.write(data)
+    n_bytes = len(data)
+    del data
+    reps = max(3, a.reps)
+
+    def leg(**kw):
+        runs = []
+        for i in range(1 + reps):  # the first run warms
+            log("%s transform -> out.bam %s" % ("warm-up" if i == 0 else "timed", kw))
+            t = time.perf_counter()
+            st = T.transform(src, out, mark_duplicates=not a.no_markdup, partition_bytes=a.partition_bytes,
+                             overwrite=True, **kw)
+            runs.append((time.perf_counter() - t, st))
+        if runs[-1][1]["reads"] != a.reads:
+            raise SystemExit("transformed %d reads, expected %d" % (runs[-1][1]["reads"], a.reads))
+        times = [dt for dt, _ in runs[1:]]
+        dt, st = min(runs[1:], key=lambda r: r[0])
+        b = st["bam"]
+        r = {"seconds": dt, "seconds_all": times, "seconds_spread": max(times) - min(times),
+             "reads_per_s": a.reads / dt, "output_bytes": os.path.getsize(out), "emit_s": st["phases"].get("emit"),
+             "close_s": st["phases"].get("close")}
+        if kw.get("bam_index"):
+            r.update({"index_bytes": b["index_bytes"], "index_chunks": b["index_chunks"], "index_bins": b["index_bins"],
+                      "index_device_bytes": b["index_device_bytes"], "index_stage_ms": b["index_ms"],
+                      "index_device_ms": sum(v for k, v in b["index_ms"].items() if not k.endswith("_host")),
+                      "member_walk_host_s": b["index_walk_s"],
+                      "serialize_host_ms": b["index_ms"]["serialize_host"]})
+        return r
+
+    res = {}
+    restated = None
+    try:
+        for name, kw in (("host", {"bam_level": a.bam_level}), ("device", {"bam_compressor": "device"})):
+            res[name] = {"no_index": leg(**kw)}
+            if not has_index:
+                continue
+            res[name]["index"] = leg(bam_index=True, **kw)
+            res[name]["index_minus_no_index_s"] = res[name]["index"]["seconds"] - res[name]["no_index"]["seconds"]
+            if name == "host":  # the external pass the flag replaces, on the finished file; and the same bytes
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import _bai_ref
+                with open(out, "rb") as fh:
+                    bam = fh.read()
+                with open(out + ".bai", "rb") as fh:
+                    bai = fh.read()
+                t = time.perf_counter()
+                want = _bai_ref.bai_of_bam(bam)
+                restated = {"seconds": time.perf_counter() - t, "equal": want == bai,
+                            "what": "tests/_bai_ref.bai_of_bam on the finished file: inflate, walk every record, build "
+                                    "the index serially (single-threaded Python)"}
+                del bam
+                if not restated["equal"]:
+                    raise SystemExit("the device's index differs from the restatement's")
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps({
+        "metric": "transform SAM -> BAM with and without -bam_index (the .bai built on the device), reads sorted by "
+                  "position, same input, same process; %sMarkDuplicates, no BQSR" % ("" if not a.no_markdup else "no "),
+        "reads": a.reads, "read_len": a.len, "input_bytes": n_bytes, "reps": reps, "bam_level": a.bam_level,
+        "index_legs": has_index,
+        "legs": res, "restatement": restated,
+        "not_measured": "real coverage (the synthetic reads spread evenly), inputs above one partition"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--bam-index", action="store_true",
+                    help="--bam-out: measure -bam_index instead (legs with and without the index, both compressors)")
     ap.add_argument("--bam-out", action="store_true",
                     help="measure transform SAM -> BAM next to SAM -> SAM text instead of the ADAM transform")
     ap.add_argument("--bam-level", type=int, default=6, help="--bam-out: the BGZF members' DEFLATE level")
@@ -999,7 +1111,7 @@ def main():
     if a.aggregate:
         return bench_aggregate(a)
     if a.bam_out:
-        return bench_bam_out(a)
+        return bench_bam_index(a) if a.bam_index else bench_bam_out(a)
     t0 = time.perf_counter()
     data = synthetic_sam(a.reads, a.len)
     if a.bam:
