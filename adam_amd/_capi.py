@@ -60,6 +60,7 @@ EXPORTS = [
     "bqsr_compare_values", "bqsr_compare_baseqs", "bqsr_compare_rows", "bqsr_compare_kernel_times",
     "bqsr_sam_tag_counts", "bqsr_arrow_tag_counts", "bqsr_sam_tag_values", "bqsr_arrow_tag_values",
     "bqsr_tag_values_fetch", "bqsr_tags_kernel_times",
+    "bqsr_arrow_sam_lines",
 ]
 
 

@@ -2472,6 +2472,7 @@ bqsr_status bqsr_job_tail_async(bqsr_context* ctx, bqsr_batch* b, const bqsr_sit
 #include "flagstat.hip"
 #include "sam_batch.hip"
 #include "arrow_ingest.hip"
+#include "adam_lines.hip"
 #include "pileup.hip"
 #include "mpileup.hip"
 #include "realign_targets.hip"

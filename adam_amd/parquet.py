@@ -392,6 +392,258 @@ class ArrowReads:
             pass
 
 
+class _LinesChunk(ctypes.Structure):
+    """bqsr_adam_lines_chunk (include/adam_sam.h)"""
+    _fields_ = [("n_reads", ctypes.c_int64), ("read_name", _Strings), ("cigar", _Strings), ("sequence", _Strings),
+                ("qual", _Strings), ("attributes", _Strings), ("md", _Strings), ("start", ctypes.c_void_p),
+                ("start_validity", ctypes.c_void_p), ("mate_start", ctypes.c_void_p),
+                ("mate_start_validity", ctypes.c_void_p), ("mapq", ctypes.c_void_p), ("mapq_validity", ctypes.c_void_p),
+                ("reference", ctypes.c_void_p), ("reference_validity", ctypes.c_void_p),
+                ("mate_reference", ctypes.c_void_p), ("mate_reference_validity", ctypes.c_void_p),
+                ("bools", ctypes.c_void_p * 11), ("bools_validity", ctypes.c_void_p * 11)]
+
+
+_LINES_SIG = {
+    "bqsr_arrow_sam_lines": (ctypes.c_int, [vp, ctypes.POINTER(_LinesChunk), i32, vp, vp, i32, ctypes.c_char_p, i64,
+                                            vp, pp]),
+    "bqsr_adam_lines_kernel_times": (ctypes.c_int, [_capi.dblp] * 4),
+}
+LINES_STAGES = ("upload", "len", "write", "parse")
+# the string columns of a line, in bqsr_adam_lines_chunk's order
+_LINES_STRINGS = (("readName", "read_name"), ("cigar", "cigar"), ("sequence", "sequence"), ("qual", "qual"),
+                  ("attributes", "attributes"), ("mismatchingPositions", "md"))
+# (@RG field, recordGroup* column) in the order the synthesised @RG line lists them
+RG_HEADER_FIELDS = (("CN", "recordGroupSequencingCenter"), ("DS", "recordGroupDescription"),
+                    ("DT", "recordGroupRunDateEpoch"), ("FO", "recordGroupFlowOrder"),
+                    ("KS", "recordGroupKeySequence"), ("LB", "recordGroupLibrary"),
+                    ("PI", "recordGroupPredictedMedianInsertSize"), ("PL", "recordGroupPlatform"),
+                    ("PU", "recordGroupPlatformUnit"), ("SM", "recordGroupSample"))
+
+
+def _lines_lib():
+    return _capi.bind(_capi.lib(), _LINES_SIG)
+
+
+def epoch_ms_iso8601(ms: int) -> str:
+    """recordGroupRunDateEpoch as an @RG DT value: UTC ISO 8601, the
+    milliseconds written only when there are some (adam_save reads it back
+    to the same number)."""
+    from datetime import datetime, timedelta, timezone
+    t = datetime(1970, 1, 1, tzinfo=timezone.utc) + timedelta(milliseconds=int(ms))
+    frac = ".%03d" % (int(ms) % 1000) if int(ms) % 1000 else ""
+    return t.strftime("%Y-%m-%dT%H:%M:%S") + frac + "Z"
+
+
+def _distinct_rows(table, cols: Sequence[str], where: str) -> List[tuple]:
+    """the distinct tuples of `cols` (a missing column is null) over the rows whose `where` column is not null"""
+    pa, pc, _ = _pa()
+    if where not in table.column_names or table.num_rows == 0:
+        return []
+    keep = pc.is_valid(table.column(where))
+    arrs = [table.column(c) if c in table.column_names else pa.nulls(table.num_rows) for c in cols]
+    t = pa.table(arrs, names=["k%d" % i for i in range(len(cols))]).filter(keep)
+    if t.num_rows == 0:
+        return []
+    d = t.group_by(t.column_names).aggregate([])
+    return list(zip(*[d.column(n).to_pylist() for n in t.column_names]))
+
+
+def _header_value(v, what: str) -> str:
+    v = str(v)
+    if "\t" in v or "\n" in v or "\r" in v:
+        raise ValueError("adam2sam: %s %r holds a TAB, LF or CR and cannot stand in a header line" % (what, v))
+    return v
+
+
+def sam_header(table) -> bytes:
+    """The SAM header an ADAMRecord table implies, for :func:`sam_text`.
+
+    @SQ: one line per distinct (referenceId, referenceName, referenceLength,
+    referenceUrl) over the records with a referenceName, together with the
+    mate's four columns over the records with a mateReference -- wider than
+    SequenceRecord.fromADAMRecord (models/SequenceDictionary.scala), which
+    skips second-of-pair reads: every RNAME and RNEXT written must have its
+    line.  Ascending id (names without an id last, by name); SN, LN and UR
+    when not null.  The line index becomes BAM's refID; ids need not be dense.
+    The same id under two names, a name under two ids, or two lengths or URLs
+    for one name raise ValueError naming the contig (SequenceDictionary.+'s
+    assertion).
+    @RG: one line per distinct recordGroupName, sorted by ID (so that
+    recordGroupId is the line's index again), ID then CN DS DT FO KS LB PI PL
+    PU SM from the recordGroup* columns, nulls left out, DT as UTC ISO 8601;
+    two values of a field under one name raise ValueError.
+    No @HD, @PG or @CO line: nothing in ADAMRecord carries them."""
+    sq = set(_distinct_rows(table, ("referenceId", "referenceName", "referenceLength", "referenceUrl"),
+                            "referenceName"))
+    sq |= set(_distinct_rows(table, ("mateReferenceId", "mateReference", "mateReferenceLength", "mateReferenceUrl"),
+                             "mateReference"))
+    by_name: Dict[str, tuple] = {}
+    by_id: Dict[int, str] = {}
+    for rid, name, length, url in sorted(sq, key=lambda q: (q[1], q[0] is None, q[0] or 0, repr(q[2:]))):
+        if name in by_name:
+            o, q = by_name[name], (rid, name, length, url)
+            k, what = (0, "ids") if o[0] != rid else (2, "lengths") if o[2] != length else (3, "URLs")
+            raise ValueError("adam2sam: contig %r has two %s (%r and %r)" % (name, what, o[k], q[k]))
+        if rid is not None and rid in by_id:
+            raise ValueError("adam2sam: contig id %d has two names (%r and %r)" % (rid, by_id[rid], name))
+        by_name[name] = (rid, name, length, url)
+        if rid is not None:
+            by_id[rid] = name
+    lines = []
+    for rid, name, length, url in sorted(by_name.values(), key=lambda q: (q[0] is None, q[0] or 0, q[1])):
+        f = ["@SQ", "SN:" + _header_value(name, "contig")]
+        if length is not None:
+            f.append("LN:%d" % length)
+        if url is not None:
+            f.append("UR:" + _header_value(url, "contig URL"))
+        lines.append("\t".join(f))
+    cols = ("recordGroupName",) + tuple(c for _, c in RG_HEADER_FIELDS)
+    groups: Dict[str, tuple] = {}
+    for row in _distinct_rows(table, cols, "recordGroupName"):
+        o = groups.setdefault(row[0], row)
+        if o != row:
+            k = next(i for i in range(1, len(row)) if o[i] != row[i])
+            raise ValueError("adam2sam: read group %r has two values of %s (%r and %r)" % (row[0], cols[k], o[k],
+                                                                                          row[k]))
+    for name in sorted(groups):
+        f = ["@RG", "ID:" + _header_value(name, "read group")]
+        for (tag, _c), v in zip(RG_HEADER_FIELDS, groups[name][1:]):
+            if v is not None:
+                f.append("%s:%s" % (tag, epoch_ms_iso8601(v) if tag == "DT" else _header_value(v, "read group " + tag)))
+        lines.append("\t".join(f))
+    return ("\n".join(lines) + "\n").encode("utf-8") if lines else b""
+
+
+def header_sq_names(header: bytes) -> List[str]:
+    """the @SQ names of a SAM header text, in line order (the first line of a name)"""
+    from .adam_save import HeaderInfo
+    return list(dict.fromkeys(kv["SN"] for kv in HeaderInfo(header.decode("latin-1")).sq))
+
+
+def _qual_bytes(a):
+    """a qual chunk with chars above 0x7F, re-encoded as _string_column(kind="qual") reads it: one byte c & 0xFF per
+    Java char (UTF-16 code unit), so that QUAL keeps SEQ's length"""
+    pa, _, _ = _pa()
+    out = [None if v is None else (np.frombuffer(v.encode("utf-16-le"), "<u2") & 0xFF).astype(np.uint8).tobytes()
+           for v in a.to_pylist()]
+    return pa.array(out, pa.binary())
+
+
+def sam_text(table, header: Optional[bytes] = None, ctx=None, stream=None):
+    """An ADAMRecord table (pyarrow) as a :class:`adam_amd.sam.SamText`: every
+    record rendered as its SAM line on the device (bqsr_arrow_sam_lines,
+    include/adam_sam.h: the line's rules and refusals are stated there) and
+    the text parsed there like SAM input -- so ``text()``, ``bam_records()``,
+    ``sort()``, ``flagstat()`` and the sinks of `transform` take it.  Loads
+    every column a line needs (ArrowReads loads BQSR's only).
+
+    header: the header lines to put before the records, as they are (a SAM or
+    BAM file's: the lossless round trip); None: :func:`sam_header` of the
+    table.  A record whose referenceName or mateReference is not among the
+    header's @SQ names raises ValueError naming it.  The whole table's column
+    buffers and its text are resident on the device at once; a table whose
+    text does not fit raises BQSRError (UNSUPPORTED).
+
+    The result carries ``adam_lines``: seconds on the host for the header
+    and the chunk buffers, the device's milliseconds per stage."""
+    import time
+
+    from . import bqsr
+    from ._capi import check
+    from .adam_save import BOOL_COLS
+    from .sam import SamText
+    pa, pc, _ = _pa()
+    L = _lines_lib()
+    ctx = ctx or bqsr.Context.get(0)
+    t0 = time.perf_counter()
+    if header is None:
+        header = sam_header(table)
+    header = bytes(header)
+    t1 = time.perf_counter()
+    names = set(table.column_names)
+    ref_names = header_sq_names(header)
+    value_set = pa.array(ref_names, pa.string())
+    blob = b"".join(n.encode("utf-8") for n in ref_names)
+    ref_off = np.zeros(len(ref_names) + 1, np.int64)
+    np.cumsum([len(n.encode("utf-8")) for n in ref_names], out=ref_off[1:])
+    keep = []
+
+    def flat(a):
+        if a.offset:
+            a = pa.concat_arrays([a])
+        keep.append(a)
+        return a
+
+    def addr(b):
+        return None if b is None else b.address
+
+    chunks = []
+    r0 = 0
+    for rb in table.to_batches():
+        m = rb.num_rows
+        if m == 0:
+            continue
+        col = lambda f: rb.column(rb.schema.get_field_index(f))  # noqa: E731
+        C = _LinesChunk()
+        C.n_reads = m
+        for fld, attr in _LINES_STRINGS:
+            if fld not in names:
+                continue
+            a = col(fld)
+            if a.type != pa.string():
+                a = a.cast(pa.string())
+            a = flat(a)
+            b = a.buffers()
+            if fld == "qual" and b[2] is not None:
+                lo, hi = (int(v) for v in np.frombuffer(b[1], np.int32, m + 1)[[0, m]])
+                d = np.frombuffer(b[2], np.uint8)[lo:hi]
+                if d.size and int(d.max()) >= 0x80:
+                    a = flat(_qual_bytes(a))
+                    b = a.buffers()
+            setattr(C, attr, _Strings(addr(b[1]), addr(b[2]) or addr(b[1]), addr(b[0])))
+        for fld, v, vv in (("referenceName", "reference", "reference_validity"),
+                           ("mateReference", "mate_reference", "mate_reference_validity")):
+            if fld not in names:
+                continue
+            a = col(fld)
+            idx = pc.index_in(a, value_set=value_set)
+            if idx.null_count != a.null_count:
+                r = int(np.flatnonzero(np.asarray(pc.and_(pc.is_valid(a), pc.is_null(idx))))[0])
+                raise ValueError("adam2sam: record %d: %s %r is not among the header's @SQ names"
+                                 % (r0 + r, fld, a[r].as_py()))
+            idx = flat(idx.cast(pa.int32()))
+            b = idx.buffers()
+            setattr(C, v, addr(b[1]))
+            setattr(C, vv, addr(b[0]))
+        for fld, typ, v, vv in (("start", pa.int64(), "start", "start_validity"),
+                                ("mateAlignmentStart", pa.int64(), "mate_start", "mate_start_validity"),
+                                ("mapq", pa.int32(), "mapq", "mapq_validity")):
+            if fld in names:
+                a = col(fld)
+                a = flat(a if a.type == typ else a.cast(typ))
+                b = a.buffers()
+                setattr(C, v, addr(b[1]))
+                setattr(C, vv, addr(b[0]))
+        for k, fld in enumerate(BOOL_COLS):
+            if fld in names:
+                b = flat(col(fld)).buffers()
+                C.bools[k], C.bools_validity[k] = addr(b[1]), addr(b[0])
+        chunks.append(C)
+        r0 += m
+    arr = (_LinesChunk * max(1, len(chunks)))(*chunks)
+    blob_a = np.frombuffer(blob, np.uint8) if blob else np.zeros(1, np.uint8)
+    t2 = time.perf_counter()
+    h = ctypes.c_void_p()
+    check(L.bqsr_arrow_sam_lines(ctx.handle, arr, len(chunks), blob_a.ctypes.data, ref_off.ctypes.data, len(ref_names),
+                                 header, len(header), stream, ctypes.byref(h)))
+    del keep
+    sam = SamText.adopt(h, ctx)
+    sam.adam_lines = dict(header_s=t1 - t0, chunks_s=t2 - t1, call_s=time.perf_counter() - t2,
+                          **{k + "_ms": v for k, v in
+                             _capi.stage_times(L.bqsr_adam_lines_kernel_times, LINES_STAGES).items()})
+    return sam
+
+
 def read_table(path: str, columns: Optional[Sequence[str]] = None):
     """The ADAMRecord Parquet file (or directory of part files) at `path`, the
     requested columns only (those the file lacks are left out)."""

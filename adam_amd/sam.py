@@ -114,6 +114,13 @@ class SamText:
         check(parse(self.ctx.handle, src, len(data), stream, ctypes.byref(self.h)))
 
     @classmethod
+    def adopt(cls, h: ctypes.c_void_p, ctx: bqsr.Context) -> "SamText":
+        """A bqsr_sam another call of the library made (parquet.sam_text), owned from here."""
+        self = cls.__new__(cls)
+        self.L, self.ctx, self.h, self.bam = _lib(), ctx, h, False
+        return self
+
+    @classmethod
     def read(cls, path: str, ctx: Optional[bqsr.Context] = None) -> "SamText":
         """A .sam or .bam file (BAM by its BGZF magic)."""
         with open(path, "rb") as fh:

@@ -16,8 +16,9 @@ adam_save.py).  BAM holds what the SAM spec allows: a record it cannot hold
 -- the reference's trimmed recalibrated QUAL strings and its chars above
 0x7F among them, which the SAM text sink writes as they are -- fails the job
 with BQSRError (UNSUPPORTED) naming the read, and no output appears.
-ADAMRecord Parquet input cannot be written as BAM (that path has no SAM lines
-to encode): a ValueError before anything is read.  ADAMRecord
+ADAMRecord Parquet input cannot be written as BAM here (that path has no SAM
+lines to encode): a ValueError before anything is read; `adam2sam`
+(adam2sam.py) renders the lines and writes SAM or BAM.  ADAMRecord
 Parquet in goes through ``transform_parquet``: Arrow decodes the Parquet
 pages on host threads, the column buffers go to the device as they are
 (parquet.ArrowReads), MarkDuplicates, the BQSR batch and the recalibrated
@@ -653,8 +654,8 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
     if bam_compressor == "device" and bam_level is not None:
         raise ValueError(DEVICE_LEVEL_REFUSAL)
     if bam_out and is_parquet(inp):  # before anything is read
-        raise ValueError("ADAM Parquet input cannot be written as BAM (no SAM lines to encode): "
-                         "use a .adam / .parquet output, or SAM / BAM input")
+        raise ValueError("ADAM Parquet input cannot be written as BAM by transform (no SAM lines to encode): "
+                         "python -m adam_amd.adam2sam writes it as BAM or SAM")
     if is_parquet(inp):
         return transform_parquet(inp, out, mark_duplicates, recalibrate, dbsnp, device, overwrite, sort_reads)
     if sort_reads:  # refused before any output file or parse exists

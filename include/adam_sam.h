@@ -1294,6 +1294,80 @@ bqsr_status bqsr_parquet_gzip(const uint8_t* in, int64_t in_len, const char* pat
 bqsr_status bqsr_gzip_bytes(const uint8_t* in, int64_t n, int32_t huffman, int32_t level, uint8_t* out, int64_t cap,
                             int64_t* out_len);
 
+/* adam2sam: ADAMRecord Parquet out as SAM or BAM.  The records of an Arrow
+ * table are rendered as SAM lines on the device (adam_lines.hip) and the text
+ * parsed like SAM input, so the result is an ordinary bqsr_sam: the SAM text
+ * sink, the BAM encoder, both compressors, the BAM index, bqsr_sam_sort and
+ * bqsr_sam_flagstat take it as they take a bqsr_sam_parse / bqsr_bam_parse
+ * result.  One bqsr_adam_lines_chunk per Arrow record batch, its buffers as
+ * they are (array offsets 0; strings as bqsr_arrow_strings; a NULL column is
+ * all null; a NULL validity: all valid; a null boolean reads as false).
+ * reference / mate_reference: int32 indices of referenceName / mateReference
+ * into the reference names (ref_names_blob cut by ref_name_offsets [n_ref +
+ * 1]).  `header`: the header lines of the text (nothing else; "" allowed) --
+ * RNAME becomes a referenceName, and BAM's refID, only through its @SQ lines.
+ *
+ * A record's line is the inverse of SAMRecordConverter.convert
+ * (core/converters/SAMRecordConverter.scala:26-144), fields in SAM's order:
+ *   QNAME CIGAR SEQ QUAL  the column's bytes (readName, cigar, sequence,
+ *            qual); null or empty: "*".  Bytes are copied as they are (the
+ *            caller re-encodes a qual chunk with chars above 0x7F: one byte
+ *            c & 0xFF per Java char, as parquet.py reads qual);
+ *   FLAG     0 when all eleven booleans are false (the converter reads FLAG 0
+ *            that way, and FLAG 0x104 too, which therefore comes back as 0);
+ *            else 0x1 readPaired, 0x2 properPair, 0x4 !readMapped, 0x8
+ *            readPaired && !mateMapped, 0x10 readNegativeStrand, 0x20
+ *            mateNegativeStrand, 0x40 firstOfPair, 0x80 secondOfPair, 0x100
+ *            !primaryAlignment, 0x200 failedVendorQualityChecks, 0x400
+ *            duplicateRead;
+ *   RNAME    the reference name, "*" when null;
+ *   POS      start + 1, 0 when null;
+ *   MAPQ     mapq; when null 255 with a referenceName (the one case in which
+ *            the converter drops a MAPQ), else 0;
+ *   RNEXT    "*" when null, "=" for RNAME's index, else the name;
+ *   PNEXT    mateAlignmentStart + 1, 0 when null;
+ *   TLEN     0 (ADAMRecord has no field for it);
+ *   optional fields  `attributes` cut at its TABs, the fields in reverse (the
+ *            converter prepends: htsjdk's order again), then MD:Z:<
+ *            mismatchingPositions> when that is not null.  Null or empty
+ *            attributes give none.  No RG tag is made from recordGroupName:
+ *            it is among the attributes already.
+ * Refused, naming the first such record (bqsr_last_error_read), nothing
+ * produced -- BQSR_ERR_UNSUPPORTED, a record SAM cannot hold (as the BAM
+ * encoder's refusals): TAB, LF or CR inside readName, cigar, sequence, qual
+ * or mismatchingPositions; LF or CR inside attributes; start or
+ * mateAlignmentStart outside [0, 2^31 - 2]; mapq outside [0, 255] --
+ * BQSR_ERR_SAM_PARSE, a malformed record (as bqsr_bam_parse's): an attribute
+ * that is not [A-Za-z][A-Za-z0-9]:[AifZHB]:..., a reference index outside
+ * [0, n_ref).  A record with both is reported as malformed.  The whole
+ * table's buffers and its text stay on the device for the call:
+ * BQSR_ERR_UNSUPPORTED when the text does not fit. */
+typedef struct bqsr_adam_lines_chunk {
+  int64_t n_reads;
+  bqsr_arrow_strings read_name, cigar, sequence, qual, attributes, md; /* md = mismatchingPositions */
+  const int64_t* start;
+  const uint8_t* start_validity;
+  const int64_t* mate_start; /* mateAlignmentStart */
+  const uint8_t* mate_start_validity;
+  const int32_t* mapq;
+  const uint8_t* mapq_validity;
+  const int32_t* reference;
+  const uint8_t* reference_validity;
+  const int32_t* mate_reference;
+  const uint8_t* mate_reference_validity;
+  /* readPaired, properPair, readMapped, mateMapped, readNegativeStrand, mateNegativeStrand, firstOfPair,
+   * secondOfPair, primaryAlignment, failedVendorQualityChecks, duplicateRead */
+  const uint8_t* bools[11];
+  const uint8_t* bools_validity[11];
+} bqsr_adam_lines_chunk;
+bqsr_status bqsr_arrow_sam_lines(bqsr_context* ctx, const bqsr_adam_lines_chunk* chunks, int32_t n_chunks,
+                                 const uint8_t* ref_names_blob, const int64_t* ref_name_offsets, int32_t n_ref,
+                                 const char* header, int64_t header_bytes, void* stream, bqsr_sam** out);
+/* MEASUREMENT ONLY: this thread's last bqsr_arrow_sam_lines: the uploads, the
+ * length pass and the write pass by device events, the parse of the text by
+ * the host's clock, in milliseconds (tools/bench_adam.py). */
+bqsr_status bqsr_adam_lines_kernel_times(double* upload_ms, double* len_ms, double* write_ms, double* parse_ms);
+
 #ifdef __cplusplus
 }
 #endif

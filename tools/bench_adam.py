@@ -75,6 +75,20 @@ the external pass the flag replaces -- timed, its bytes required to equal the
 device's.  On a tree whose transform has no bam_index argument the no-index
 legs alone are run: the same tool measures the parent commit.  One JSON line.
 
+    python tools/bench_adam.py --adam2sam [--reads 2000000] [--bam-level 6]
+
+--adam2sam measures `adam2sam` (adam_amd/adam2sam.py): the synthetic reads
+written once as .adam (--compression), then in this process, three timed runs
+each after a warm-up (all reported, with their spread), ADAM -> SAM and ADAM ->
+BAM (host compressor at --bam-level, and the device compressor) next to
+`transform` SAM -> SAM and SAM -> BAM over the same reads (no MarkDuplicates, no
+BQSR: the same sinks).  Per adam2sam leg the phase split -- Arrow's Parquet
+read on the host, the header synthesis, the chunk buffers, their upload, the
+two line kernels by device events (per byte of record text too), the parse,
+emit, close.  The same reads are parsed once more as BAM input, whose lines
+bam_lines_len / bam_lines_write render: a rocprofv3 --kernel-trace --stats run
+of this leg puts the two pairs of kernels side by side.  One JSON line.
+
     python tools/bench_adam.py --print-tags [--reads 2000000] [--variant-lib LIB.so]
 
 --mpileup measures `adam mpileup` (adam_amd/mpileup.py) over the same
@@ -1063,8 +1077,104 @@ def bench_bam_index(a):
         "not_measured": "real coverage (the synthetic reads spread evenly), inputs above one partition"}))
 
 
+def bench_adam2sam(a):
+    """--adam2sam: the synthetic reads written once as .adam, then in one
+    process, after a warm-up each, max(3, --reps) timed runs of ADAM -> SAM and
+    ADAM -> BAM (adam2sam) next to SAM -> SAM and SAM -> BAM (transform without
+    MarkDuplicates or BQSR: the same sinks over the same records).  Phases of
+    the adam2sam legs: the Parquet read (Arrow's decode on host threads),
+    the header synthesis, the chunk buffers and their upload, the two line
+    kernels by device events, the parse, emit, close.  The same reads are
+    also parsed as BAM input (bam_ingest.hip renders their lines with
+    bam_lines_len / bam_lines_write): under rocprofv3 --kernel-trace --stats
+    one run gives both pairs of kernels."""
+    t0 = time.perf_counter()
+    data = synthetic_sam(a.reads, a.len, p_q2tail=0.0)
+    log("generated %d bytes in %.1f s" % (len(data), time.perf_counter() - t0))
+    import torch
+    from adam_amd import transform as T
+    from adam_amd.adam2sam import adam2sam
+    from adam_amd.sam import SamText
+    torch.zeros(1, device="cuda")
+    work = a.dir or tempfile.mkdtemp(prefix="bench_adam_")
+    os.makedirs(work, exist_ok=True)
+    src, adam, bam_in = (os.path.join(work, n) for n in ("in.sam", "in.adam", "in.bam"))
+    with open(src, "wb") as fh:
+        fh.write(data)
+    n_bytes = len(data)
+    header_bytes = len(T.sam_partitions(data, len(data))[0])
+    del data
+    reps = max(3, a.reps)
+
+    def leg(run, out, **kw):
+        runs = []
+        for i in range(1 + reps):  # the first run warms
+            log("%s %s -> %s %s" % ("warm-up" if i == 0 else "timed", run.__name__, os.path.basename(out), kw or ""))
+            t = time.perf_counter()
+            st = run(adam if run is adam2sam else src, out, overwrite=True, **kw)
+            runs.append((time.perf_counter() - t, st))
+        if runs[-1][1]["reads"] != a.reads:
+            raise SystemExit("wrote %d reads, expected %d" % (runs[-1][1]["reads"], a.reads))
+        times = [dt for dt, _ in runs[1:]]
+        dt, st = min(runs[1:], key=lambda r: r[0])
+        r = {"seconds": dt, "seconds_all": times, "seconds_spread": max(times) - min(times),
+             "reads_per_s": a.reads / dt, "output_bytes": os.path.getsize(out), "phases_s": st.get("phases")}
+        if "adam_lines" in st:
+            L = st["adam_lines"]
+            r["lines"] = dict(L, len_ms_all=[s["adam_lines"]["len_ms"] for _, s in runs[1:]],
+                              write_ms_all=[s["adam_lines"]["write_ms"] for _, s in runs[1:]])
+        return r
+
+    res = {}
+    try:
+        t = time.perf_counter()
+        T.transform(src, adam, compression=a.compression, part_reads=a.part_reads, overwrite=True)
+        T.transform(src, bam_in, bam_level=1, overwrite=True)
+        log("wrote in.adam and in.bam in %.1f s" % (time.perf_counter() - t))
+        adam_bytes = sum(os.path.getsize(os.path.join(adam, f)) for f in os.listdir(adam))
+        res["adam_to_sam"] = leg(adam2sam, os.path.join(work, "a.sam"))
+        with open(os.path.join(work, "a.sam"), "rb") as fh:  # the record text the two kernels wrote
+            head = fh.read(1 << 16)
+        text_bytes = res["adam_to_sam"]["output_bytes"] - len(T.sam_partitions(head, len(head))[0])
+        res["adam_to_bam"] = leg(adam2sam, os.path.join(work, "a.bam"), bam_level=a.bam_level)
+        res["adam_to_bam_device"] = leg(adam2sam, os.path.join(work, "a.bam"), bam_compressor="device")
+        res["sam_to_sam"] = leg(T.transform, os.path.join(work, "s.sam"))
+        res["sam_to_bam"] = leg(T.transform, os.path.join(work, "s.bam"), bam_level=a.bam_level)
+        res["sam_to_bam_device"] = leg(T.transform, os.path.join(work, "s.bam"), bam_compressor="device")
+        ingest = []
+        for i in range(1 + reps):  # BAM input: bam_lines_len / bam_lines_write over the same reads
+            t = time.perf_counter()
+            s = SamText.read(bam_in)
+            n_text = s.counts().text_bytes
+            s.close()
+            ingest.append(time.perf_counter() - t)
+        for k in ("adam_to_sam", "adam_to_bam", "adam_to_bam_device"):
+            L = res[k]["lines"]
+            body = L["record_text_bytes"] = text_bytes
+            L["len_ns_per_text_byte"] = min(L["len_ms_all"]) * 1e6 / body
+            L["write_ns_per_text_byte"] = min(L["write_ms_all"]) * 1e6 / body
+            L["write_GB_per_s_of_text"] = body / (min(L["write_ms_all"]) * 1e-3) / 1e9
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps({
+        "metric": "adam2sam: ADAM Parquet -> SAM / BAM (lines rendered on the device) next to transform SAM -> SAM / "
+                  "BAM, same reads, same process, no MarkDuplicates, no BQSR",
+        "reads": a.reads, "read_len": a.len, "sam_bytes": n_bytes, "sam_record_bytes": n_bytes - header_bytes,
+        "adam_bytes": adam_bytes, "adam_compression": a.compression, "reps": reps, "bam_level": a.bam_level,
+        "legs": res,
+        "bam_input_parse": {"seconds_all": ingest[1:], "text_bytes": n_text,
+                            "what": "SamText.read of the same reads as BAM (device inflate, bam_lines_len / "
+                                    "bam_lines_write, the parse): the kernels' times come from a rocprofv3 "
+                                    "--kernel-trace --stats run of this leg"},
+        "not_measured": "real data (the synthetic reads carry two or three short tags), inputs beyond one resident "
+                        "table"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--adam2sam", action="store_true",
+                    help="measure adam2sam (ADAM -> SAM / BAM) next to transform SAM -> SAM / BAM instead")
     ap.add_argument("--bam-index", action="store_true",
                     help="--bam-out: measure -bam_index instead (legs with and without the index, both compressors)")
     ap.add_argument("--bam-out", action="store_true",
@@ -1098,6 +1208,8 @@ def main():
     ap.add_argument("--reps", type=int, default=1)
     ap.add_argument("--dir", default=None, help="scratch directory (default: a temporary one)")
     a = ap.parse_args()
+    if a.adam2sam:
+        return bench_adam2sam(a)
     if a.flagstat:
         return bench_flagstat(a)
     if a.print_tags:
