@@ -43,7 +43,10 @@ EXPORTS = [
     "bqsr_sam_flagstat", "bqsr_flagstat_arrow", "bqsr_flagstat_arrow_device",
     "bqsr_bgzf_inflate", "bqsr_sam_bam_form", "bqsr_sam_markdup_path",
     "bqsr_sam_pileup_prepare", "bqsr_sam_pileup_columns", "bqsr_arrow_pileup_prepare", "bqsr_arrow_pileup_columns",
-    "bqsr_pileup_kernel_times",
+    "bqsr_pileup_kernel_times", "bqsr_sam_pileup_device_columns", "bqsr_arrow_pileup_device_columns",
+    "bqsr_sam_pileup_read_spans", "bqsr_arrow_pileup_read_spans",
+    "bqsr_parquet_pages_create", "bqsr_parquet_pages_destroy", "bqsr_parquet_pages_size", "bqsr_parquet_pages_emit",
+    "bqsr_parquet_pages_minmax",
     "bqsr_sam_mpileup_prepare", "bqsr_sam_mpileup_text", "bqsr_arrow_mpileup_prepare", "bqsr_arrow_mpileup_text",
     "bqsr_mpileup_kernel_times",
     "bqsr_sam_realign_targets_prepare", "bqsr_sam_realign_targets_fetch", "bqsr_arrow_realign_targets_prepare",

@@ -553,13 +553,9 @@ bqsr_status pileup_prepare(bqsr_context* ctx, PileupState& A, const PileupView& 
   return ok();
 }
 
-bqsr_status pileup_columns(bqsr_context* ctx, PileupState& A, const PileupView& V, const bqsr_pileup_host* dst,
-                           hipStream_t s, const char* who) {
-  if (!A.prepared) return fail(BQSR_ERR_INVALID_ARG, std::string(who) + " before its prepare call");
-  g_pileup_ms[PILEUP_EMIT] = 0.0;
+// the emit pass over the prepared range into the state's columns (queued on s; m = A.n_rows > 0)
+bqsr_status pileup_emit_columns(bqsr_context* ctx, PileupState& A, const PileupView& V, hipStream_t s) {
   const int64_t m = A.n_rows;
-  if (m == 0) return ok();
-  const size_t W = (size_t)((m + 63) / 64);
   if (A.cap_rows < m) {  // one block, carved: the 8-byte columns first, every column 8-byte aligned
     if (A.col_block) (void)hipFree(A.col_block);
     A.col_block = nullptr;
@@ -598,6 +594,17 @@ bqsr_status pileup_columns(bqsr_context* ctx, PileupState& A, const PileupView& 
   JOB_TRY(launch(pilk::pileup_emit, pileup_grid(ctx, (groups + pilk::kWaves - 1) / pilk::kWaves), pilk::kThreads, s,
                  P));
   HIP_TRY(A.clock.mark(PILEUP_EMIT_1, s));
+  return BQSR_OK;
+}
+
+bqsr_status pileup_columns(bqsr_context* ctx, PileupState& A, const PileupView& V, const bqsr_pileup_host* dst,
+                           hipStream_t s, const char* who) {
+  if (!A.prepared) return fail(BQSR_ERR_INVALID_ARG, std::string(who) + " before its prepare call");
+  g_pileup_ms[PILEUP_EMIT] = 0.0;
+  const int64_t m = A.n_rows;
+  if (m == 0) return ok();
+  const size_t W = (size_t)((m + 63) / 64);
+  JOB_TRY(pileup_emit_columns(ctx, A, V, s));
   auto cp = [&](void* d, const void* src, size_t bytes) -> hipError_t {
     if (!d || !bytes) return hipSuccess;
     return hipMemcpyAsync(d, src, bytes, hipMemcpyDeviceToHost, s);
@@ -622,6 +629,35 @@ bqsr_status pileup_columns(bqsr_context* ctx, PileupState& A, const PileupView& 
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return fail(BQSR_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
   A.clock.add(g_pileup_ms[PILEUP_EMIT], PILEUP_EMIT_0, PILEUP_EMIT_1);
+  return ok();
+}
+
+// the emit pass, the columns left on the device: *cols their device addresses
+bqsr_status pileup_device_columns(bqsr_context* ctx, PileupState& A, const PileupView& V, bqsr_pileup_host* cols,
+                                  hipStream_t s, const char* who) {
+  if (!A.prepared) return fail(BQSR_ERR_INVALID_ARG, std::string(who) + " before its prepare call");
+  g_pileup_ms[PILEUP_EMIT] = 0.0;
+  *cols = bqsr_pileup_host{};
+  if (A.n_rows == 0) return ok();
+  JOB_TRY(pileup_emit_columns(ctx, A, V, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  A.clock.add(g_pileup_ms[PILEUP_EMIT], PILEUP_EMIT_0, PILEUP_EMIT_1);
+  const pilk::Cols& C = A.C;
+  *cols = bqsr_pileup_host{C.read, C.position, C.range_offset, C.range_length, C.reference_base, C.read_base,
+                           C.sanger, C.mapq, C.soft, C.rev, C.read_start, C.read_end, C.v_range,
+                           C.v_reference_base, C.v_read_base, C.v_mapq};
+  return ok();
+}
+
+// readStart and readEnd per read of the prepared range into host memory
+bqsr_status pileup_read_spans(PileupState& A, const PileupView& V, int64_t* read_start, int64_t* read_end,
+                              hipStream_t s, const char* who) {
+  if (!A.prepared) return fail(BQSR_ERR_INVALID_ARG, std::string(who) + " before its prepare call");
+  if (A.n == 0) return ok();
+  const size_t bytes = (size_t)A.n * sizeof(int64_t);
+  HIP_TRY(hipMemcpyAsync(read_start, V.R.start + A.r0, bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(read_end, A.X.rend, bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return ok();
 }
 
@@ -726,6 +762,43 @@ bqsr_status bqsr_arrow_pileup_columns(bqsr_context* ctx, bqsr_arrow* a, const bq
   HIP_TRY(hipSetDevice(ctx->device));
   PileupState& A = *job_state<PileupState>(a->pileup);
   return pileup_columns(ctx, A, pileup_view(a, A), dst, S(stream), "bqsr_arrow_pileup_columns");
+}
+
+bqsr_status bqsr_sam_pileup_device_columns(bqsr_context* ctx, bqsr_sam* s, bqsr_pileup_host* cols, void* stream) {
+  if (!ctx || !s || !cols) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_pileup_device_columns: bad arguments");
+  if (!s->pileup) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_pileup_device_columns before bqsr_sam_pileup_prepare");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return pileup_device_columns(ctx, *job_state<PileupState>(s->pileup), pileup_view(s), cols, S(stream),
+                               "bqsr_sam_pileup_device_columns");
+}
+
+bqsr_status bqsr_arrow_pileup_device_columns(bqsr_context* ctx, bqsr_arrow* a, bqsr_pileup_host* cols, void* stream) {
+  if (!ctx || !a || !cols) return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_device_columns: bad arguments");
+  if (!a->pileup)
+    return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_device_columns before bqsr_arrow_pileup_prepare");
+  HIP_TRY(hipSetDevice(ctx->device));
+  PileupState& A = *job_state<PileupState>(a->pileup);
+  return pileup_device_columns(ctx, A, pileup_view(a, A), cols, S(stream), "bqsr_arrow_pileup_device_columns");
+}
+
+bqsr_status bqsr_sam_pileup_read_spans(bqsr_context* ctx, bqsr_sam* s, int64_t* read_start, int64_t* read_end,
+                                       void* stream) {
+  if (!ctx || !s || !read_start || !read_end)
+    return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_pileup_read_spans: bad arguments");
+  if (!s->pileup) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_pileup_read_spans before bqsr_sam_pileup_prepare");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return pileup_read_spans(*job_state<PileupState>(s->pileup), pileup_view(s), read_start, read_end, S(stream),
+                           "bqsr_sam_pileup_read_spans");
+}
+
+bqsr_status bqsr_arrow_pileup_read_spans(bqsr_context* ctx, bqsr_arrow* a, int64_t* read_start, int64_t* read_end,
+                                         void* stream) {
+  if (!ctx || !a || !read_start || !read_end)
+    return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_read_spans: bad arguments");
+  if (!a->pileup) return fail(BQSR_ERR_INVALID_ARG, "bqsr_arrow_pileup_read_spans before bqsr_arrow_pileup_prepare");
+  HIP_TRY(hipSetDevice(ctx->device));
+  PileupState& A = *job_state<PileupState>(a->pileup);
+  return pileup_read_spans(A, pileup_view(a, A), read_start, read_end, S(stream), "bqsr_arrow_pileup_read_spans");
 }
 
 bqsr_status bqsr_pileup_kernel_times(double* count_ms, double* emit_ms) {

@@ -33,6 +33,12 @@ What is kept from the reference, quirks included:
 
     python -m adam_amd.reads2ref INPUT.{sam,bam,adam} OUTPUT.adam [-mapq N] [-aggregate]
         [-parquet_compression gzip|snappy|none] [-part_reads N] [-partition_bytes N] [-overwrite]
+        [-parquet_encoder host|device]
+
+``-parquet_encoder device`` builds the part files' data pages on the GPU from
+the columns the emit pass leaves there (adam_amd/parquet_pages.py): only the
+encoded pages are downloaded; the host adds page headers, dictionary pages,
+the codec and the footer.  The default, ``host``, is Arrow's writer.
 """
 from __future__ import annotations
 
@@ -92,6 +98,10 @@ _SIG = {
     "bqsr_sam_pileup_columns": (ctypes.c_int, [vp, vp, ctypes.POINTER(PileupHost), vp]),
     "bqsr_arrow_pileup_prepare": (ctypes.c_int, [vp, vp, i64, i64, vp, vp, vp, i32, vp, ctypes.POINTER(PileupSizes)]),
     "bqsr_arrow_pileup_columns": (ctypes.c_int, [vp, vp, ctypes.POINTER(PileupHost), vp]),
+    "bqsr_sam_pileup_device_columns": (ctypes.c_int, [vp, vp, ctypes.POINTER(PileupHost), vp]),
+    "bqsr_arrow_pileup_device_columns": (ctypes.c_int, [vp, vp, ctypes.POINTER(PileupHost), vp]),
+    "bqsr_sam_pileup_read_spans": (ctypes.c_int, [vp, vp, vp, vp, vp]),
+    "bqsr_arrow_pileup_read_spans": (ctypes.c_int, [vp, vp, vp, vp, vp]),
     "bqsr_pileup_kernel_times": (ctypes.c_int, [dblp, dblp]),
 }
 
@@ -312,6 +322,144 @@ def arrow_pileups(reads, r0: int = 0, n: Optional[int] = None, stream=None):
     return _table(sz.n_rows, arrays, _arrow_read_level(table, r0, n))
 
 
+# ---- -parquet_encoder device: the part files' data pages built on the GPU ----
+# (adam_amd/parquet_pages.py; the columns stay on the device, only the encoded pages come back)
+
+# the int32 columns small enough for a dense-range dictionary [min, max], index = value - min: (field, device
+# column, validity bitmap)
+_SMALL_INTS = (("rangeOffset", "range_offset", "range_valid"), ("rangeLength", "range_length", "range_valid"),
+               ("sangerQuality", "sanger_quality", None), ("mapQuality", "map_quality", "map_quality_valid"),
+               ("numSoftClipped", "num_soft_clipped", None), ("numReverseStrand", "num_reverse_strand", None))
+
+
+# readStart and readEnd with the device encoder, by codec: "dictionary" -- one entry per read of the part
+# (duplicates are legal), the `read` column as indices, the stream readName already has -- or "plain" int64 like
+# position.  Measured on the 2M-read run: the dictionary form is the faster under every codec and the
+# smaller under snappy; under gzip, which folds PLAIN's runs of one value to almost nothing, it is 12 % larger in
+# all, so gzip -- chosen for size -- keeps PLAIN.
+READ_SPANS = {"gzip": "plain", "snappy": "dictionary", "none": "dictionary"}
+
+
+def _page_columns(enc, D: PileupHost, n_rows: int, n_reads: int, rl: _ReadLevel, spans, page_rows: int, device: int,
+                  stream=None):
+    """The 25 parquet_pages.Column of a part from the device columns D (their
+    device addresses, bqsr_*_pileup_device_columns): what :func:`_table`
+    builds on the host, as descriptors.  spans: the reads' (readStart,
+    readEnd) arrays (bqsr_*_pileup_read_spans), or None to write the two
+    columns PLAIN."""
+    import torch
+
+    from . import parquet_pages as PP
+    n = n_rows
+    dev = torch.device("cuda", device)
+    held = []  # the uploaded read-level tables, alive until the last encode
+
+    def up(a):
+        t = torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+        held.append(t)
+        return t.data_ptr()
+
+    def desc(kind, src, width, src_n=n, **kw):
+        return PP.ParquetColumn(kind=kind, src_width=width, src=getattr(D, src) if isinstance(src, str) else src,
+                                src_n=src_n, gather=kw.get("gather"), remap=kw.get("remap"),
+                                remap_n=kw.get("remap_n", 0), bit_width=kw.get("bit_width", 0), base=kw.get("base", 0),
+                                validity=getattr(D, kw["validity"]) if kw.get("validity") else None)
+
+    def encode(d):
+        return enc.encode(d, n, page_rows, stream)
+
+    cols = {}
+    plain64 = [("position", "position")]
+    if spans is None:
+        plain64 += [("readStart", "read_start"), ("readEnd", "read_end")]
+    for name, src in plain64:
+        cols[name] = PP.Column(name, "int64", encode(desc(PP.PLAIN_INT64, src, 8)))
+    bases = PP.plain_strings(BASES)
+    for name, src in (("referenceBase", "reference_base"), ("readBase", "read_base")):
+        d = desc(PP.DICT_INDEX, src, 1, bit_width=PP.bit_width(len(BASES)), validity=src + "_valid")
+        cols[name] = PP.Column(name, "string", encode(d), bases)
+    for name, src, valid in _SMALL_INTS:
+        cols[name] = PP.small_int_column(enc, name, desc(PP.PLAIN_INT32, src, 4, validity=valid), n, page_rows, stream)
+    # countAtPosition, the constant 1: a one-entry dictionary, every index 0 -- any byte column mapped through a
+    # table of zeros
+    zeros = up(np.zeros(256, np.int32))
+    d = desc(PP.DICT_INDEX, "read_base", 1, remap=zeros, remap_n=256, bit_width=1)
+    cols["countAtPosition"] = PP.Column("countAtPosition", "int32", encode(d), PP.plain_ints([1], "int32"))
+    # readName: the part's names are the dictionary, `read` the indices
+    names = rl.read_name
+    kw = {}
+    if names.null_count:
+        ok = np.asarray(names.is_valid().to_numpy(zero_copy_only=False), bool)
+        kw = dict(remap=up(np.where(ok, np.arange(n_reads), -1)), remap_n=n_reads)
+        names = names.fill_null("")
+    named = encode(desc(PP.DICT_INDEX, "read", 4, bit_width=PP.bit_width(n_reads), **kw))
+    cols["readName"] = PP.Column("readName", "string", named, PP.plain_string_array(names))
+    if spans is not None:  # the same index stream (when no name is null): encoded and compressed once
+        by_read = encode(desc(PP.DICT_INDEX, "read", 4, bit_width=PP.bit_width(n_reads))) if kw else named
+        for name, values in zip(("readStart", "readEnd"), spans):
+            cols[name] = PP.Column(name, "int64", by_read, PP.plain_ints(values, "int64"))
+    # the read-level fields: the read's code (-1: null) gathered through `read`, mapped through the field's
+    # code -> index table, in which an entry without a value is -1; equal index streams are encoded once
+    codes_dev: Dict[int, int] = {}
+    streams: Dict[tuple, object] = {}
+    for name, kind in _READ_LEVEL:
+        codes, valid, values = rl.coded[name]
+        if id(codes) not in codes_dev:
+            codes_dev[id(codes)] = up(np.where(valid, codes, -1))
+        has = np.asarray([v is not None for v in values], bool)
+        remap = np.where(has, np.arange(len(values)), -1).astype(np.int32) if len(values) else np.full(1, -1, np.int32)
+        key = (id(codes), remap.tobytes())
+        if key not in streams:
+            d = desc(PP.DICT_INDEX, codes_dev[id(codes)], 4, src_n=n_reads, gather=D.read, remap=up(remap),
+                     remap_n=len(remap), bit_width=PP.bit_width(len(remap)))
+            streams[key] = encode(d)
+        fill = "" if kind == "string" else 0
+        entries = [fill if v is None else v for v in values] or [fill]
+        dic = PP.plain_strings(entries) if kind == "string" else PP.plain_ints(entries, kind)
+        cols[name] = PP.Column(name, kind, streams[key], dic)
+    del held
+    return [cols[name] for name, _ in PILEUP_FIELDS]
+
+
+def _read_spans(call, ctx_handle, handle, n: int, form: str, stream=None):
+    """(readStart, readEnd) per read of the prepared range; None when the form is "plain" """
+    if form != "dictionary":
+        return None
+    spans = np.zeros((2, max(1, n)), np.int64)
+    check(call(ctx_handle, handle, spans[0].ctypes.data, spans[1].ctypes.data, stream))
+    return spans[0, :n], spans[1, :n]
+
+
+def sam_pileup_pages(sam, enc, r0: int, n: int, hdr: HeaderInfo, page_rows: int, device: int = 0, stream=None,
+                     read_spans: str = "dictionary"):
+    """(rows, parquet_pages columns or None when there is no row) of reads
+    [r0, r0 + n) of a sam.SamText, the pages encoded on the device"""
+    L = _lib()
+    sz = PileupSizes()
+    check(L.bqsr_sam_pileup_prepare(sam.ctx.handle, sam.h, r0, n, stream, ctypes.byref(sz)))
+    if sz.n_rows == 0:
+        return 0, None
+    D = PileupHost()
+    check(L.bqsr_sam_pileup_device_columns(sam.ctx.handle, sam.h, ctypes.byref(D), stream))
+    rl = _sam_read_level(sam, r0, n, hdr, stream)
+    spans = _read_spans(L.bqsr_sam_pileup_read_spans, sam.ctx.handle, sam.h, n, read_spans, stream)
+    return sz.n_rows, _page_columns(enc, D, sz.n_rows, n, rl, spans, page_rows, device, stream)
+
+
+def arrow_pileup_pages(reads, enc, r0: int, n: int, page_rows: int, device: int = 0, stream=None,
+                       read_spans: str = "dictionary"):
+    """the same for reads [r0, r0 + n) of a parquet.ArrowReads"""
+    L = _lib()
+    sz = _arrow_prepare(reads, r0, n, stream)
+    if sz.n_rows == 0:
+        return 0, None
+    D = PileupHost()
+    check(L.bqsr_arrow_pileup_device_columns(reads.ctx.handle, reads.h, ctypes.byref(D), stream))
+    rl = _arrow_read_level(reads.table, r0, n)
+    spans = _read_spans(L.bqsr_arrow_pileup_read_spans, reads.ctx.handle, reads.h, n, read_spans, stream)
+    return sz.n_rows, _page_columns(enc, D, sz.n_rows, n, rl, spans, page_rows, device, stream)
+
+
 def locus_filter(table):
     """LocusPredicate (predicates/LocusPredicate.scala) over an Arrow table of
     ADAMRecords: readMapped, primaryAlignment, !failedVendorQualityChecks,
@@ -328,27 +476,49 @@ def locus_filter(table):
 
 
 def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_bytes: int, overwrite: bool,
-               device: int, writer_args: Optional[dict] = None) -> Dict[str, object]:
+               device: int, writer_args: Optional[dict] = None, parquet_encoder: str = "host",
+               page_rows: Optional[int] = None) -> Dict[str, object]:
+    if parquet_encoder not in ("host", "device"):
+        raise ValueError("parquet_encoder is 'host' or 'device'")
+    on_device = parquet_encoder == "device"
     check_out(out, overwrite, True)
     ctx = bqsr.Context.get(device)
     ph = Phases()
     part_reads = max(1, int(part_reads))
     stats: Dict[str, object] = {"reads": 0, "pileups": 0}
-    W = AdamWriter(out, compression, overwrite=overwrite, dict_cols=PILEUP_DICT_COLS, stats_cols=PILEUP_STATS_COLS,
-                   huffman_cols=(), max_pending=2, **(writer_args or {}))
+    enc = None
+    if on_device:
+        from . import parquet_pages as PP
+        page_rows = PP.DEFAULT_PAGE_ROWS if page_rows is None else int(page_rows)
+        spans = READ_SPANS[compression or "none"]
+        W = PP.PagesWriter(out, PILEUP_FIELDS, compression, overwrite=overwrite, max_pending=2, **(writer_args or {}))
+    else:
+        W = AdamWriter(out, compression, overwrite=overwrite, dict_cols=PILEUP_DICT_COLS,
+                       stats_cols=PILEUP_STATS_COLS, huffman_cols=(), max_pending=2, **(writer_args or {}))
     ok = False
     try:
-        def emit(make_table, n, base):
+        if on_device:
+            enc = PP.Encoder(ctx)
+
+        def emit(make_table, make_pages, n, base):
             for r0 in range(0, n, part_reads):
+                m = min(part_reads, n - r0)
                 try:
                     with ph("pileups"):
-                        t = make_table(r0, min(part_reads, n - r0))
+                        if on_device:
+                            rows, cols = make_pages(r0, m)
+                        else:
+                            t = make_table(r0, m)
+                            rows = t.num_rows
                 except _capi.BQSRError as e:
                     raise rebased(e, base) from None
-                if t.num_rows:
-                    stats["pileups"] += t.num_rows
+                if rows:
+                    stats["pileups"] += rows
                     with ph("write"):
-                        W.add(t)
+                        if on_device:
+                            W.add(cols, rows)
+                        else:
+                            W.add(t)
 
         if is_parquet(inp):
             from . import parquet as P
@@ -357,7 +527,9 @@ def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_
             with ph("parse"):
                 A = P.ArrowReads(table, ctx)
             try:
-                emit(lambda r0, n: arrow_pileups(A, r0, n), table.num_rows, 0)
+                emit(lambda r0, n: arrow_pileups(A, r0, n),
+                     lambda r0, n: arrow_pileup_pages(A, enc, r0, n, page_rows, device, read_spans=spans),
+                     table.num_rows, 0)
             finally:
                 A.close()
             stats["reads"] = table.num_rows
@@ -367,36 +539,51 @@ def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_
                 for sam, base in src:
                     hdr = header_info(sam)
                     n = sam.counts().n_reads
-                    emit(lambda r0, m: sam_pileups(sam, r0, m, hdr), n, base)
+                    emit(lambda r0, m: sam_pileups(sam, r0, m, hdr),
+                         lambda r0, m: sam_pileup_pages(sam, enc, r0, m, hdr, page_rows, device, read_spans=spans),
+                         n, base)
                     stats["reads"] = base + n
         if W.parts == 0:  # no pileups at all: one empty part file carries the schema
-            W.add(pileup_schema().empty_table())
+            if on_device:
+                W.add([], 0)
+            else:
+                W.add(pileup_schema().empty_table())
         ok = True
     finally:
+        if enc is not None:
+            enc.close()
         with ph("close"):
             W.close(ok)
     stats["parts"] = W.parts
     stats["phases"] = ph.t
+    if on_device:
+        stats["page_kernels_ms"] = enc.ms
+        stats["page_bytes_downloaded"] = enc.bytes_down
+        stats["file_bytes"] = W.file_bytes
     return stats
 
 
 def reads2ref(inp: str, out: str, aggregate: bool = False, min_mapq: int = 30, compression: str = "gzip",
               part_reads: int = DEFAULT_PART_READS, partition_bytes: Optional[int] = None, overwrite: bool = False,
-              device: int = 0) -> Dict[str, object]:
+              device: int = 0, parquet_encoder: str = "host", page_rows: Optional[int] = None) -> Dict[str, object]:
     """`adam reads2ref`: the reads of a SAM, BAM or ADAMRecord Parquet input
     as ADAMPileup Parquet part files under `out` (which appears only when the
     job succeeds; an existing one is refused unless overwrite, and then only
     an earlier part-file directory is replaced).  min_mapq is accepted and
     ignored, as the reference never reads its -mapq.  part_reads: reads per
     part file (:data:`DEFAULT_PART_READS`); partition_bytes: SAM text per
-    streamed partition (inputs.DEFAULT_PARTITION_BYTES).  Returns the
-    job's statistics."""
+    streamed partition (inputs.DEFAULT_PARTITION_BYTES).  parquet_encoder:
+    "host" (Arrow's writer over downloaded columns) or "device" (the data
+    pages built on the GPU, adam_amd/parquet_pages.py; page_rows rows per
+    page, a multiple of 64); both give files that read back as the same
+    table.  Returns the job's statistics."""
     if aggregate:
         raise ValueError("-aggregate is outside this build: PileupAggregator joins read names in Spark's shuffle "
                          "order, so the reference itself does not define its result")
     int(min_mapq)  # (checked to be a number, then unused: Reads2Ref.scala parses -mapq and never reads it)
     return _reads2ref(inp, out, compression, part_reads,
-                      DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes, overwrite, device)
+                      DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes, overwrite, device,
+                      parquet_encoder=parquet_encoder, page_rows=page_rows)
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -411,12 +598,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("-partition_bytes", type=int, default=DEFAULT_PARTITION_BYTES,
                     help="SAM text per streamed partition, in bytes")
     ap.add_argument("-overwrite", action="store_true")
+    ap.add_argument("-parquet_encoder", default="host", choices=("host", "device"),
+                    help="where the part files' data pages are encoded (device: adam_amd/parquet_pages.py)")
     a = ap.parse_args(argv)
     if a.aggregate:
         ap.error("-aggregate is outside this build (PileupAggregator's result depends on Spark's shuffle order)")
     t0 = time.perf_counter()
     st = reads2ref(a.input, a.output, False, a.mapq, a.parquet_compression, a.part_reads, a.partition_bytes,
-                   a.overwrite)
+                   a.overwrite, parquet_encoder=a.parquet_encoder)
     report(st, t0)
     return 0
 

@@ -787,6 +787,22 @@ bqsr_status bqsr_arrow_pileup_prepare(bqsr_context* ctx, bqsr_arrow* a, int64_t 
                                       const uint8_t* const* mapq_validity, int32_t n_chunks, void* stream,
                                       bqsr_pileup_sizes* out);
 bqsr_status bqsr_arrow_pileup_columns(bqsr_context* ctx, bqsr_arrow* a, const bqsr_pileup_host* dst, void* stream);
+/* The same emit pass with the columns LEFT ON THE DEVICE: *cols receives their
+ * device addresses (n_rows entries, bitmaps ceil(n_rows / 64) words; all NULL
+ * when the range has no rows) and nothing is copied to the host -- what
+ * bqsr_parquet_pages_* encodes from (reads2ref -parquet_encoder device).  The
+ * addresses hold until the next pileup call on the handle. */
+bqsr_status bqsr_sam_pileup_device_columns(bqsr_context* ctx, bqsr_sam* s, bqsr_pileup_host* cols, void* stream);
+bqsr_status bqsr_arrow_pileup_device_columns(bqsr_context* ctx, bqsr_arrow* a, bqsr_pileup_host* cols, void* stream);
+/* readStart and readEnd per READ of the last prepared range, n_reads entries
+ * each, into host memory: every row of read i carries read_start[i] and
+ * read_end[i], so the two columns can be written as a dictionary of one entry
+ * per read with the `read` column as the indices.  (A read without rows: end
+ * 0, start as the parse holds it.) */
+bqsr_status bqsr_sam_pileup_read_spans(bqsr_context* ctx, bqsr_sam* s, int64_t* read_start, int64_t* read_end,
+                                       void* stream);
+bqsr_status bqsr_arrow_pileup_read_spans(bqsr_context* ctx, bqsr_arrow* a, int64_t* read_start, int64_t* read_end,
+                                         void* stream);
 /* MEASUREMENT ONLY, not part of the stable interface: the device-event times
  * of the count and the emit kernel of the calling thread's last prepare /
  * columns call, in milliseconds (tools/bench_adam.py --reads2ref). */
@@ -1293,6 +1309,79 @@ bqsr_status bqsr_parquet_gzip(const uint8_t* in, int64_t in_len, const char* pat
  * libdeflate / zlib at `level` (tests). */
 bqsr_status bqsr_gzip_bytes(const uint8_t* in, int64_t n, int32_t huffman, int32_t level, uint8_t* out, int64_t cap,
                             int64_t* out_len);
+
+/* Parquet data page bodies built on the device (adam_amd/csrc/
+ * parquet_pages.hip): one column chunk at a time, from columns in DEVICE
+ * memory, cut into V1 data pages of page_rows rows (a multiple of 64; the
+ * last page may be short).  The caller adds page headers, dictionary pages,
+ * the codec and the footer (adam_amd/parquet_pages.py).  A column is
+ * described by a bqsr_parquet_column; row g of it is
+ *   null    when `validity` (an Arrow bitmap in u64 words) is given and bit g
+ *           is clear; else with i = gather ? gather[g] : g, when i is outside
+ *           [0, src_n); else with v = src[i] (src_width 1: uint8, 4: int32,
+ *           8: int64) and a `remap` table, when v is outside [0, remap_n) or
+ *           remap[v] < 0;
+ *   else    (remap ? remap[v] : v) - base.
+ * A page body is, in order:
+ *   definition levels (max level 1, RLE encoding): u32 LE length, then ONE
+ *     bit-packed run of the hybrid encoding -- varint(ceil(rows / 8) << 1 | 1)
+ *     and the page's ceil(rows / 8) bitmap bytes (bit set = value present,
+ *     padding bits clear);
+ *   BQSR_PARQUET_PLAIN_INT32 / _INT64: the page's non-null values in row
+ *     order, 4 / 8 bytes LE each;
+ *   BQSR_PARQUET_DICT_INDEX: one byte bit_width (w, 1..32), then the page's
+ *     non-null values (their low w bits) in row order under this BLOCK RULE:
+ *     the values are taken in blocks of 64; a full block whose 64 values are
+ *     equal is one RLE run, varint(64 << 1) = 80 01 and the value in
+ *     ceil(w / 8) bytes LE; any other block is one bit-packed run,
+ *     varint(groups << 1 | 1) with groups = ceil(values / 8), then groups * w
+ *     bytes, values LSB first, the last group zero-padded to 8 values.
+ *     Adjacent equal runs are not merged: the bytes are a pure function of
+ *     the column.
+ * size: the passes up to the chunk's exact size (nothing is allocated for the
+ * output before it is known); emit: the write pass and ONE copy of the bodies
+ * and one of the page table into host memory (bodies: body_bytes bytes, pages:
+ * n_pages entries; offsets are into `bodies`).  One emit per size call.
+ * minmax: the least and greatest non-null value and their count (min > max
+ * when there is none): a caller's dense-range dictionary [min, max] with base
+ * = min.  An encoder handle keeps its device scratch across calls and serves
+ * one thread at a time.  BQSR_ERR_INVALID_ARG: a kind, width or page_rows
+ * outside the above, remap or base on a PLAIN column, more than 2^31 - 1 rows. */
+enum { BQSR_PARQUET_PLAIN_INT32 = 0, BQSR_PARQUET_PLAIN_INT64 = 1, BQSR_PARQUET_DICT_INDEX = 2 };
+typedef struct bqsr_parquet_pages bqsr_parquet_pages;
+typedef struct bqsr_parquet_column {
+  int32_t kind;
+  int32_t src_width;
+  const void* src;
+  int64_t src_n; /* elements of src */
+  const int32_t* gather;
+  const int32_t* remap;
+  int32_t remap_n;
+  int32_t bit_width;
+  int64_t base;
+  const uint64_t* validity;
+} bqsr_parquet_column;
+typedef struct bqsr_parquet_page {
+  int64_t offset; /* of the body in the chunk's bodies */
+  int64_t bytes;
+  int64_t rows;
+  int64_t non_nulls;
+} bqsr_parquet_page;
+typedef struct bqsr_parquet_pages_sizes {
+  int64_t n_pages;
+  int64_t body_bytes;
+} bqsr_parquet_pages_sizes;
+bqsr_status bqsr_parquet_pages_create(bqsr_context* ctx, bqsr_parquet_pages** out);
+void bqsr_parquet_pages_destroy(bqsr_parquet_pages* enc);
+bqsr_status bqsr_parquet_pages_size(bqsr_parquet_pages* enc, const bqsr_parquet_column* col, int64_t n_rows,
+                                    int64_t page_rows, void* stream, bqsr_parquet_pages_sizes* out);
+bqsr_status bqsr_parquet_pages_emit(bqsr_parquet_pages* enc, uint8_t* bodies, bqsr_parquet_page* pages, void* stream);
+bqsr_status bqsr_parquet_pages_minmax(bqsr_parquet_pages* enc, const bqsr_parquet_column* col, int64_t n_rows,
+                                      void* stream, int64_t* min_out, int64_t* max_out, int64_t* non_nulls);
+/* MEASUREMENT ONLY: the device-event times of the calling thread's last size
+ * call (levels, compaction, item sizes and the two scans) and of the emit call
+ * after it, in milliseconds (tools/bench_adam.py --reads2ref). */
+bqsr_status bqsr_parquet_pages_kernel_times(double* size_ms, double* emit_ms);
 
 /* adam2sam: ADAMRecord Parquet out as SAM or BAM.  The records of an Arrow
  * table are rendered as SAM lines on the device (adam_lines.hip) and the text

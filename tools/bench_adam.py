@@ -20,6 +20,7 @@ best of --reps), Arrow's read, the upload-and-count call and the kernel alone
 --kernel-reads random reads on the device, as bytes/s.  One JSON line.
 
     python tools/bench_adam.py --reads2ref [--reads 2000000] [--part-reads N] [--compression snappy]
+    python tools/bench_adam.py --reads2ref --parquet-encoder [--reads 2000000]   (host next to device pages)
 
 --reads2ref measures `adam reads2ref` (adam_amd/reads2ref.py) over the same
 synthetic reads as SAM text: the job's steps run one after the other in the
@@ -603,6 +604,83 @@ def bench_reads2ref(a):
     print(json.dumps(res))
 
 
+def bench_reads2ref_pages(a):
+    """--reads2ref --parquet-encoder: `reads2ref` with the host's Parquet
+    encoder (Arrow's writer over downloaded columns: unchanged code, the
+    yardstick) and with -parquet_encoder device, in this process on the same
+    file; per codec (snappy, gzip) each leg runs once after a warm-up of its
+    own.  Per leg: wall seconds, the job's phases, the part files' bytes in
+    all and per column (from the footers); the device leg also the page
+    kernels' device-event times and the bytes it downloaded; and a third
+    leg: the device encoder runs with readStart / readEnd as the per-read
+    dictionary and as PLAIN int64 (reads2ref.READ_SPANS names the form kept
+    per codec; the ratios are the kept form's)."""
+    import pyarrow.parquet as pq
+    import torch
+    from adam_amd import reads2ref as R
+    t0 = time.perf_counter()
+    sam = synthetic_sam(a.reads, a.len)
+    log("generated %d bytes of SAM in %.1f s" % (len(sam), time.perf_counter() - t0))
+    torch.zeros(1, device="cuda")
+    work = a.dir or tempfile.mkdtemp(prefix="bench_reads2ref_pages_")
+    os.makedirs(work, exist_ok=True)
+    part_reads = a.part_reads if a.part_reads != 1 << 19 else R.DEFAULT_PART_READS
+    res = {"metric": "adam reads2ref SAM -> ADAMPileup Parquet, -parquet_encoder host next to device: wall seconds of "
+                     "one run after a warm-up, same process, same file",
+           "reads": a.reads, "read_len": a.len, "input_bytes": len(sam), "part_reads": part_reads, "codecs": {}}
+    try:
+        src = os.path.join(work, "in.sam")
+        with open(src, "wb") as fh:
+            fh.write(sam)
+        del sam
+
+        kept_forms = dict(R.READ_SPANS)
+
+        def leg(codec, encoder, spans="dictionary"):
+            R.READ_SPANS = dict.fromkeys(R.READ_SPANS, spans)  # (the device leg's form of readStart / readEnd)
+            out = os.path.join(work, "out_%s.adam" % encoder)
+            run = lambda: R._reads2ref(src, out, codec, part_reads, a.partition_bytes, True, 0,  # noqa: E731
+                                       parquet_encoder=encoder)
+            run()
+            t = time.perf_counter()
+            st = run()
+            dt = time.perf_counter() - t
+            parts = sorted(f for f in os.listdir(out) if f.startswith("part-r-"))
+            per_col = {}
+            for f in parts:
+                md = pq.ParquetFile(os.path.join(out, f)).metadata
+                for g in range(md.num_row_groups):  # (Arrow's writer cuts a part into row groups of 1M rows)
+                    rg = md.row_group(g)
+                    for i in range(rg.num_columns):
+                        c = rg.column(i)
+                        per_col[c.path_in_schema] = per_col.get(c.path_in_schema, 0) + c.total_compressed_size
+            r = {"seconds": dt, "rows": st["pileups"], "parts": st["parts"], "phases_s": st["phases"],
+                 "file_bytes": sum(os.path.getsize(os.path.join(out, f)) for f in parts),
+                 "column_bytes": per_col}
+            if encoder == "device":
+                r["page_kernels_ms"] = st["page_kernels_ms"]
+                r["bytes_downloaded"] = st["page_bytes_downloaded"]
+            else:  # the columns of every row and the four bitmaps
+                rows = st["pileups"]
+                r["bytes_downloaded"] = rows * (3 * 8 + 7 * 4 + 2) + 4 * ((rows + 63) // 64) * 8
+            log("%s %s: %.2f s, %d bytes" % (codec, encoder, dt, r["file_bytes"]))
+            shutil.rmtree(out, ignore_errors=True)
+            return r
+
+        for codec in ("snappy", "gzip"):
+            kept = kept_forms[codec]
+            h, d, p = leg(codec, "host"), leg(codec, "device", "dictionary"), leg(codec, "device", "plain")
+            k = d if kept == "dictionary" else p
+            res["codecs"][codec] = {"host": h, "device_dictionary_read_spans": d, "device_plain_read_spans": p,
+                                    "read_spans_kept": kept,
+                                    "device_over_host_seconds": k["seconds"] / h["seconds"],
+                                    "device_over_host_file_bytes": k["file_bytes"] / h["file_bytes"]}
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps(res))
+
+
 def _thin_to_one_reference(sam: bytes):
     """(text, kept): the sorted SAM text without the reads LocusPredicate would
     keep that overlap the read kept before them.  The generator draws every
@@ -1181,6 +1259,8 @@ def main():
                     help="measure transform SAM -> BAM next to SAM -> SAM text instead of the ADAM transform")
     ap.add_argument("--bam-level", type=int, default=6, help="--bam-out: the BGZF members' DEFLATE level")
     ap.add_argument("--reads2ref", action="store_true", help="measure adam reads2ref instead of the transform")
+    ap.add_argument("--parquet-encoder", action="store_true",
+                    help="--reads2ref: measure -parquet_encoder device next to the host encoder, snappy and gzip")
     ap.add_argument("--aggregate", action="store_true",
                     help="measure adam aggregate_pileups next to adam reads2ref instead of the transform")
     ap.add_argument("--mpileup", action="store_true",
@@ -1219,7 +1299,7 @@ def main():
     if a.realign_targets:
         return bench_realign_targets(a)
     if a.reads2ref:
-        return bench_reads2ref(a)
+        return bench_reads2ref_pages(a) if a.parquet_encoder else bench_reads2ref(a)
     if a.aggregate:
         return bench_aggregate(a)
     if a.bam_out:
