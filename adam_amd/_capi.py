@@ -46,7 +46,8 @@ EXPORTS = [
     "bqsr_pileup_kernel_times", "bqsr_sam_pileup_device_columns", "bqsr_arrow_pileup_device_columns",
     "bqsr_sam_pileup_read_spans", "bqsr_arrow_pileup_read_spans",
     "bqsr_parquet_pages_create", "bqsr_parquet_pages_destroy", "bqsr_parquet_pages_size", "bqsr_parquet_pages_emit",
-    "bqsr_parquet_pages_minmax",
+    "bqsr_parquet_pages_minmax", "bqsr_parquet_pages_size_strings", "bqsr_parquet_pages_size_bools",
+    "bqsr_sam_adam_device_columns",
     "bqsr_sam_mpileup_prepare", "bqsr_sam_mpileup_text", "bqsr_arrow_mpileup_prepare", "bqsr_arrow_mpileup_text",
     "bqsr_mpileup_kernel_times",
     "bqsr_sam_realign_targets_prepare", "bqsr_sam_realign_targets_fetch", "bqsr_arrow_realign_targets_prepare",

@@ -463,6 +463,26 @@ bqsr_status adam_code_fail(uint32_t code, int64_t read) {
   return fail(code == adamk::kAdamTagValue ? BQSR_ERR_SAM_PARSE : BQSR_ERR_UNSUPPORTED,
               "ADAM record of read " + std::to_string(read) + ": " + what, read);
 }
+// pass 2 over the prepared range: the string columns' offsets and bytes (the other columns are pass 1's)
+bqsr_status adam_write_pass(bqsr_context* ctx, const bqsr_sam* s, AdamBufs& A, hipStream_t st) {
+  const int64_t n = A.n;
+  adamk::AdamParams P{};
+  P.text = s->d_text;
+  P.line_span = s->line_span;
+  P.cig_off = s->cig_off;
+  P.cig = s->cig;
+  P.r0 = A.r0;
+  P.n = n;
+  P.sq = s->sq_tab;
+  P.rg = s->rg_tab;
+  P.off = A.off;
+  P.soff = A.soff;
+  for (int c = 0; c < adamk::kStr; ++c) P.sbytes[c] = A.sbytes[c];
+  P.W = A.W;
+  adam_quals(P, A, s);
+  if (n > 0) return launch(adamk::adam_write, sam_grid(n, 256, ctx->n_cu * 8), 256, st, P);
+  return launch(adamk::adam_empty_offsets, 1, 64, st, A.soff, n);
+}
 }  // namespace
 
 extern "C" {
@@ -598,25 +618,7 @@ bqsr_status bqsr_sam_adam_columns(bqsr_context* ctx, bqsr_sam* s, const bqsr_ada
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = S(stream);
   const int64_t n = A.n;
-  adamk::AdamParams P{};
-  P.text = s->d_text;
-  P.line_span = s->line_span;
-  P.cig_off = s->cig_off;
-  P.cig = s->cig;
-  P.r0 = A.r0;
-  P.n = n;
-  P.sq = s->sq_tab;
-  P.rg = s->rg_tab;
-  P.off = A.off;
-  P.soff = A.soff;
-  for (int c = 0; c < adamk::kStr; ++c) P.sbytes[c] = A.sbytes[c];
-  P.W = A.W;
-  adam_quals(P, A, s);
-  if (n > 0) {
-    JOB_TRY(launch(adamk::adam_write, sam_grid(n, 256, ctx->n_cu * 8), 256, st, P));
-  } else {
-    JOB_TRY(launch(adamk::adam_empty_offsets, 1, 64, st, A.soff, n));
-  }
+  JOB_TRY(adam_write_pass(ctx, s, A, st));
   const size_t N1 = (size_t)n + 1, WB = (size_t)A.W * 8;
   auto cp = [&](void* d, const void* src, size_t bytes) -> hipError_t {
     if (!d || !bytes) return hipSuccess;
@@ -635,6 +637,29 @@ bqsr_status bqsr_sam_adam_columns(bqsr_context* ctx, bqsr_sam* s, const bqsr_ada
   for (int c = 0; c < adamk::kBools && e == hipSuccess; ++c) e = cp(dst->bools[c], A.bools + c * (size_t)A.W, WB);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return fail(BQSR_ERR_DEVICE, std::string("bqsr_sam_adam_columns: ") + hipGetErrorString(e));
+  return ok();
+}
+
+bqsr_status bqsr_sam_adam_device_columns(bqsr_context* ctx, bqsr_sam* s, bqsr_adam_host* cols, void* stream) {
+  if (!ctx || !s || !cols) return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_adam_device_columns: bad arguments");
+  AdamBufs* Ap = (AdamBufs*)s->adam;
+  if (!Ap || !Ap->prepared)
+    return fail(BQSR_ERR_INVALID_ARG, "bqsr_sam_adam_device_columns before bqsr_sam_adam_prepare");
+  AdamBufs& A = *Ap;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = S(stream);
+  JOB_TRY(adam_write_pass(ctx, s, A, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const size_t n = (size_t)A.n, N1 = n + 1, W = (size_t)A.W;
+  for (int c = 0; c < adamk::kStr; ++c) {
+    cols->str_offsets[c] = A.soff + c * N1;
+    cols->str_bytes[c] = A.sbytes[c];
+    cols->str_valid[c] = A.svalid + c * W;
+  }
+  for (int c = 0; c < adamk::kI32; ++c) cols->i32[c] = A.i32 + c * n;
+  for (int c = 0; c < adamk::kI64; ++c) cols->i64[c] = A.i64 + c * n;
+  for (int c = 0; c < adamk::kI32 + adamk::kI64; ++c) cols->int_valid[c] = A.ivalid + c * W;
+  for (int c = 0; c < adamk::kBools; ++c) cols->bools[c] = A.bools + c * W;
   return ok();
 }
 

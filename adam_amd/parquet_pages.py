@@ -3,8 +3,10 @@
 The device (include/adam_sam.h ``bqsr_parquet_pages_*``, adam_amd/csrc/
 parquet_pages.hip) turns one column at a time, read from device memory, into
 V1 data page BODIES: definition levels as the validity bitmap in one
-bit-packed run, then either PLAIN int32 / int64 values or dictionary indices
-in the RLE / bit-packed hybrid under the header's block rule.  This module is
+bit-packed run, then PLAIN int32 / int64 values, dictionary indices in the
+RLE / bit-packed hybrid under the header's block rule, or (from the size
+calls adam_pages.py binds, for ``transform``) PLAIN BYTE_ARRAY / BOOLEAN
+values.  This module is
 the host's share: :class:`Encoder` drives those calls and brings a chunk's
 bodies and page table back in one copy each; :class:`PagesWriter` -- an
 :class:`adam_save.AdamWriter`, so with its part-file, ``.partial``,
@@ -25,9 +27,9 @@ and per column chunk, from the device's popcounts; min / max are left out (no
 reader of these files filters on them, and they would need a reduction per
 column and, for strings, a pass over the dictionary).
 
-Out of scope here: BYTE_ARRAY data pages (every string column is written
-through a dictionary), compressing pages on the device, and the writers of
-``transform`` and ``aggregate_pileups``.
+Out of scope here: a string dictionary built on the device (a dictionary
+page's entries come from the host), compressing pages on the device, and the
+writers of ``transform_parquet`` and ``aggregate_pileups``.
 """
 from __future__ import annotations
 
@@ -108,14 +110,20 @@ class Stream:
 
 class Column:
     """A column of a part file: its Arrow type name ("string", "int32",
-    "int64"), its stream, and for a dictionary column the PLAIN-encoded
-    dictionary page body with its entry count (None: PLAIN data pages)."""
+    "int64", "bool"), its stream, and for a dictionary column the
+    PLAIN-encoded dictionary page body with its entry count (None: PLAIN data
+    pages).  huffman: under gzip its data pages are literal-only Huffman
+    blocks (``bqsr_gzip_bytes(huffman=1)``: per-base strings, whose letter
+    frequencies are their redundancy), as adam_save.HUFFMAN_COLS are on the
+    host path."""
 
-    def __init__(self, name: str, kind: str, stream: Stream, dictionary: Optional[Tuple[object, int]] = None):
+    def __init__(self, name: str, kind: str, stream: Stream, dictionary: Optional[Tuple[object, int]] = None,
+                 huffman: bool = False):
         self.name = name
         self.kind = kind
         self.stream = stream
         self.dictionary = dictionary
+        self.huffman = bool(huffman)
 
 
 class Encoder:
@@ -260,7 +268,7 @@ class _Struct:
 
 
 # parquet.thrift's enums
-_TYPE = {"int32": 1, "int64": 2, "string": 6}  # INT32, INT64, BYTE_ARRAY
+_TYPE = {"bool": 0, "int32": 1, "int64": 2, "string": 6}  # BOOLEAN, INT32, INT64, BYTE_ARRAY
 _CODEC = {None: 0, "snappy": 1, "gzip": 2}
 _ENC_PLAIN, _ENC_PLAIN_DICTIONARY, _ENC_RLE = 0, 2, 3
 _DATA_PAGE, _DICTIONARY_PAGE = 0, 2
@@ -290,27 +298,28 @@ def _schema_elements(fields: Sequence[Tuple[str, str]]) -> List[bytes]:
     return out
 
 
-def gzip_bytes(buf: np.ndarray, level: int = 6) -> bytes:
-    """one gzip member of `buf` through the library (libdeflate / zlib at `level`)"""
+def gzip_bytes(buf: np.ndarray, level: int = 6, huffman: bool = False) -> bytes:
+    """one gzip member of `buf` through the library (libdeflate / zlib at
+    `level`; huffman: one literal-only Huffman block)"""
     L = _save_lib()
     n = ctypes.c_int64()
     cap = len(buf) + len(buf) // 8 + 64
     while True:
         out = np.empty(cap, np.uint8)
-        check(L.bqsr_gzip_bytes(buf.ctypes.data if len(buf) else None, len(buf), 0, level, out.ctypes.data, cap,
-                                ctypes.byref(n)))
+        check(L.bqsr_gzip_bytes(buf.ctypes.data if len(buf) else None, len(buf), int(huffman), level, out.ctypes.data,
+                                cap, ctypes.byref(n)))
         if n.value <= cap:
             return out[:n.value].tobytes()
         cap = n.value
 
 
-def compress(codec: Optional[str], buf) -> object:
-    """a page body under the codec (None: as it is)"""
+def compress(codec: Optional[str], buf, huffman: bool = False) -> object:
+    """a page body under the codec (None: as it is); huffman: see :class:`Column` (gzip only)"""
     if codec is None:
         return buf
     a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
     if codec == "gzip":
-        return gzip_bytes(np.ascontiguousarray(a))
+        return gzip_bytes(np.ascontiguousarray(a), huffman=huffman)
     import pyarrow as pa
     return pa.compress(pa.py_buffer(a), codec=codec, asbytes=True)
 
@@ -327,22 +336,22 @@ def assemble(path: str, fields: Sequence[Tuple[str, str]], columns: Sequence[Col
     assert [c.name for c in columns] == [n for n, _ in fields] or not columns
     run = (lambda f, *a: pool.submit(f, *a)) if pool else (lambda f, *a: _Done(f(*a)))
 
-    def pages_of(st: Stream, a: int, b: int):
-        return [compress(codec, st.bodies[o:o + nb]) for o, nb in st.pages[a:b, :2]]
+    def pages_of(st: Stream, a: int, b: int, huffman: bool):
+        return [compress(codec, st.bodies[o:o + nb], huffman) for o, nb in st.pages[a:b, :2]]
 
-    # every distinct stream once, cut into tasks of whole pages
-    jobs: Dict[int, list] = {}
+    # every distinct stream once (per form), cut into tasks of whole pages
+    jobs: Dict[Tuple[int, bool], list] = {}
     for c in columns:
         st = c.stream
-        if id(st) in jobs:
+        if (id(st), c.huffman) in jobs:
             continue
         tasks, a, acc = [], 0, 0
         for p in range(len(st.pages)):
             acc += int(st.pages[p, 1])
             if acc >= _TASK_BYTES or p + 1 == len(st.pages):
-                tasks.append(run(pages_of, st, a, p + 1))
+                tasks.append(run(pages_of, st, a, p + 1, c.huffman))
                 a, acc = p + 1, 0
-        jobs[id(st)] = tasks
+        jobs[(id(st), c.huffman)] = tasks
     dicts = [run(compress, codec, c.dictionary[0]) if c.dictionary else None for c in columns]
     with open(path, "wb") as fh:
         fh.write(b"PAR1")
@@ -362,7 +371,7 @@ def assemble(path: str, fields: Sequence[Tuple[str, str]], columns: Sequence[Col
                 pos += len(head) + len(comp)
                 raw_size += len(head) + len(body)
             data_off = pos
-            done = [x for t in jobs[id(c.stream)] for x in t.result()]
+            done = [x for t in jobs[(id(c.stream), c.huffman)] for x in t.result()]
             for (o, nb, rows, nn), comp in zip(c.stream.pages.tolist(), done):
                 head = _data_page_header(nb, len(comp), rows, nn, c.dictionary is not None)
                 fh.write(head)

@@ -4,6 +4,7 @@
     python -m adam_amd.transform INPUT.sam OUTPUT.sam [-mark_duplicate_reads]
         [-recalibrate_base_qualities] [-dbsnp_sites SITES.vcf]
     python -m adam_amd.transform INPUT.{adam,parquet,sam} OUTPUT.{adam,parquet} [...]
+    python -m adam_amd.transform INPUT.{sam,bam} OUTPUT.{adam,parquet} -parquet_encoder device [...]
     python -m adam_amd.transform INPUT.{sam,bam} OUTPUT.bam [-bam_compression_level N]
         [-bam_compressor {host,device}] [-bam_index] [...]
 
@@ -34,6 +35,15 @@ OUTPUT.adam / .parquet / a directory), or SAM text -- the input records with
 their QUAL fields replaced by the recalibrated strings (and FLAG 0x400 by
 MarkDuplicates' result).  -coalesce and -realignIndels are outside this
 build and are refused.
+
+-parquet_encoder device (SAM or BAM in, ADAM out; gzip, snappy or none): the
+part files' data pages are encoded on the device from the columns the ADAM
+passes leave there (adam_pages.py, parquet_pages.py), and only the encoded
+pages come down; the default, host, copies the columns down and has pyarrow
+encode them.  Both write the same records; the device encoder writes cigar
+PLAIN, the host encoder through a dictionary.  Refused before anything is
+read: SAM or BAM output, ADAM Parquet input (transform_parquet keeps its
+writer), zstd.
 
 -sort_reads (adamSortReadsByReferencePosition,
 core/rdd/AdamRDDFunctions.scala:63-93; the last step before the save,
@@ -608,23 +618,73 @@ class _BamOut:
                         os.remove(p)
 
 
-class _AdamOut:
-    """ADAM output (adamSave): part files of `part_reads` records each."""
+PARQUET_ENCODERS = ("host", "device")
 
-    def __init__(self, path: str, compression: str, part_reads: int, overwrite: bool = False):
-        from .adam_save import AdamWriter
-        self.w = AdamWriter(path, compression, overwrite=overwrite)
+
+def _encoder_refusal(inp: str, adam_out: bool, compression: str) -> Optional[str]:
+    """why -parquet_encoder device cannot serve this job (None: it can)"""
+    if not adam_out:
+        return "-parquet_encoder device applies to ADAM Parquet output only (not SAM or BAM)"
+    if is_parquet(inp):
+        return "-parquet_encoder device applies to SAM or BAM input (ADAM Parquet input keeps its own writer)"
+    if compression == "zstd":
+        return "-parquet_encoder device writes gzip, snappy or none (not zstd)"
+    return None
+
+
+class _AdamOut:
+    """ADAM output (adamSave): part files of `part_reads` records each.
+    encoder "device": the parts' data pages are built on the device
+    (adam_pages.part_columns) and put together by a parquet_pages.PagesWriter
+    -- the same part numbering, .partial / _SUCCESS / overwrite rules; page_rows
+    overrides the rows per page (tests)."""
+
+    def __init__(self, path: str, compression: str, part_reads: int, overwrite: bool = False,
+                 encoder: str = "host", page_rows: Optional[int] = None, device: int = 0):
+        from .adam_save import ADAM_FIELDS, AdamWriter
+        self.on_device = encoder == "device"
         self.part_reads = part_reads
+        self.page_rows = page_rows
+        self.device = device
+        self.enc = None  # the page encoder (made at the first emit: it needs the parse's context)
+        if self.on_device:
+            from .parquet_pages import PagesWriter
+            self.w = PagesWriter(path, ADAM_FIELDS, compression, overwrite=overwrite, max_pending=2)
+        else:
+            self.w = AdamWriter(path, compression, overwrite=overwrite)
 
     def emit(self, i, sam, quals=None):
         """the ADAM columns with the apply's quals (no text rewrite)"""
-        from .adam_save import set_quals
+        from .adam_save import header_info, set_quals
         if quals is not None:
             set_quals(sam, *quals)
-        self.w.emit(sam, self.part_reads)
+        if not self.on_device:
+            self.w.emit(sam, self.part_reads)
+            return
+        from . import adam_pages
+        from .parquet_pages import Encoder
+        if self.enc is None:
+            self.enc = Encoder(sam.ctx)
+        hdr = header_info(sam)
+        n = sam.counts().n_reads
+        for r0 in range(0, max(n, 1), max(1, self.part_reads)):  # (no reads: one part of the schema alone)
+            m = min(self.part_reads, n - r0) if n else 0
+            cols = adam_pages.part_columns(sam, self.enc, r0, m, hdr, self.w.compression, self.page_rows,
+                                           self.device) if m else []
+            self.w.add(cols, m)
 
     def close(self, ok: bool = True):
-        self.w.close(ok)
+        try:
+            self.w.close(ok)
+        finally:
+            if self.enc is not None:
+                self.enc.close()
+
+    def page_stats(self) -> Dict[str, object]:
+        """measured: the page kernels' device-event ms, the encoded bytes downloaded, the files' bytes"""
+        ms = dict(self.enc.ms) if self.enc is not None else {}
+        return {"kernel_ms": ms, "bytes_downloaded": self.enc.bytes_down if self.enc is not None else 0,
+                "file_bytes": self.w.file_bytes}
 
 
 def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bool = False,
@@ -632,7 +692,8 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
               compression: str = "gzip", part_reads: int = 1 << 19, overwrite: bool = False,
               sort_reads: bool = False, bam_level: Optional[int] = None,
               bam_piece_reads: int = BAM_PIECE_READS, bam_compressor: Optional[str] = None,
-              bam_index: bool = False) -> Dict[str, float]:
+              bam_index: bool = False, parquet_encoder: str = "host",
+              page_rows: Optional[int] = None) -> Dict[str, float]:
     """Transform.run (cli/Transform.scala:62-97) over SAM or BAM input: the
     records parsed on the device (a BAM's records become SAM lines there),
     MarkDuplicates, BQSR, then adamSave (OUT.adam / .parquet / a directory:
@@ -640,11 +701,23 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
     bam_level 0-9 (None: 6), records per encoded piece bam_piece_reads,
     bam_compressor "host" (None) or "device": the BGZF members deflated on
     the device, one level; bam_index: OUT.bam.bai beside it, built on the
-    device, see _BamOut) or SAM text.
+    device, see _BamOut) or SAM text.  parquet_encoder "device": the ADAM part
+    files' data pages encoded on the device (see the module doc and _AdamOut;
+    page_rows: rows per page, for tests).
     ADAM Parquet input goes through transform_parquet (Arrow reads it on the
     host).  sort_reads: the records sorted on the device before the save (see
     the module doc); the input must be one partition."""
+    from .adam_save import is_adam_output
     bam_out = out.endswith(".bam")
+    # ADAM output by name, or over an earlier adamSave directory (never just
+    # because `out` is some existing directory: the sinks refuse that)
+    adam_out = not bam_out and (out.endswith((".adam", ".parquet")) or is_adam_output(out))
+    if parquet_encoder not in PARQUET_ENCODERS:
+        raise ValueError("-parquet_encoder must be one of %s" % ", ".join(PARQUET_ENCODERS))
+    if parquet_encoder == "device":  # before anything is read or created
+        why = _encoder_refusal(inp, adam_out, compression)
+        if why:
+            raise ValueError(why)
     if bam_index and not bam_out:  # before anything is read
         raise ValueError(BAM_INDEX_REFUSAL)
     if bam_compressor is not None and not bam_out:  # before anything is read
@@ -663,12 +736,9 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
             if src.n_partitions > 1:
                 raise ValueError("-sort_reads needs the input in one partition; raise -partition_bytes")
     t0 = time.perf_counter()
-    # ADAM output by name, or over an earlier adamSave directory (never just
-    # because `out` is some existing directory: the sinks refuse that)
-    from .adam_save import is_adam_output
-    adam_out = not bam_out and (out.endswith((".adam", ".parquet")) or is_adam_output(out))
     sink = (_BamOut(out, bam_level, bam_piece_reads, overwrite, bam_compressor or "host", bam_index) if bam_out
-            else _AdamOut(out, compression, part_reads, overwrite) if adam_out else _SamOut(out, overwrite))
+            else _AdamOut(out, compression, part_reads, overwrite, parquet_encoder, page_rows, device) if adam_out
+            else _SamOut(out, overwrite))
     try:
         ctx = bqsr.Context.get(device)
     except BaseException:
@@ -723,6 +793,8 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
         stats.setdefault("phases", {})["close"] = time.perf_counter() - t1
     if adam_out:
         stats["parts"] = sink.w.parts
+        if ok and parquet_encoder == "device":
+            stats["pages"] = sink.page_stats()
     if bam_out:
         stats["bam"] = sink.stats
     stats["seconds"] = time.perf_counter() - t0
@@ -745,6 +817,9 @@ def main(argv=None) -> int:
     ap.add_argument("-parquet_compression", default="gzip", choices=("gzip", "snappy", "zstd", "none"),
                     help="ADAM output: the part files' codec (adamSave's default: GZIP)")
     ap.add_argument("-part_reads", type=int, default=1 << 19, help="ADAM output: records per part file")
+    ap.add_argument("-parquet_encoder", default="host", choices=PARQUET_ENCODERS,
+                    help="ADAM output from SAM or BAM input: where the part files' data pages are encoded (device: "
+                         "adam_amd/adam_pages.py; gzip, snappy or none)")
     ap.add_argument("-bam_compression_level", type=int, default=None, choices=range(10), metavar="N",
                     help="BAM output (OUTPUT.bam): the BGZF members' DEFLATE level, 0-9 (0: stored; default 6, "
                          "zlib's and samtools'); the host compressor's")
@@ -769,7 +844,7 @@ def main(argv=None) -> int:
     st = transform(a.input, a.output, a.mark_duplicate_reads, a.recalibrate_base_qualities, a.dbsnp_sites,
                    partition_bytes=a.partition_bytes, compression=a.parquet_compression, part_reads=a.part_reads,
                    overwrite=a.overwrite, sort_reads=a.sort_reads, bam_level=a.bam_compression_level,
-                   bam_compressor=a.bam_compressor, bam_index=a.bam_index)
+                   bam_compressor=a.bam_compressor, bam_index=a.bam_index, parquet_encoder=a.parquet_encoder)
     report(st, t0)
     return 0
 

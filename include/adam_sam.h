@@ -240,6 +240,11 @@ typedef struct bqsr_adam_host {
 bqsr_status bqsr_sam_adam_prepare(bqsr_context* ctx, bqsr_sam* s, int64_t r0, int64_t n, void* stream,
                                   bqsr_adam_sizes* out);
 bqsr_status bqsr_sam_adam_columns(bqsr_context* ctx, bqsr_sam* s, const bqsr_adam_host* dst, void* stream);
+/* The same pass 2, the columns left on the device: *cols their DEVICE
+ * addresses (nothing is copied), what bqsr_parquet_pages_size_strings / _bools
+ * / _size encode from (transform -parquet_encoder device).  The addresses hold
+ * until the next adam call on the parse. */
+bqsr_status bqsr_sam_adam_device_columns(bqsr_context* ctx, bqsr_sam* s, bqsr_adam_host* cols, void* stream);
 /* The ADAM columns' qual from an apply's outputs for batch `b` (built from
  * this parse in read order) instead of the text's QUAL, as
  * bqsr_sam_rewrite_quals would write them (pass-through reads keep theirs),
@@ -1338,6 +1343,20 @@ bqsr_status bqsr_gzip_bytes(const uint8_t* in, int64_t n, int32_t huffman, int32
  *     bytes, values LSB first, the last group zero-padded to 8 values.
  *     Adjacent equal runs are not merged: the bytes are a pure function of
  *     the column.
+ *   BQSR_PARQUET_PLAIN_BYTE_ARRAY (bqsr_parquet_pages_size_strings: an Arrow
+ *     string column -- int32 offsets [n_rows + 1], bytes, an optional validity
+ *     bitmap in u64 words): for every non-null row of the page, in row order,
+ *     a u32 LE length and the bytes offsets[r] .. offsets[r + 1].  A null row
+ *     gives nothing, whatever its offsets span.
+ *   BQSR_PARQUET_PLAIN_BOOLEAN (bqsr_parquet_pages_size_bools: an Arrow bitmap
+ *     of values in u64 words, bit r = row r, and an optional validity bitmap):
+ *     the page's non-null values one bit each, LSB first, in
+ *     ceil(non_nulls / 8) bytes, the last byte's padding bits clear.  Bits of
+ *     either bitmap beyond n_rows are not read into the output.
+ * The last two kinds have size calls of their own (no bqsr_parquet_column
+ * describes them); the emit call after any size call writes the kind that
+ * call left in the handle, and the column's buffers must stay as they are
+ * until then.
  * size: the passes up to the chunk's exact size (nothing is allocated for the
  * output before it is known); emit: the write pass and ONE copy of the bodies
  * and one of the page table into host memory (bodies: body_bytes bytes, pages:
@@ -1346,8 +1365,15 @@ bqsr_status bqsr_gzip_bytes(const uint8_t* in, int64_t n, int32_t huffman, int32
  * when there is none): a caller's dense-range dictionary [min, max] with base
  * = min.  An encoder handle keeps its device scratch across calls and serves
  * one thread at a time.  BQSR_ERR_INVALID_ARG: a kind, width or page_rows
- * outside the above, remap or base on a PLAIN column, more than 2^31 - 1 rows. */
-enum { BQSR_PARQUET_PLAIN_INT32 = 0, BQSR_PARQUET_PLAIN_INT64 = 1, BQSR_PARQUET_DICT_INDEX = 2 };
+ * outside the above, remap or base on a PLAIN column, more than 2^31 - 1 rows,
+ * a null source (offsets, bytes, bits) with rows, an emit without a size call. */
+enum {
+  BQSR_PARQUET_PLAIN_INT32 = 0,
+  BQSR_PARQUET_PLAIN_INT64 = 1,
+  BQSR_PARQUET_DICT_INDEX = 2,
+  BQSR_PARQUET_PLAIN_BYTE_ARRAY = 3,
+  BQSR_PARQUET_PLAIN_BOOLEAN = 4
+};
 typedef struct bqsr_parquet_pages bqsr_parquet_pages;
 typedef struct bqsr_parquet_column {
   int32_t kind;
@@ -1375,6 +1401,12 @@ bqsr_status bqsr_parquet_pages_create(bqsr_context* ctx, bqsr_parquet_pages** ou
 void bqsr_parquet_pages_destroy(bqsr_parquet_pages* enc);
 bqsr_status bqsr_parquet_pages_size(bqsr_parquet_pages* enc, const bqsr_parquet_column* col, int64_t n_rows,
                                     int64_t page_rows, void* stream, bqsr_parquet_pages_sizes* out);
+bqsr_status bqsr_parquet_pages_size_strings(bqsr_parquet_pages* enc, const int32_t* offsets, const uint8_t* bytes,
+                                            const uint64_t* validity, int64_t n_rows, int64_t page_rows, void* stream,
+                                            bqsr_parquet_pages_sizes* sizes);
+bqsr_status bqsr_parquet_pages_size_bools(bqsr_parquet_pages* enc, const uint64_t* bits, const uint64_t* validity,
+                                          int64_t n_rows, int64_t page_rows, void* stream,
+                                          bqsr_parquet_pages_sizes* sizes);
 bqsr_status bqsr_parquet_pages_emit(bqsr_parquet_pages* enc, uint8_t* bodies, bqsr_parquet_page* pages, void* stream);
 bqsr_status bqsr_parquet_pages_minmax(bqsr_parquet_pages* enc, const bqsr_parquet_column* col, int64_t n_rows,
                                       void* stream, int64_t* min_out, int64_t* max_out, int64_t* non_nulls);

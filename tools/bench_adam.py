@@ -681,6 +681,98 @@ def bench_reads2ref_pages(a):
     print(json.dumps(res))
 
 
+def bench_transform_pages(a):
+    """--parquet-encoder (without --reads2ref): `transform` to ADAM Parquet
+    with the host's Parquet encoder (pyarrow over downloaded columns: unchanged
+    code, the yardstick) and with -parquet_encoder device, in this process on
+    the same reads: SAM and BAM input, gzip and snappy.  Each leg is warmed
+    once and timed three times.  Per leg: the three wall times, their median
+    and spread, the emit and close phases of the median run, the part files'
+    bytes in all and per column (from the footers), the bytes downloaded; the
+    device leg also the page kernels' device-event times."""
+    import pyarrow.compute as pc
+    import pyarrow.parquet as pq
+    import torch
+    from adam_amd import adam_save, bqsr
+    from adam_amd import transform as T
+    from adam_amd.bam_writer import sam_to_bam_parallel
+    t0 = time.perf_counter()
+    sam = synthetic_sam(a.reads, a.len)
+    log("generated %d bytes of SAM in %.1f s" % (len(sam), time.perf_counter() - t0))
+    bam = sam_to_bam_parallel(sam, min(16, len(os.sched_getaffinity(0))),  # (forks: before the GPU is touched)
+                              progress=lambda i, n: log("bam slice %d / %d" % (i, n)) if i % 8 == 0 else None)
+    torch.zeros(1, device="cuda")
+    bqsr.Context.get(0).tune(bgzf=a.bgzf)
+    work = a.dir or tempfile.mkdtemp(prefix="bench_transform_pages_")
+    os.makedirs(work, exist_ok=True)
+    res = {"metric": "transform SAM / BAM -> ADAM Parquet, -parquet_encoder host next to device: wall seconds of three "
+                     "runs after a warm-up, same process, same reads",
+           "reads": a.reads, "read_len": a.len, "part_reads": a.part_reads, "markdup": not a.no_markdup,
+           "recalibrate": True, "legs": {}}
+    try:
+        src = {"sam": os.path.join(work, "in.sam"), "bam": os.path.join(work, "in.bam")}
+        with open(src["sam"], "wb") as fh:
+            fh.write(sam)
+        with open(src["bam"], "wb") as fh:
+            fh.write(bam)
+        res["input_bytes"] = {k: os.path.getsize(v) for k, v in src.items()}
+        del sam, bam
+
+        def leg(kind, codec, encoder):
+            out = os.path.join(work, "out_%s.adam" % encoder)
+            run = lambda: T.transform(src[kind], out, mark_duplicates=not a.no_markdup, recalibrate=True,  # noqa: E731
+                                      partition_bytes=a.partition_bytes, compression=codec, part_reads=a.part_reads,
+                                      overwrite=True, parquet_encoder=encoder)
+            run()
+            runs = []
+            for _ in range(3):
+                t = time.perf_counter()
+                st = run()
+                runs.append((time.perf_counter() - t, st))
+            runs.sort(key=lambda x: x[0])
+            secs = [x[0] for x in runs]
+            dt, st = runs[1]
+            if st["reads"] != a.reads:
+                raise SystemExit("transformed %d reads, expected %d" % (st["reads"], a.reads))
+            parts = sorted(f for f in os.listdir(out) if f.startswith("part-r-"))
+            per_col, raw_strings = {}, 0
+            for f in parts:
+                md = pq.ParquetFile(os.path.join(out, f)).metadata
+                for g in range(md.num_row_groups):
+                    rg = md.row_group(g)
+                    for i in range(rg.num_columns):
+                        c = rg.column(i)
+                        per_col[c.path_in_schema] = per_col.get(c.path_in_schema, 0) + c.total_compressed_size
+            r = {"seconds": secs, "median_s": dt, "spread_s": secs[-1] - secs[0], "parts": st["parts"],
+                 "phases_s": st["phases"], "emit_s": st["phases"].get("emit"), "close_s": st["phases"].get("close"),
+                 "file_bytes": sum(os.path.getsize(os.path.join(out, f)) for f in parts), "column_bytes": per_col}
+            if encoder == "device":
+                r["page_kernels_ms"] = st["pages"]["kernel_ms"]
+                r["bytes_downloaded"] = st["pages"]["bytes_downloaded"]
+            else:  # every column of every row: offsets, the strings' bytes, values and 23 bitmaps
+                for f in parts:
+                    t = pq.read_table(os.path.join(out, f), columns=list(adam_save.STR_COLS))
+                    raw_strings += sum(pc.sum(pc.binary_length(c)).as_py() or 0 for c in t.columns)
+                n, w = a.reads, (a.reads // 64 + 1) * 8
+                r["bytes_downloaded"] = 6 * 4 * (n + st["parts"]) + raw_strings + 4 * 4 * n + 2 * 8 * n + 23 * w
+            log("%s %s %s: %s s, %d bytes" % (kind, codec, encoder, ["%.2f" % x for x in secs], r["file_bytes"]))
+            shutil.rmtree(out, ignore_errors=True)
+            return r
+
+        for kind in ("sam", "bam"):
+            for codec in ("gzip", "snappy"):
+                h, d = leg(kind, codec, "host"), leg(kind, codec, "device")
+                res["legs"]["%s_%s" % (kind, codec)] = {
+                    "host": h, "device": d, "device_over_host_seconds": d["median_s"] / h["median_s"],
+                    "device_over_host_file_bytes": d["file_bytes"] / h["file_bytes"],
+                    "cigar_bytes_host_dictionary": h["column_bytes"].get("cigar"),
+                    "cigar_bytes_device_plain": d["column_bytes"].get("cigar")}
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps(res))
+
+
 def _thin_to_one_reference(sam: bytes):
     """(text, kept): the sorted SAM text without the reads LocusPredicate would
     keep that overlap the read kept before them.  The generator draws every
@@ -1260,7 +1352,8 @@ def main():
     ap.add_argument("--bam-level", type=int, default=6, help="--bam-out: the BGZF members' DEFLATE level")
     ap.add_argument("--reads2ref", action="store_true", help="measure adam reads2ref instead of the transform")
     ap.add_argument("--parquet-encoder", action="store_true",
-                    help="--reads2ref: measure -parquet_encoder device next to the host encoder, snappy and gzip")
+                    help="measure -parquet_encoder device next to the host encoder, snappy and gzip: of the transform "
+                         "(SAM and BAM input), or with --reads2ref of reads2ref")
     ap.add_argument("--aggregate", action="store_true",
                     help="measure adam aggregate_pileups next to adam reads2ref instead of the transform")
     ap.add_argument("--mpileup", action="store_true",
@@ -1304,6 +1397,8 @@ def main():
         return bench_aggregate(a)
     if a.bam_out:
         return bench_bam_index(a) if a.bam_index else bench_bam_out(a)
+    if a.parquet_encoder:
+        return bench_transform_pages(a)
     t0 = time.perf_counter()
     data = synthetic_sam(a.reads, a.len)
     if a.bam:
