@@ -47,6 +47,7 @@ EXPORTS = [
     "bqsr_sam_pileup_read_spans", "bqsr_arrow_pileup_read_spans",
     "bqsr_parquet_pages_create", "bqsr_parquet_pages_destroy", "bqsr_parquet_pages_size", "bqsr_parquet_pages_emit",
     "bqsr_parquet_pages_minmax", "bqsr_parquet_pages_size_strings", "bqsr_parquet_pages_size_bools",
+    "bqsr_snappy_pages", "bqsr_snappy_pages_host", "bqsr_parquet_pages_compress", "bqsr_parquet_pages_fetch",
     "bqsr_sam_adam_device_columns",
     "bqsr_sam_mpileup_prepare", "bqsr_sam_mpileup_text", "bqsr_arrow_mpileup_prepare", "bqsr_arrow_mpileup_text",
     "bqsr_mpileup_kernel_times",

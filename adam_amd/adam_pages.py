@@ -44,7 +44,7 @@ from . import _capi
 from . import parquet_pages as PP
 from ._capi import check, i64, vp
 from .adam_save import (ADAM_FIELDS, BOOL_COLS, HUFFMAN_COLS, I32_COLS, I64_COLS, RG_TAGS, STR_COLS, AdamHost,
-                        AdamSizes, HeaderInfo, _lib as _save_lib, _pinned)
+                        AdamSizes, HeaderInfo, _lib as _save_lib)
 
 PLAIN_BYTE_ARRAY, PLAIN_BOOLEAN = 3, 4
 # Rows per data page of the six string columns: 8192 reads of 100 bases are about 0.8 MB of sequence or qual, the
@@ -63,18 +63,6 @@ def _lib():
     return _capi.bind(_capi.lib(), _SIG)
 
 
-def _emit(enc: PP.Encoder, sz: PP.PagesSizes, stream=None) -> PP.Stream:
-    """the emit call after a size call of this module (what Encoder.encode does after its own)"""
-    bodies = _pinned(sz.body_bytes)[:sz.body_bytes]
-    pages = np.zeros((sz.n_pages, 4), np.int64)
-    check(_lib().bqsr_parquet_pages_emit(enc.h, bodies.ctypes.data if sz.body_bytes else None,
-                                         pages.ctypes.data if sz.n_pages else None, stream))
-    for k, v in zip(PP.KERNELS, PP.kernel_times()):
-        enc.ms[k] += v
-    enc.bytes_down += sz.body_bytes + pages.nbytes
-    return PP.Stream(bodies, pages)
-
-
 def encode_strings(enc: PP.Encoder, offsets, data, validity, n_rows: int, page_rows: int = STRING_PAGE_ROWS,
                    stream=None) -> PP.Stream:
     """An Arrow string column in device memory (addresses: int32 offsets
@@ -83,7 +71,7 @@ def encode_strings(enc: PP.Encoder, offsets, data, validity, n_rows: int, page_r
     sz = PP.PagesSizes()
     check(_lib().bqsr_parquet_pages_size_strings(enc.h, offsets, data, validity, n_rows, page_rows, stream,
                                                  ctypes.byref(sz)))
-    return _emit(enc, sz, stream)
+    return enc.emit(sz, stream)
 
 
 def encode_bools(enc: PP.Encoder, bits, validity, n_rows: int, page_rows: int = PP.DEFAULT_PAGE_ROWS,
@@ -92,7 +80,7 @@ def encode_bools(enc: PP.Encoder, bits, validity, n_rows: int, page_rows: int = 
     validity bitmap or None, u64 words) as PLAIN BOOLEAN pages."""
     sz = PP.PagesSizes()
     check(_lib().bqsr_parquet_pages_size_bools(enc.h, bits, validity, n_rows, page_rows, stream, ctypes.byref(sz)))
-    return _emit(enc, sz, stream)
+    return enc.emit(sz, stream)
 
 
 def header_columns(hdr: HeaderInfo):

@@ -100,8 +100,10 @@ inline void dfl_or(uint32_t* p, uint32_t v) { *p |= v; }
 #endif
 
 // S.scan[t] -> its exclusive prefix over the workgroup, S.scan_total the sum.
-// Called by every lane between phases (it holds its own barriers).
-__host__ __device__ inline void dfl_scan(Lds& S) {
+// Called by every lane between phases (it holds its own barriers).  (L: this
+// file's Lds or snappy_pages.hip's, which has the same scan fields.)
+template <class L>
+__host__ __device__ inline void dfl_scan(L& S) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const int t = (int)threadIdx.x, lane = t & 63, wv = t >> 6;
   const uint32_t v = S.scan[t];
@@ -133,7 +135,8 @@ __host__ __device__ inline void dfl_scan(Lds& S) {
 }
 
 // the 4 bytes at byte p of the staged member
-__host__ __device__ __forceinline__ uint32_t ld4(const Lds& S, int p) {
+template <class L>
+__host__ __device__ __forceinline__ uint32_t ld4(const L& S, int p) {
   const int i = p >> 2, s = (p & 3) * 8;
   const uint32_t a = S.in32[i];
   return s ? (a >> s) | (S.in32[i + 1] << (32 - s)) : a;
@@ -141,7 +144,8 @@ __host__ __device__ __forceinline__ uint32_t ld4(const Lds& S, int p) {
 __host__ __device__ __forceinline__ uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashBits); }
 __host__ __device__ __forceinline__ int ctz32(uint32_t x) { return __builtin_ctz(x); }  // x != 0
 // bytes in[p ..] and in[q ..] have in common, at most maxlen (<= 258), q < p
-__host__ __device__ __forceinline__ int extend(const Lds& S, int p, int q, int maxlen) {
+template <class L>
+__host__ __device__ __forceinline__ int extend(const L& S, int p, int q, int maxlen) {
   int l = 0;
   for (int it = 0; it < 65 && l < maxlen; ++it) {
     const uint32_t x = ld4(S, p + l) ^ ld4(S, q + l);

@@ -2475,6 +2475,7 @@ bqsr_status bqsr_job_tail_async(bqsr_context* ctx, bqsr_batch* b, const bqsr_sit
 #include "adam_lines.hip"
 #include "pileup.hip"
 #include "parquet_pages.hip"
+#include "snappy_pages.hip"
 #include "mpileup.hip"
 #include "realign_targets.hip"
 #include "pileup_agg.hip"

@@ -390,6 +390,12 @@ struct bqsr_parquet_pages {
   const int32_t* s_off = nullptr;
   const uint8_t* s_bytes = nullptr;
   StageClock<4> clock;
+  // of the last bqsr_parquet_pages_compress (snappy_pages.hip): the page table and the compressed pages' offsets
+  // on the host, until the fetch; the codec's device scratch
+  bool compressed = false;
+  std::vector<bqsr_parquet_page> h_pages;
+  std::vector<int64_t> comp_off;
+  std::shared_ptr<void> codec;
 };
 
 namespace {
@@ -433,7 +439,7 @@ bqsr_status pq_begin(bqsr_parquet_pages* enc, int64_t n_rows, int64_t page_rows,
   if (!enc || !out || page_rows <= 0 || page_rows % 64 || page_rows > (1 << 24))
     return fail(BQSR_ERR_INVALID_ARG, std::string(who) + ": bad arguments (page_rows is a multiple of 64)");
   if (n_rows < 0 || n_rows > (int64_t)INT32_MAX) return fail(BQSR_ERR_INVALID_ARG, std::string(who) + ": bad arguments");
-  enc->sized = false;
+  enc->sized = enc->compressed = false;
   g_pq_ms[PQ_SIZE] = g_pq_ms[PQ_EMIT] = 0.0;
   pqk::Geo& G = enc->G;
   G.n_rows = n_rows;
@@ -490,6 +496,28 @@ bqsr_status pq_size_bytes(bqsr_parquet_pages* enc, const PqScratch& B, const uin
                  (const uint64_t*)B.voff, bits, (void*)B.vals));
   JOB_TRY(launch(pqk::pq_items_bytes, pq_grid(enc->ctx, G.n_items), pqk::kThreads, s, G, (const uint64_t*)B.voff,
                  (const void*)B.vals, offsets, B.isz));
+  return BQSR_OK;
+}
+// the launch half of an emit (rows at all): the write pass into the handle's device buffers, between the emit
+// stage's marks.  The bodies are readable to their end rounded up to 4 (the codec reads aligned words).
+bqsr_status pq_emit_launch(bqsr_parquet_pages* enc, hipStream_t s, uint8_t** out_p, bqsr_parquet_page** ptab_p) {
+  const pqk::Geo& G = enc->G;
+  uint8_t* out;
+  bqsr_parquet_page* ptab;
+  JOB_TRY(dev_need(enc->out, &out, (size_t)enc->body_bytes + 64, kPqJob, "page bodies"));
+  JOB_TRY(dev_need(enc->ptab, &ptab, (size_t)G.n_pages, kPqJob, "page table"));
+  HIP_TRY(enc->clock.mark(PQ_EMIT_0, s));
+  if (G.kind == BQSR_PARQUET_PLAIN_BYTE_ARRAY || G.kind == BQSR_PARQUET_PLAIN_BOOLEAN) {
+    JOB_TRY(launch(pqk::pq_emit_bytes, pq_grid(enc->ctx, G.n_items), pqk::kThreads, s, G,
+                   (const uint64_t*)enc->vword.p, (const uint64_t*)enc->voff.p, (const void*)enc->vals.p, enc->s_off,
+                   enc->s_bytes, (const uint64_t*)enc->ioff.p, out, ptab));
+  } else {
+    JOB_TRY(launch(pqk::pq_emit, pq_grid(enc->ctx, G.n_items), pqk::kThreads, s, G, (const uint64_t*)enc->vword.p,
+                   (const uint64_t*)enc->voff.p, (const void*)enc->vals.p, (const uint64_t*)enc->ioff.p, out, ptab));
+  }
+  HIP_TRY(enc->clock.mark(PQ_EMIT_1, s));
+  *out_p = out;
+  *ptab_p = ptab;
   return BQSR_OK;
 }
 
@@ -576,18 +604,7 @@ bqsr_status bqsr_parquet_pages_emit(bqsr_parquet_pages* enc, uint8_t* bodies, bq
   hipStream_t s = S(stream);
   uint8_t* out;
   bqsr_parquet_page* ptab;
-  JOB_TRY(dev_need(enc->out, &out, (size_t)enc->body_bytes, kPqJob, "page bodies"));
-  JOB_TRY(dev_need(enc->ptab, &ptab, (size_t)G.n_pages, kPqJob, "page table"));
-  HIP_TRY(enc->clock.mark(PQ_EMIT_0, s));
-  if (G.kind == BQSR_PARQUET_PLAIN_BYTE_ARRAY || G.kind == BQSR_PARQUET_PLAIN_BOOLEAN) {
-    JOB_TRY(launch(pqk::pq_emit_bytes, pq_grid(enc->ctx, G.n_items), pqk::kThreads, s, G,
-                   (const uint64_t*)enc->vword.p, (const uint64_t*)enc->voff.p, (const void*)enc->vals.p, enc->s_off,
-                   enc->s_bytes, (const uint64_t*)enc->ioff.p, out, ptab));
-  } else {
-    JOB_TRY(launch(pqk::pq_emit, pq_grid(enc->ctx, G.n_items), pqk::kThreads, s, G, (const uint64_t*)enc->vword.p,
-                   (const uint64_t*)enc->voff.p, (const void*)enc->vals.p, (const uint64_t*)enc->ioff.p, out, ptab));
-  }
-  HIP_TRY(enc->clock.mark(PQ_EMIT_1, s));
+  JOB_TRY(pq_emit_launch(enc, s, &out, &ptab));
   HIP_TRY(hipMemcpyAsync(bodies, out, (size_t)enc->body_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(pages, ptab, (size_t)G.n_pages * sizeof(bqsr_parquet_page), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

@@ -15,6 +15,16 @@ headers, the codec (gzip through ``bqsr_gzip_bytes`` at level 6, snappy
 through ``pyarrow.compress``, or none) on the writer's thread pool, and the
 footer.
 
+``Encoder(ctx, compressor="device")`` (``-parquet_compressor device``, snappy
+only) compresses the data pages before they come down
+(``bqsr_parquet_pages_compress`` / ``_fetch``, adam_amd/csrc/snappy_pages.hip:
+every 64 KiB block of a page by one workgroup, in the raw snappy format
+include/adam_sam.h declares): a :class:`Stream` then carries the compressed
+pages and their offsets, the raw bodies never leave the device, and
+:func:`assemble` writes them as they are.  Dictionary pages stay with
+``pyarrow.compress``.  :func:`snappy_pages` and :func:`snappy_pages_host` are
+the codec alone, on the device and as the same routine compiled for the host.
+
 The files hold only what parquet-format 1.0 defines, so that parquet-mr of the
 reference's vintage reads them: V1 data pages, RLE levels, PLAIN and
 PLAIN_DICTIONARY.  (The Arrow writer of the host path declares
@@ -28,8 +38,9 @@ reader of these files filters on them, and they would need a reduction per
 column and, for strings, a pass over the dictionary).
 
 Out of scope here: a string dictionary built on the device (a dictionary
-page's entries come from the host), compressing pages on the device, and the
-writers of ``transform_parquet`` and ``aggregate_pileups``.
+page's entries come from the host), gzip pages and dictionary pages compressed
+on the device, and the writers of ``transform_parquet`` and
+``aggregate_pileups``.
 """
 from __future__ import annotations
 
@@ -72,6 +83,29 @@ class PagesSizes(ctypes.Structure):
 
 
 KERNELS = ("size", "emit")
+# the stages a device compressor adds to Encoder.ms
+CODEC_KERNELS = ("snappy", "pack")
+COMPRESSORS = ("host", "device")
+CODEC_SNAPPY = 1  # BQSR_PARQUET_CODEC_SNAPPY
+COMPRESSOR_CHOICE = "-parquet_compressor must be one of %s" % ", ".join(COMPRESSORS)
+COMPRESSOR_NEEDS_ENCODER = ("-parquet_compressor device compresses the pages -parquet_encoder device builds: it "
+                            "cannot be combined with -parquet_encoder host")
+COMPRESSOR_NEEDS_SNAPPY = ("-parquet_compressor device has one codec: it needs -parquet_compression snappy (gzip "
+                           "and none keep -parquet_compressor host)")
+
+
+def compressor_refusal(compressor: str, encoder: str, compression: Optional[str]) -> Optional[str]:
+    """why -parquet_compressor `compressor` cannot serve a job with this
+    -parquet_encoder and -parquet_compression (None: it can)"""
+    if compressor not in COMPRESSORS:
+        return COMPRESSOR_CHOICE
+    if compressor == "device" and encoder != "device":
+        return COMPRESSOR_NEEDS_ENCODER
+    if compressor == "device" and compression != "snappy":
+        return COMPRESSOR_NEEDS_SNAPPY
+    return None
+
+
 _SIG = {
     "bqsr_parquet_pages_create": (ctypes.c_int, [vp, ctypes.POINTER(vp)]),
     "bqsr_parquet_pages_destroy": (None, [vp]),
@@ -81,16 +115,69 @@ _SIG = {
     "bqsr_parquet_pages_minmax": (ctypes.c_int, [vp, ctypes.POINTER(ParquetColumn), i64, vp, i64p, i64p, i64p]),
     "bqsr_parquet_pages_kernel_times": (ctypes.c_int, [dblp, dblp]),
 }
+# the snappy codec (adam_amd/csrc/snappy_pages.hip)
+_CODEC_SIG = {
+    "bqsr_snappy_pages": (ctypes.c_int, [vp, vp, i64p, i64, vp, vp, i64, i64p]),
+    "bqsr_snappy_pages_host": (ctypes.c_int, [vp, i64p, i64, vp, i64, i64p]),
+    "bqsr_parquet_pages_compress": (ctypes.c_int, [vp, ctypes.c_int32, vp, i64p]),
+    "bqsr_parquet_pages_fetch": (ctypes.c_int, [vp, vp, vp, i64p, vp]),
+    "bqsr_parquet_pages_compress_times": (ctypes.c_int, [dblp, dblp]),
+}
 
 
 def _lib():
-    return _capi.bind(_capi.lib(), _SIG)
+    return _capi.bind(_capi.bind(_capi.lib(), _SIG), _CODEC_SIG)
 
 
 def kernel_times():
     """(size ms, emit ms) of this thread's last size / emit calls, by device
     events (measurement only)"""
     return tuple(_capi.stage_times(_lib().bqsr_parquet_pages_kernel_times, KERNELS).values())
+
+
+def compress_times():
+    """(snappy ms, pack ms) of this thread's last device compress call, by
+    device events (measurement only)"""
+    return tuple(_capi.stage_times(_lib().bqsr_parquet_pages_compress_times, CODEC_KERNELS).values())
+
+
+def _snappy_call(call, data, offsets):
+    """pages of `data` cut at `offsets` [n_pages + 1] through one of the two
+    codec entry points: (the packed pages as a uint8 array, int64 offsets
+    [n_pages + 1]); a first call with the usual bound, a second with the size
+    the first reports when that was short"""
+    a = np.ascontiguousarray(np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data)
+    off = np.ascontiguousarray(offsets, np.int64)
+    n_pages = len(off) - 1
+    if n_pages < 0:
+        raise ValueError("offsets has n_pages + 1 entries")
+    out_off = np.zeros(n_pages + 1, np.int64)
+    cap = int(off[-1] - off[0]) // 32 * 33 + 16 * n_pages + 64 if n_pages else 0
+    while True:
+        out = np.empty(cap, np.uint8)
+        rc = call(a.ctypes.data if len(a) else None, off.ctypes.data_as(i64p), n_pages,
+                  out.ctypes.data if cap else None, cap, out_off.ctypes.data_as(i64p))
+        if rc == _capi.INVALID_ARG and n_pages and int(out_off[-1]) > cap:
+            cap = int(out_off[-1])
+            continue
+        check(rc)
+        return out[:int(out_off[-1])], out_off
+
+
+def snappy_pages(data, offsets, ctx=None, stream=None):
+    """The pages data[offsets[i]:offsets[i + 1]] compressed on the device
+    (``bqsr_snappy_pages``): (packed uint8 array, int64 offsets [n_pages +
+    1]).  Every page is a raw snappy stream any snappy decoder reads."""
+    from . import bqsr
+    L, ctx = _lib(), ctx or bqsr.Context.get(0)
+    return _snappy_call(lambda a, off, n, out, cap, oo: L.bqsr_snappy_pages(ctx.handle, a, off, n, stream, out, cap, oo),
+                        data, offsets)
+
+
+def snappy_pages_host(data, offsets):
+    """:func:`snappy_pages` by the block routine compiled for the host
+    (``bqsr_snappy_pages_host``): the same bytes, no device"""
+    return _snappy_call(_lib().bqsr_snappy_pages_host, data, offsets)
 
 
 def bit_width(n_entries: int) -> int:
@@ -101,11 +188,19 @@ def bit_width(n_entries: int) -> int:
 class Stream:
     """One encoded column chunk: `bodies`, the concatenated page bodies (a
     uint8 array), and `pages`, int64 [n_pages, 4]: body offset, body bytes,
-    rows, non-nulls.  Columns whose index streams are equal share one."""
+    rows, non-nulls.  Columns whose index streams are equal share one.  From a
+    device compressor: `comp`, the pages already under `codec`, page i being
+    comp[comp_off[i]:comp_off[i + 1]]; `bodies` is None then (the raw bytes
+    stayed on the device) and `pages` still holds the RAW sizes."""
 
-    def __init__(self, bodies: np.ndarray, pages: np.ndarray):
+    def __init__(self, bodies: Optional[np.ndarray], pages: np.ndarray, comp: Optional[np.ndarray] = None,
+                 comp_off: Optional[np.ndarray] = None, codec: Optional[str] = None):
         self.bodies = bodies
         self.pages = np.asarray(pages, np.int64).reshape(-1, 4)
+        self.comp = comp
+        self.comp_off = None if comp is None else np.asarray(comp_off, np.int64)
+        self.codec = codec if comp is not None else None
+        assert comp is None or len(self.comp_off) == len(self.pages) + 1
 
 
 class Column:
@@ -129,13 +224,18 @@ class Column:
 class Encoder:
     """The device encoder of one context: `encode` a column chunk into a
     :class:`Stream`, `minmax` for a dense-range dictionary.  Sums the kernels'
-    device-event times (`ms`) and the bytes downloaded (`bytes_down`)."""
+    device-event times (`ms`) and the bytes downloaded (`bytes_down`).
+    compressor "device": the streams come down snappy-compressed (see
+    :class:`Stream`), and `ms` has the codec's two stages too."""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, compressor: str = "host"):
+        if compressor not in COMPRESSORS:
+            raise ValueError("compressor must be one of %s" % ", ".join(COMPRESSORS))
         self.ctx = ctx
+        self.compressor = compressor
         self.h = vp()
         check(_lib().bqsr_parquet_pages_create(ctx.handle, ctypes.byref(self.h)))
-        self.ms = dict.fromkeys(KERNELS, 0.0)
+        self.ms = dict.fromkeys(KERNELS + (CODEC_KERNELS if compressor == "device" else ()), 0.0)
         self.bytes_down = 0
 
     def close(self):
@@ -153,14 +253,37 @@ class Encoder:
         L = _lib()
         sz = PagesSizes()
         check(L.bqsr_parquet_pages_size(self.h, ctypes.byref(col), n_rows, page_rows, stream, ctypes.byref(sz)))
-        bodies = _pinned(sz.body_bytes)[:sz.body_bytes]
+        return self.emit(sz, stream)
+
+    def emit(self, sz: PagesSizes, stream=None) -> Stream:
+        """the emit call after a size call -- or, with the device compressor,
+        compress and fetch -- and its share of `ms` and `bytes_down`"""
+        L = _lib()
         pages = np.zeros((sz.n_pages, 4), np.int64)
-        check(L.bqsr_parquet_pages_emit(self.h, bodies.ctypes.data if sz.body_bytes else None,
-                                        pages.ctypes.data if sz.n_pages else None, stream))
+        if self.compressor == "device":
+            n = ctypes.c_int64()
+            check(L.bqsr_parquet_pages_compress(self.h, CODEC_SNAPPY, stream, ctypes.byref(n)))
+            comp = _pinned(n.value)[:n.value]
+            comp_off = np.zeros(sz.n_pages + 1, np.int64)
+            check(L.bqsr_parquet_pages_fetch(self.h, comp.ctypes.data if n.value else None,
+                                             pages.ctypes.data if sz.n_pages else None,
+                                             comp_off.ctypes.data_as(i64p), stream))
+            for k, v in zip(CODEC_KERNELS, compress_times()):
+                self.ms[k] += v
+            st = Stream(None, pages, comp, comp_off, "snappy")
+            # what came down: the packed pages, the page table, and the offsets of the size table's items (a
+            # page's varint and each of its 64 KiB blocks), from which the library cuts comp_off
+            items = sz.n_pages + int(((pages[:, 1] + 65535) // 65536).sum())
+            self.bytes_down += n.value + pages.nbytes + 8 * (items + 1) if sz.n_pages else 0
+        else:
+            bodies = _pinned(sz.body_bytes)[:sz.body_bytes]
+            check(L.bqsr_parquet_pages_emit(self.h, bodies.ctypes.data if sz.body_bytes else None,
+                                            pages.ctypes.data if sz.n_pages else None, stream))
+            st = Stream(bodies, pages)
+            self.bytes_down += sz.body_bytes + pages.nbytes
         for k, v in zip(KERNELS, kernel_times()):
             self.ms[k] += v
-        self.bytes_down += sz.body_bytes + pages.nbytes
-        return Stream(bodies, pages)
+        return st
 
     def minmax(self, col: ParquetColumn, n_rows: int, stream=None) -> Tuple[int, int, int]:
         """(min, max, non-null count) of the column's values (min > max: none)"""
@@ -337,6 +460,10 @@ def assemble(path: str, fields: Sequence[Tuple[str, str]], columns: Sequence[Col
     run = (lambda f, *a: pool.submit(f, *a)) if pool else (lambda f, *a: _Done(f(*a)))
 
     def pages_of(st: Stream, a: int, b: int, huffman: bool):
+        if st.comp is not None:  # compressed on the device: as they are
+            if st.codec != codec:
+                raise ValueError("a stream compressed as %s in a file of codec %s" % (st.codec, codec))
+            return [st.comp[st.comp_off[p]:st.comp_off[p + 1]] for p in range(a, b)]
         return [compress(codec, st.bodies[o:o + nb], huffman) for o, nb in st.pages[a:b, :2]]
 
     # every distinct stream once (per form), cut into tasks of whole pages

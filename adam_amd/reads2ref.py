@@ -33,12 +33,16 @@ What is kept from the reference, quirks included:
 
     python -m adam_amd.reads2ref INPUT.{sam,bam,adam} OUTPUT.adam [-mapq N] [-aggregate]
         [-parquet_compression gzip|snappy|none] [-part_reads N] [-partition_bytes N] [-overwrite]
-        [-parquet_encoder host|device]
+        [-parquet_encoder host|device] [-parquet_compressor host|device]
 
 ``-parquet_encoder device`` builds the part files' data pages on the GPU from
 the columns the emit pass leaves there (adam_amd/parquet_pages.py): only the
 encoded pages are downloaded; the host adds page headers, dictionary pages,
 the codec and the footer.  The default, ``host``, is Arrow's writer.
+``-parquet_compressor device`` (only with ``-parquet_encoder device
+-parquet_compression snappy``; refused otherwise before anything is read or
+created) compresses those data pages on the GPU too
+(adam_amd/csrc/snappy_pages.hip): the raw bodies are not downloaded.
 """
 from __future__ import annotations
 
@@ -55,6 +59,7 @@ from ._capi import check, dblp, i32, i64, vp
 from .adam_save import (BASES, PILEUP_DICT_COLS, PILEUP_FIELDS, PILEUP_STATS_COLS, RG_TAGS, AdamHost, AdamSizes,
                         AdamWriter, HeaderInfo, _pinned, check_out, header_info, pileup_schema)
 from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
+from .parquet_pages import COMPRESSORS, compressor_refusal
 
 # Reads per part file.  A read gives about as many rows as it has bases and a
 # row takes 54 bytes of device columns and as many of pinned host memory
@@ -477,9 +482,12 @@ def locus_filter(table):
 
 def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_bytes: int, overwrite: bool,
                device: int, writer_args: Optional[dict] = None, parquet_encoder: str = "host",
-               page_rows: Optional[int] = None) -> Dict[str, object]:
+               page_rows: Optional[int] = None, parquet_compressor: str = "host") -> Dict[str, object]:
     if parquet_encoder not in ("host", "device"):
         raise ValueError("parquet_encoder is 'host' or 'device'")
+    why = compressor_refusal(parquet_compressor, parquet_encoder, compression)  # before anything is read or created
+    if why:
+        raise ValueError(why)
     on_device = parquet_encoder == "device"
     check_out(out, overwrite, True)
     ctx = bqsr.Context.get(device)
@@ -498,7 +506,7 @@ def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_
     ok = False
     try:
         if on_device:
-            enc = PP.Encoder(ctx)
+            enc = PP.Encoder(ctx, parquet_compressor)
 
         def emit(make_table, make_pages, n, base):
             for r0 in range(0, n, part_reads):
@@ -565,7 +573,8 @@ def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_
 
 def reads2ref(inp: str, out: str, aggregate: bool = False, min_mapq: int = 30, compression: str = "gzip",
               part_reads: int = DEFAULT_PART_READS, partition_bytes: Optional[int] = None, overwrite: bool = False,
-              device: int = 0, parquet_encoder: str = "host", page_rows: Optional[int] = None) -> Dict[str, object]:
+              device: int = 0, parquet_encoder: str = "host", page_rows: Optional[int] = None,
+              parquet_compressor: str = "host") -> Dict[str, object]:
     """`adam reads2ref`: the reads of a SAM, BAM or ADAMRecord Parquet input
     as ADAMPileup Parquet part files under `out` (which appears only when the
     job succeeds; an existing one is refused unless overwrite, and then only
@@ -576,14 +585,17 @@ def reads2ref(inp: str, out: str, aggregate: bool = False, min_mapq: int = 30, c
     "host" (Arrow's writer over downloaded columns) or "device" (the data
     pages built on the GPU, adam_amd/parquet_pages.py; page_rows rows per
     page, a multiple of 64); both give files that read back as the same
-    table.  Returns the job's statistics."""
+    table.  parquet_compressor "device": the data pages are snappy-compressed
+    on the GPU before they come down (only with parquet_encoder "device" and
+    compression "snappy"; a ValueError otherwise, before anything is read or
+    created).  Returns the job's statistics."""
     if aggregate:
         raise ValueError("-aggregate is outside this build: PileupAggregator joins read names in Spark's shuffle "
                          "order, so the reference itself does not define its result")
     int(min_mapq)  # (checked to be a number, then unused: Reads2Ref.scala parses -mapq and never reads it)
     return _reads2ref(inp, out, compression, part_reads,
                       DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes, overwrite, device,
-                      parquet_encoder=parquet_encoder, page_rows=page_rows)
+                      parquet_encoder=parquet_encoder, page_rows=page_rows, parquet_compressor=parquet_compressor)
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -600,12 +612,17 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("-overwrite", action="store_true")
     ap.add_argument("-parquet_encoder", default="host", choices=("host", "device"),
                     help="where the part files' data pages are encoded (device: adam_amd/parquet_pages.py)")
+    ap.add_argument("-parquet_compressor", default="host", choices=COMPRESSORS,
+                    help="where the data pages are compressed (device: snappy only, with -parquet_encoder device)")
     a = ap.parse_args(argv)
     if a.aggregate:
         ap.error("-aggregate is outside this build (PileupAggregator's result depends on Spark's shuffle order)")
+    why = compressor_refusal(a.parquet_compressor, a.parquet_encoder, a.parquet_compression)
+    if why:
+        ap.error(why)
     t0 = time.perf_counter()
     st = reads2ref(a.input, a.output, False, a.mapq, a.parquet_compression, a.part_reads, a.partition_bytes,
-                   a.overwrite, parquet_encoder=a.parquet_encoder)
+                   a.overwrite, parquet_encoder=a.parquet_encoder, parquet_compressor=a.parquet_compressor)
     report(st, t0)
     return 0
 

@@ -7,6 +7,8 @@
     python -m adam_amd.transform INPUT.{sam,bam} OUTPUT.{adam,parquet} -parquet_encoder device [...]
     python -m adam_amd.transform INPUT.{sam,bam} OUTPUT.bam [-bam_compression_level N]
         [-bam_compressor {host,device}] [-bam_index] [...]
+    python -m adam_amd.transform INPUT.{sam,bam} OUTPUT.adam -parquet_encoder device -parquet_compression snappy
+        -parquet_compressor device [...]
 
 SAM or BAM in goes through the device path described below, out as SAM text,
 as BAM (an output name ending in .bam: the records encoded on the device,
@@ -43,7 +45,10 @@ pages come down; the default, host, copies the columns down and has pyarrow
 encode them.  Both write the same records; the device encoder writes cigar
 PLAIN, the host encoder through a dictionary.  Refused before anything is
 read: SAM or BAM output, ADAM Parquet input (transform_parquet keeps its
-writer), zstd.
+writer), zstd.  -parquet_compressor device (only with -parquet_encoder device
+-parquet_compression snappy; refused otherwise before anything is read or
+created) compresses those data pages on the device too
+(adam_amd/csrc/snappy_pages.hip) and only the compressed pages come down.
 
 -sort_reads (adamSortReadsByReferencePosition,
 core/rdd/AdamRDDFunctions.scala:63-93; the last step before the save,
@@ -93,6 +98,7 @@ from ._capi import check
 from .adam_save import check_out as _check_out
 from .inputs import DEFAULT_PARTITION_BYTES, SamInput, is_bam, is_parquet, report, sam_partitions  # noqa: F401
 from .inputs import Phases as _Phases, host_bytes as _host_bytes  # noqa: F401
+from .parquet_pages import COMPRESSORS as PARQUET_COMPRESSORS, compressor_refusal
 from .sam import SamText
 
 def _bqsr_partitions(data, header: bytes, ranges: List[Tuple[int, int]], snp, ctx, device: int, emit,
@@ -637,12 +643,14 @@ class _AdamOut:
     encoder "device": the parts' data pages are built on the device
     (adam_pages.part_columns) and put together by a parquet_pages.PagesWriter
     -- the same part numbering, .partial / _SUCCESS / overwrite rules; page_rows
-    overrides the rows per page (tests)."""
+    overrides the rows per page (tests).  compressor "device": the encoder
+    compresses the data pages (snappy) before they come down."""
 
     def __init__(self, path: str, compression: str, part_reads: int, overwrite: bool = False,
-                 encoder: str = "host", page_rows: Optional[int] = None, device: int = 0):
+                 encoder: str = "host", page_rows: Optional[int] = None, device: int = 0, compressor: str = "host"):
         from .adam_save import ADAM_FIELDS, AdamWriter
         self.on_device = encoder == "device"
+        self.compressor = compressor
         self.part_reads = part_reads
         self.page_rows = page_rows
         self.device = device
@@ -664,7 +672,7 @@ class _AdamOut:
         from . import adam_pages
         from .parquet_pages import Encoder
         if self.enc is None:
-            self.enc = Encoder(sam.ctx)
+            self.enc = Encoder(sam.ctx, self.compressor)
         hdr = header_info(sam)
         n = sam.counts().n_reads
         for r0 in range(0, max(n, 1), max(1, self.part_reads)):  # (no reads: one part of the schema alone)
@@ -693,7 +701,7 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
               sort_reads: bool = False, bam_level: Optional[int] = None,
               bam_piece_reads: int = BAM_PIECE_READS, bam_compressor: Optional[str] = None,
               bam_index: bool = False, parquet_encoder: str = "host",
-              page_rows: Optional[int] = None) -> Dict[str, float]:
+              page_rows: Optional[int] = None, parquet_compressor: str = "host") -> Dict[str, float]:
     """Transform.run (cli/Transform.scala:62-97) over SAM or BAM input: the
     records parsed on the device (a BAM's records become SAM lines there),
     MarkDuplicates, BQSR, then adamSave (OUT.adam / .parquet / a directory:
@@ -703,7 +711,9 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
     the device, one level; bam_index: OUT.bam.bai beside it, built on the
     device, see _BamOut) or SAM text.  parquet_encoder "device": the ADAM part
     files' data pages encoded on the device (see the module doc and _AdamOut;
-    page_rows: rows per page, for tests).
+    page_rows: rows per page, for tests); parquet_compressor "device": those
+    pages snappy-compressed on the device too (only with parquet_encoder
+    "device" and compression "snappy").
     ADAM Parquet input goes through transform_parquet (Arrow reads it on the
     host).  sort_reads: the records sorted on the device before the save (see
     the module doc); the input must be one partition."""
@@ -718,6 +728,9 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
         why = _encoder_refusal(inp, adam_out, compression)
         if why:
             raise ValueError(why)
+    why = compressor_refusal(parquet_compressor, parquet_encoder, compression)  # before anything is read or created
+    if why:
+        raise ValueError(why)
     if bam_index and not bam_out:  # before anything is read
         raise ValueError(BAM_INDEX_REFUSAL)
     if bam_compressor is not None and not bam_out:  # before anything is read
@@ -737,7 +750,8 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
                 raise ValueError("-sort_reads needs the input in one partition; raise -partition_bytes")
     t0 = time.perf_counter()
     sink = (_BamOut(out, bam_level, bam_piece_reads, overwrite, bam_compressor or "host", bam_index) if bam_out
-            else _AdamOut(out, compression, part_reads, overwrite, parquet_encoder, page_rows, device) if adam_out
+            else _AdamOut(out, compression, part_reads, overwrite, parquet_encoder, page_rows, device,
+                          parquet_compressor) if adam_out
             else _SamOut(out, overwrite))
     try:
         ctx = bqsr.Context.get(device)
@@ -820,6 +834,9 @@ def main(argv=None) -> int:
     ap.add_argument("-parquet_encoder", default="host", choices=PARQUET_ENCODERS,
                     help="ADAM output from SAM or BAM input: where the part files' data pages are encoded (device: "
                          "adam_amd/adam_pages.py; gzip, snappy or none)")
+    ap.add_argument("-parquet_compressor", default="host", choices=PARQUET_COMPRESSORS,
+                    help="with -parquet_encoder device and -parquet_compression snappy: where the data pages are "
+                         "compressed (device: adam_amd/csrc/snappy_pages.hip)")
     ap.add_argument("-bam_compression_level", type=int, default=None, choices=range(10), metavar="N",
                     help="BAM output (OUTPUT.bam): the BGZF members' DEFLATE level, 0-9 (0: stored; default 6, "
                          "zlib's and samtools'); the host compressor's")
@@ -840,11 +857,15 @@ def main(argv=None) -> int:
         ap.error(DEVICE_LEVEL_REFUSAL)
     if a.bam_index and not a.output.endswith(".bam"):
         ap.error(BAM_INDEX_REFUSAL)
+    why = compressor_refusal(a.parquet_compressor, a.parquet_encoder, a.parquet_compression)
+    if why:
+        ap.error(why)
     t0 = time.perf_counter()
     st = transform(a.input, a.output, a.mark_duplicate_reads, a.recalibrate_base_qualities, a.dbsnp_sites,
                    partition_bytes=a.partition_bytes, compression=a.parquet_compression, part_reads=a.part_reads,
                    overwrite=a.overwrite, sort_reads=a.sort_reads, bam_level=a.bam_compression_level,
-                   bam_compressor=a.bam_compressor, bam_index=a.bam_index, parquet_encoder=a.parquet_encoder)
+                   bam_compressor=a.bam_compressor, bam_index=a.bam_index, parquet_encoder=a.parquet_encoder,
+                   parquet_compressor=a.parquet_compressor)
     report(st, t0)
     return 0
 

@@ -1415,6 +1415,58 @@ bqsr_status bqsr_parquet_pages_minmax(bqsr_parquet_pages* enc, const bqsr_parque
  * after it, in milliseconds (tools/bench_adam.py --reads2ref). */
 bqsr_status bqsr_parquet_pages_kernel_times(double* size_ms, double* emit_ms);
 
+/* Page bodies compressed with snappy on the device (adam_amd/csrc/
+ * snappy_pages.hip).  `in` (host memory) holds n_pages pages laid end to end:
+ * page i is in[page_off[i], page_off[i + 1]) (any byte offsets, not
+ * decreasing; a page is below 2^31 bytes).  The bytes are uploaded, every page
+ * compressed, the pages packed on the device and only the packed bytes come
+ * back: page i is out[out_off[i], out_off[i + 1]).  out_off[n_pages] is the
+ * total, also when it exceeds cap (BQSR_ERR_INVALID_ARG then, nothing
+ * written); 32 + n + n / 6 bytes per page of n bytes always suffice.
+ * THE FORMAT (raw snappy, a pure function of the page's bytes: no level, no
+ * dependence on timing).  A compressed page is varint(n) followed by the
+ * elements of its ceil(n / 65536) blocks in order (the last block may be
+ * short; n == 0 gives the single byte 00).  Every block is compressed on its
+ * own, and within a block:
+ *   - no copy reaches before the block's first byte;
+ *   - a copy has length 4..64 and offset 1..65535;
+ *   - a copy is written in the 1-byte-offset form (tag 01) when its length is
+ *     4..11 and its offset is below 2048, otherwise in the 2-byte-offset form
+ *     (tag 10); the 4-byte-offset form never appears;
+ *   - the positions the parse leaves as literals are merged into maximal runs
+ *     within the block, each run one literal element: the length inline for
+ *     runs up to 60, in one extra byte up to 256, in two up to 65536.
+ * The parse is greedy over three match candidates per position (distance 1,
+ * the first position of the position's hash bucket in its chunk of 2048, the
+ * bucket's highest position of the earlier chunks), the longest winning, the
+ * nearer one on a tie; a match is extended to at most 64 bytes. */
+bqsr_status bqsr_snappy_pages(bqsr_context* ctx, const uint8_t* in, const int64_t* page_off, int64_t n_pages,
+                              void* stream, uint8_t* out, int64_t cap, int64_t* out_off);
+/* The same block routine compiled for the host, a lane at a time: the bytes
+ * bqsr_snappy_pages gives, without a context, a stream or a device call.  For
+ * tests on a machine without a GPU; far slower than a host snappy. */
+bqsr_status bqsr_snappy_pages_host(const uint8_t* in, const int64_t* page_off, int64_t n_pages, uint8_t* out,
+                                   int64_t cap, int64_t* out_off);
+/* The encoder's pages compressed before they come down.  compress: in place
+ * of bqsr_parquet_pages_emit after a size call -- the write pass, the bodies
+ * kept on the device, every page compressed as bqsr_snappy_pages does it, the
+ * packed size into *comp_bytes.  codec: BQSR_PARQUET_CODEC_SNAPPY (any other
+ * value: BQSR_ERR_INVALID_ARG).  fetch: ONE copy of the packed pages into comp
+ * (comp_bytes bytes) and the two tables: pages (n_pages entries; offset and
+ * bytes are those of the RAW body, which the page header needs) and comp_off
+ * [n_pages + 1], page i's compressed bytes being comp[comp_off[i],
+ * comp_off[i + 1]).  One compress and one fetch per size call.
+ * BQSR_ERR_INVALID_ARG: a compress without a size call, a fetch without a
+ * compress, an emit after a compress. */
+enum { BQSR_PARQUET_CODEC_SNAPPY = 1 };
+bqsr_status bqsr_parquet_pages_compress(bqsr_parquet_pages* enc, int32_t codec, void* stream, int64_t* comp_bytes);
+bqsr_status bqsr_parquet_pages_fetch(bqsr_parquet_pages* enc, uint8_t* comp, bqsr_parquet_page* pages,
+                                     int64_t* comp_off, void* stream);
+/* MEASUREMENT ONLY: the device-event times of the calling thread's last
+ * bqsr_parquet_pages_compress or bqsr_snappy_pages: the block kernel and the
+ * pack kernel, in milliseconds (tools/bench_adam.py --parquet-encoder). */
+bqsr_status bqsr_parquet_pages_compress_times(double* snappy_ms, double* pack_ms);
+
 /* adam2sam: ADAMRecord Parquet out as SAM or BAM.  The records of an Arrow
  * table are rendered as SAM lines on the device (adam_lines.hip) and the text
  * parsed like SAM input, so the result is an ordinary bqsr_sam: the SAM text

@@ -21,6 +21,8 @@ best of --reps), Arrow's read, the upload-and-count call and the kernel alone
 
     python tools/bench_adam.py --reads2ref [--reads 2000000] [--part-reads N] [--compression snappy]
     python tools/bench_adam.py --reads2ref --parquet-encoder [--reads 2000000]   (host next to device pages)
+    python tools/bench_adam.py [--reads2ref] --parquet-encoder --device-snappy-only   (device pages under snappy:
+                                                 -parquet_compressor host next to device, nothing else)
 
 --reads2ref measures `adam reads2ref` (adam_amd/reads2ref.py) over the same
 synthetic reads as SAM text: the job's steps run one after the other in the
@@ -604,6 +606,44 @@ def bench_reads2ref(a):
     print(json.dumps(res))
 
 
+def _device_snappy_legs(run, file_bytes, stats_of):
+    """The device encoder under snappy with the host codec and with
+    -parquet_compressor device, in this process on the same input: a warm-up
+    each, then three timed runs each, the two legs alternating.  run(compressor)
+    does one job and returns its statistics; file_bytes() the part files' bytes
+    of the job just done; stats_of(st) -> (page kernels' ms, bytes downloaded).
+    Per leg: the three wall times, their median and spread, the median run's
+    phases, kernel times (the compressor's two among them) and bytes
+    downloaded, the files' bytes; then the comparison, and whether the
+    difference of the medians exceeds the larger of the two spreads."""
+    legs = {"host": [], "device": []}
+    sizes = {}
+    for c in legs:
+        run(c)
+        sizes[c] = file_bytes()
+    for _ in range(3):
+        for c in legs:
+            t = time.perf_counter()
+            st = run(c)
+            legs[c].append((time.perf_counter() - t, st))
+    out = {}
+    for c, runs in legs.items():
+        runs.sort(key=lambda x: x[0])
+        secs = [x[0] for x in runs]
+        ms, down = stats_of(runs[1][1])
+        out[c + "_compressor"] = {"seconds": secs, "median_s": secs[1], "spread_s": secs[-1] - secs[0],
+                                  "phases_s": runs[1][1]["phases"], "page_kernels_ms": ms, "bytes_downloaded": down,
+                                  "file_bytes": sizes[c]}
+        log("device pages, %s compressor: %s s, %d bytes down, %d bytes of files" % (
+            c, ["%.2f" % x for x in secs], down, sizes[c]))
+    h, d = out["host_compressor"], out["device_compressor"]
+    out["device_over_host_compressor_seconds"] = d["median_s"] / h["median_s"]
+    out["device_over_host_compressor_bytes_downloaded"] = d["bytes_downloaded"] / h["bytes_downloaded"]
+    out["device_over_host_compressor_file_bytes"] = d["file_bytes"] / h["file_bytes"]
+    out["device_compressor_faster_beyond_spread"] = h["median_s"] - d["median_s"] > max(h["spread_s"], d["spread_s"])
+    return out
+
+
 def bench_reads2ref_pages(a):
     """--reads2ref --parquet-encoder: `reads2ref` with the host's Parquet
     encoder (Arrow's writer over downloaded columns: unchanged code, the
@@ -614,7 +654,9 @@ def bench_reads2ref_pages(a):
     kernels' device-event times and the bytes it downloaded; and a third
     leg: the device encoder runs with readStart / readEnd as the per-read
     dictionary and as PLAIN int64 (reads2ref.READ_SPANS names the form kept
-    per codec; the ratios are the kept form's)."""
+    per codec; the ratios are the kept form's).  Then "device_snappy": the
+    device encoder under snappy with -parquet_compressor host next to device
+    (_device_snappy_legs); --device-snappy-only runs nothing else."""
     import pyarrow.parquet as pq
     import torch
     from adam_amd import reads2ref as R
@@ -667,7 +709,16 @@ def bench_reads2ref_pages(a):
             shutil.rmtree(out, ignore_errors=True)
             return r
 
-        for codec in ("snappy", "gzip"):
+        def snappy_run(compressor):
+            R.READ_SPANS = dict(kept_forms)
+            return R._reads2ref(src, os.path.join(work, "out_snappy.adam"), "snappy", part_reads, a.partition_bytes,
+                                True, 0, parquet_encoder="device", parquet_compressor=compressor)
+
+        def snappy_bytes():
+            out = os.path.join(work, "out_snappy.adam")
+            return sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out) if f.startswith("part-r-"))
+
+        for codec in () if a.device_snappy_only else ("snappy", "gzip"):
             kept = kept_forms[codec]
             h, d, p = leg(codec, "host"), leg(codec, "device", "dictionary"), leg(codec, "device", "plain")
             k = d if kept == "dictionary" else p
@@ -675,7 +726,10 @@ def bench_reads2ref_pages(a):
                                     "read_spans_kept": kept,
                                     "device_over_host_seconds": k["seconds"] / h["seconds"],
                                     "device_over_host_file_bytes": k["file_bytes"] / h["file_bytes"]}
+        res["device_snappy"] = _device_snappy_legs(
+            snappy_run, snappy_bytes, lambda st: (st["page_kernels_ms"], st["page_bytes_downloaded"]))
     finally:
+        R.READ_SPANS = kept_forms
         if not a.dir:
             shutil.rmtree(work, ignore_errors=True)
     print(json.dumps(res))
@@ -689,7 +743,10 @@ def bench_transform_pages(a):
     once and timed three times.  Per leg: the three wall times, their median
     and spread, the emit and close phases of the median run, the part files'
     bytes in all and per column (from the footers), the bytes downloaded; the
-    device leg also the page kernels' device-event times."""
+    device leg also the page kernels' device-event times.  Then
+    "device_snappy" (SAM input): the device encoder under snappy with
+    -parquet_compressor host next to device (_device_snappy_legs);
+    --device-snappy-only runs nothing else and makes no BAM."""
     import pyarrow.compute as pc
     import pyarrow.parquet as pq
     import torch
@@ -699,8 +756,9 @@ def bench_transform_pages(a):
     t0 = time.perf_counter()
     sam = synthetic_sam(a.reads, a.len)
     log("generated %d bytes of SAM in %.1f s" % (len(sam), time.perf_counter() - t0))
-    bam = sam_to_bam_parallel(sam, min(16, len(os.sched_getaffinity(0))),  # (forks: before the GPU is touched)
-                              progress=lambda i, n: log("bam slice %d / %d" % (i, n)) if i % 8 == 0 else None)
+    bam = b"" if a.device_snappy_only else sam_to_bam_parallel(  # (forks: before the GPU is touched)
+        sam, min(16, len(os.sched_getaffinity(0))),
+        progress=lambda i, n: log("bam slice %d / %d" % (i, n)) if i % 8 == 0 else None)
     torch.zeros(1, device="cuda")
     bqsr.Context.get(0).tune(bgzf=a.bgzf)
     work = a.dir or tempfile.mkdtemp(prefix="bench_transform_pages_")
@@ -759,7 +817,20 @@ def bench_transform_pages(a):
             shutil.rmtree(out, ignore_errors=True)
             return r
 
-        for kind in ("sam", "bam"):
+        def snappy_run(compressor):
+            st = T.transform(src["sam"], os.path.join(work, "out_snappy.adam"), mark_duplicates=not a.no_markdup,
+                             recalibrate=True, partition_bytes=a.partition_bytes, compression="snappy",
+                             part_reads=a.part_reads, overwrite=True, parquet_encoder="device",
+                             parquet_compressor=compressor)
+            if st["reads"] != a.reads:
+                raise SystemExit("transformed %d reads, expected %d" % (st["reads"], a.reads))
+            return st
+
+        def snappy_bytes():
+            out = os.path.join(work, "out_snappy.adam")
+            return sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out) if f.startswith("part-r-"))
+
+        for kind in () if a.device_snappy_only else ("sam", "bam"):
             for codec in ("gzip", "snappy"):
                 h, d = leg(kind, codec, "host"), leg(kind, codec, "device")
                 res["legs"]["%s_%s" % (kind, codec)] = {
@@ -767,6 +838,8 @@ def bench_transform_pages(a):
                     "device_over_host_file_bytes": d["file_bytes"] / h["file_bytes"],
                     "cigar_bytes_host_dictionary": h["column_bytes"].get("cigar"),
                     "cigar_bytes_device_plain": d["column_bytes"].get("cigar")}
+        res["device_snappy"] = _device_snappy_legs(
+            snappy_run, snappy_bytes, lambda st: (st["pages"]["kernel_ms"], st["pages"]["bytes_downloaded"]))
     finally:
         if not a.dir:
             shutil.rmtree(work, ignore_errors=True)
@@ -1354,6 +1427,9 @@ def main():
     ap.add_argument("--parquet-encoder", action="store_true",
                     help="measure -parquet_encoder device next to the host encoder, snappy and gzip: of the transform "
                          "(SAM and BAM input), or with --reads2ref of reads2ref")
+    ap.add_argument("--device-snappy-only", action="store_true",
+                    help="--parquet-encoder: only the device encoder's snappy legs, -parquet_compressor host next to "
+                         "device")
     ap.add_argument("--aggregate", action="store_true",
                     help="measure adam aggregate_pileups next to adam reads2ref instead of the transform")
     ap.add_argument("--mpileup", action="store_true",
