@@ -61,6 +61,9 @@ EXPORTS = [
     "bqsr_bgzf_deflate_times",
     "bqsr_bam_index_create", "bqsr_bam_index_destroy", "bqsr_bam_index_add", "bqsr_bam_index_set_members",
     "bqsr_bam_index_finish", "bqsr_bam_index_size", "bqsr_bam_index_bytes",
+    "bqsr_bam_reader_open", "bqsr_bam_reader_destroy", "bqsr_bam_reader_members", "bqsr_bam_reader_seek",
+    "bqsr_bam_reader_next", "bqsr_bam_index_add_window", "bqsr_bam_reader_filter", "bqsr_bam_reader_parse",
+    "bqsr_bam_reader_get_stats",
     "bqsr_compare_create", "bqsr_compare_destroy", "bqsr_compare_check_terms", "bqsr_compare_sam", "bqsr_compare_sides",
     "bqsr_compare_values", "bqsr_compare_baseqs", "bqsr_compare_rows", "bqsr_compare_kernel_times",
     "bqsr_sam_tag_counts", "bqsr_arrow_tag_counts", "bqsr_sam_tag_values", "bqsr_arrow_tag_values",

@@ -66,7 +66,7 @@ from . import reads2ref as R
 from ._capi import check, dblp, i64, pp, vp
 from .adam_save import (BASES, PILEUP_DICT_COLS, PILEUP_FIELDS, PILEUP_STATS_COLS, RG_TAGS, AdamWriter, check_out,
                         header_info, pileup_schema)
-from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
+from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, add_region_arguments, is_parquet, rebased, region_plan, report
 
 DEFAULT_PART_ROWS = 1 << 20  # aggregated rows per part file (their joined read names stay far below 2 GB)
 WORKGROUP = 256              # rows per scan tile (pileup_agg.hip kThreads): the size the boundary tests straddle
@@ -480,14 +480,16 @@ def _sam_units(U: Units, hdr):
 
 def aggregate_pileups(inp: str, out: str, compression: str = "gzip", part_rows: int = DEFAULT_PART_ROWS,
                       partition_bytes: Optional[int] = None, overwrite: bool = False, device: int = 0,
-                      part_reads: int = R.DEFAULT_PART_READS, writer_args: Optional[dict] = None) -> Dict[str, object]:
+                      part_reads: int = R.DEFAULT_PART_READS, writer_args: Optional[dict] = None,
+                      region: Optional[str] = None, bai: Optional[str] = None) -> Dict[str, object]:
     """`adam aggregate_pileups`: the ADAMPileup rows of `inp` (ADAMPileup
     Parquet; or SAM, BAM or ADAMRecord Parquet, expanded as reads2ref does)
     aggregated by position into ADAMPileup Parquet part files under `out`,
     which appears only when the job succeeds.  part_rows: aggregated rows per
     part file; partition_bytes: SAM text per streamed partition; part_reads:
-    reads per expansion call.  Returns the job's statistics."""
+    reads per expansion call.  region, bai: BAM input read through its .bai index, only the reads that overlap the region (inputs.SamInput).  Returns the job's statistics."""
     from . import parquet as P
+    region = region_plan(inp, region, bai)  # (refused before anything is read or created)
     partition_bytes = DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes
     check_out(out, overwrite, True)
     ctx = bqsr.Context.get(device)
@@ -527,8 +529,9 @@ def aggregate_pileups(inp: str, out: str, compression: str = "gzip", part_rows: 
                 stats["reads"] = table.num_rows
         else:
             n_reads = 0
-            with SamInput(inp, ctx, ph, partition_bytes) as src:
+            with SamInput(inp, ctx, ph, partition_bytes, region=region, bai=bai) as src:
                 for sam, base in src:
+                    stats.update(src.region_stats or {})
                     hdr = header_info(sam)
                     ranks = _sam_units(U, hdr)
                     n = sam.counts().n_reads
@@ -599,9 +602,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("-partition_bytes", type=int, default=DEFAULT_PARTITION_BYTES,
                     help="SAM text per streamed partition, in bytes")
     ap.add_argument("-overwrite", action="store_true")
+    add_region_arguments(ap)
     a = ap.parse_args(argv)
+    try:
+        a.region = region_plan(a.input, a.region, a.bai)
+    except (ValueError, OSError) as e:
+        ap.error(str(e))
     t0 = time.perf_counter()
-    st = aggregate_pileups(a.input, a.output, a.parquet_compression, a.part_rows, a.partition_bytes, a.overwrite)
+    st = aggregate_pileups(a.input, a.output, a.parquet_compression, a.part_rows, a.partition_bytes, a.overwrite,
+                           region=a.region, bai=a.bai)
     report(st, t0)
     return 0
 

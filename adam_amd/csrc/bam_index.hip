@@ -76,6 +76,54 @@ extern "C" __global__ void __launch_bounds__(kThreads) bai_rows(RowsParams A) {
   }
 }
 
+// The same row straight from a raw BAM record (`bam_index` on a file this project did not write, bam_windows.hip):
+// buf holds the window's records, record i's block_size word at rec[i] and its end at rec[i + 1].  beg = max(pos, 0),
+// end = pos + the CIGAR words' reference length over M D N = X (pos + 1 when that is 0), at least beg + 1.  A record
+// whose name and CIGAR do not fit its block_size leaves (first + i) << 8 | 1 in *err, the smallest wins.
+struct RawRecord {
+  int32_t ref;
+  uint32_t beg, end, flag;
+  bool good;
+};
+__device__ __forceinline__ RawRecord raw_record(const uint8_t* b, uint64_t size) {
+  const int64_t pos = (int32_t)bamk::rd32(b + 8);
+  const uint32_t l_name = b[12], n_cig = bamk::rd16(b + 16);
+  RawRecord r{(int32_t)bamk::rd32(b + 4), 0u, 1u, (uint32_t)bamk::rd16(b + 18), 36ull + l_name + 4ull * n_cig <= size};
+  int64_t ref_len = 0;
+  if (r.good) {
+    const uint8_t* c = b + 36 + l_name;
+    for (uint32_t k = 0; k < n_cig; ++k) {
+      const uint32_t w = bamk::rd32(c + 4 * k), op = w & 15u;
+      if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += w >> 4;
+    }
+  }
+  const int64_t beg = pos < 0 ? 0 : pos;
+  int64_t end = pos + (ref_len > 0 ? ref_len : 1);
+  if (end < beg + 1) end = beg + 1;
+  r.beg = (uint32_t)beg;
+  r.end = (uint32_t)(end > 0xFFFFFFFFll ? 0xFFFFFFFFll : end);
+  return r;
+}
+
+struct RawRowsParams {
+  const uint8_t* buf;
+  const uint64_t* rec;  // [n + 1]
+  int64_t n;
+  Row* rows;
+  uint64_t base;        // the stream offset of buf[0]
+  int64_t first;        // the ordinal of record 0 in the whole file
+  unsigned long long* err;
+};
+
+extern "C" __global__ void __launch_bounds__(kThreads) bai_rows_raw(RawRowsParams A) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t o = A.rec[i];
+    const RawRecord r = raw_record(A.buf + o, A.rec[i + 1] - o);
+    if (!r.good) atomicMin(A.err, ((unsigned long long)(A.first + i) << 8) | 1ull);
+    A.rows[i] = Row{r.ref, r.beg, r.end, r.flag & 4u, A.base + o};
+  }
+}
+
 // mem: [2 (nm + 1)] (stream start, file offset) of every member, the EOF marker included, then the terminal entry.
 // Position p lies in the last member whose start is not above it: among members of one start (an empty one
 // before the next) that is the one that holds bytes, and for p = the stream's end it is the EOF marker.
@@ -312,6 +360,32 @@ void bai_put(std::string& o, T v) {
   o.append((const char*)&v, sizeof v);
 }
 
+// room for n more rows: grown with what it holds (a new array, a copy, the old one freed after it)
+bqsr_status bai_rows_reserve(bqsr_bam_index& X, int64_t n, hipStream_t st) {
+  if (X.cap_rows < X.n_rows + n) {
+    const int64_t cap = std::max<int64_t>(X.n_rows + n, 2 * X.cap_rows);
+    baik::Row* p = nullptr;
+    if (hipMalloc((void**)&p, (size_t)cap * sizeof(baik::Row)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(BQSR_ERR_UNSUPPORTED, "BAM index: the rows of the whole output stay resident on the device and do "
+                                        "not fit: " + std::to_string((size_t)cap * sizeof(baik::Row)) + " bytes");
+    }
+    hipError_t e = hipSuccess;
+    if (X.n_rows > 0) {
+      e = hipMemcpyAsync(p, X.rows, (size_t)X.n_rows * sizeof(baik::Row), hipMemcpyDeviceToDevice, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      return fail(BQSR_ERR_DEVICE, std::string("bqsr_bam_index_add: ") + hipGetErrorString(e));
+    }
+    if (X.rows) (void)hipFree(X.rows);
+    X.rows = p;
+    X.cap_rows = cap;
+  }
+  return BQSR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -347,27 +421,7 @@ bqsr_status bqsr_bam_index_add(bqsr_bam_index* x, bqsr_sam* s, int64_t stream_ba
   X.on_device = true;
   hipStream_t st = S(stream);
   bai_rows_time(X);
-  if (X.cap_rows < X.n_rows + A.n) {  // grown with what it holds: a new array, a copy, the old one freed after it
-    const int64_t cap = std::max<int64_t>(X.n_rows + A.n, 2 * X.cap_rows);
-    baik::Row* p = nullptr;
-    if (hipMalloc((void**)&p, (size_t)cap * sizeof(baik::Row)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(BQSR_ERR_UNSUPPORTED, "BAM index: the rows of the whole output stay resident on the device and do "
-                                        "not fit: " + std::to_string((size_t)cap * sizeof(baik::Row)) + " bytes");
-    }
-    hipError_t e = hipSuccess;
-    if (X.n_rows > 0) {
-      e = hipMemcpyAsync(p, X.rows, (size_t)X.n_rows * sizeof(baik::Row), hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (e != hipSuccess) {
-      (void)hipFree(p);
-      return fail(BQSR_ERR_DEVICE, std::string("bqsr_bam_index_add: ") + hipGetErrorString(e));
-    }
-    if (X.rows) (void)hipFree(X.rows);
-    X.rows = p;
-    X.cap_rows = cap;
-  }
+  JOB_TRY(bai_rows_reserve(X, A.n, st));
   if (A.n > 0) {
     baik::RowsParams R{bam_params(s, A), X.rows + X.n_rows, (uint64_t)stream_base};
     HIP_TRY(X.clock.mark(BAI_ROWS_0, st));

@@ -649,6 +649,70 @@ bqsr_status bam_inflate_device(bqsr_context* ctx, const uint8_t* data, int64_t n
   return BQSR_OK;
 }
 
+// The records of an inflated BAM stream as SAM text on the device: d_records
+// holds them, record r's block_size word at d_rec[r] (n + 1 entries); the
+// header text (newline-terminated here, H.body set) goes first.  *d_text is the
+// caller's (sam_parse_device takes it over).  Shared by bqsr_bam_parse and the
+// region reader (bam_windows.hip).
+bqsr_status bam_lines_text(bqsr_context* ctx, const uint8_t* d_records, const uint64_t* d_rec, int64_t nr, BamHead& BH,
+                           SamHeader& H, std::string& hdr, hipStream_t s, std::vector<void*>& tmp, uint8_t** d_text_out,
+                           int64_t* n_text_out) {
+  bqsr_status st;
+  std::vector<uint8_t>& ref_blob = BH.ref_blob;
+  std::vector<uint64_t>& ref_off = BH.ref_off;
+  const int64_t n_ref = (int64_t)ref_off.size() - 1;
+  // the header text, newline-terminated, then the records' SAM lines
+  if (!hdr.empty() && hdr.back() != '\n') hdr.push_back('\n');
+  H.body = (int64_t)hdr.size();
+  bamk::BamParams P{};
+  P.buf = d_records;
+  P.n = nr;
+  P.n_ref = (int32_t)n_ref;
+  P.hdr = H.body;
+  P.rec = d_rec;
+  if ((st = sam_upload(tmp, (uint8_t**)&P.ref_blob, ref_blob.empty() ? std::vector<uint8_t>{0} : ref_blob, s)) != BQSR_OK)
+    return st;
+  if ((st = sam_upload(tmp, (uint64_t**)&P.ref_off, ref_off, s)) != BQSR_OK) return st;
+  if ((st = sam_alloc(tmp, &P.err, 1)) != BQSR_OK) return st;
+  HIP_TRY(hipMemsetAsync(P.err, 0xFF, 8, s));
+  uint64_t *len, *off, *part;
+  if ((st = sam_alloc(tmp, &len, (size_t)nr)) != BQSR_OK || (st = sam_alloc(tmp, &off, (size_t)nr + 1)) != BQSR_OK ||
+      (st = sam_alloc(tmp, &part, (size_t)(nr / samk::kScanChunk + 2))) != BQSR_OK)
+    return st;
+  P.len = len;
+  P.off = off;
+  const unsigned g = sam_grid(nr, 256, ctx->n_cu * 16);
+  if (nr > 0) JOB_TRY(launch(bamk::bam_lines_len, g, 256, s, P));
+  if ((st = sam_scan(len, nr, off, part, s)) != BQSR_OK) return st;
+  unsigned long long e_word = ~0ull;
+  uint64_t body_bytes = 0;
+  HIP_TRY(hipMemcpyAsync(&e_word, P.err, 8, hipMemcpyDeviceToHost, s));
+  if (nr > 0) HIP_TRY(hipMemcpyAsync(&body_bytes, off + nr, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (e_word != ~0ull) {
+    const uint32_t code = (uint32_t)(e_word & 0xFF);
+    char buf[160];
+    snprintf(buf, sizeof buf, "BAM record %lld: %s", (long long)(e_word >> 8),
+             code == bamk::kBamTag ? "malformed optional field" : "malformed record");
+    return fail(BQSR_ERR_SAM_PARSE, buf);
+  }
+  const int64_t n_text = H.body + (int64_t)body_bytes;
+  uint8_t* d_text = nullptr;
+  HIP_TRY(hipMalloc(&d_text, (size_t)n_text + 64));
+  hipError_t e = hipMemsetAsync(d_text + n_text, 0, 64, s);
+  if (e == hipSuccess && H.body > 0) e = hipMemcpyAsync(d_text, hdr.data(), hdr.size(), hipMemcpyHostToDevice, s);
+  P.out = d_text;
+  if (e == hipSuccess && nr > 0) e = launch_err(bamk::bam_lines_write, g, 256, s, P);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the header copy reads `hdr`)
+  if (e != hipSuccess) {
+    (void)hipFree(d_text);
+    return fail(BQSR_ERR_DEVICE, std::string("bqsr_bam_parse: ") + hipGetErrorString(e));
+  }
+  *d_text_out = d_text;
+  *n_text_out = n_text;
+  return BQSR_OK;
+}
+
 }  // namespace
 
 bqsr_status bqsr_bam_parse(bqsr_context* ctx, const uint8_t* data, int64_t n, void* stream, bqsr_sam** out) {
@@ -714,63 +778,14 @@ bqsr_status bqsr_bam_parse(bqsr_context* ctx, const uint8_t* data, int64_t n, vo
   }
   }  // (host form)
   const double t_inflated = now_s();
-  const int64_t body = BH.body;
-  std::vector<uint64_t>& rec = scan.rec;
-  std::vector<uint8_t>& ref_blob = BH.ref_blob;
-  std::vector<uint64_t>& ref_off = BH.ref_off;
-  const int64_t n_ref = (int64_t)ref_off.size() - 1;
-  const int64_t nr = dev ? nr_dev : (int64_t)rec.size();
-  if (!dev) rec.push_back((uint64_t)(m - body));
-  // the header text, newline-terminated, then the records' SAM lines
-  if (!hdr.empty() && hdr.back() != '\n') hdr.push_back('\n');
-  H.body = (int64_t)hdr.size();
-  bamk::BamParams P{};
-  P.buf = d_raw + body;
-  P.n = nr;
-  P.n_ref = (int32_t)n_ref;
-  P.hdr = H.body;
-  if (dev)
-    P.rec = d_rec;
-  else if ((st = sam_upload(tmp, (uint64_t**)&P.rec, rec, s)) != BQSR_OK)
-    return st;
-  if ((st = sam_upload(tmp, (uint8_t**)&P.ref_blob, ref_blob.empty() ? std::vector<uint8_t>{0} : ref_blob, s)) != BQSR_OK)
-    return st;
-  if ((st = sam_upload(tmp, (uint64_t**)&P.ref_off, ref_off, s)) != BQSR_OK) return st;
-  if ((st = sam_alloc(tmp, &P.err, 1)) != BQSR_OK) return st;
-  HIP_TRY(hipMemsetAsync(P.err, 0xFF, 8, s));
-  uint64_t *len, *off, *part;
-  if ((st = sam_alloc(tmp, &len, (size_t)nr)) != BQSR_OK || (st = sam_alloc(tmp, &off, (size_t)nr + 1)) != BQSR_OK ||
-      (st = sam_alloc(tmp, &part, (size_t)(nr / samk::kScanChunk + 2))) != BQSR_OK)
-    return st;
-  P.len = len;
-  P.off = off;
-  const unsigned g = sam_grid(nr, 256, ctx->n_cu * 16);
-  if (nr > 0) JOB_TRY(launch(bamk::bam_lines_len, g, 256, s, P));
-  if ((st = sam_scan(len, nr, off, part, s)) != BQSR_OK) return st;
-  unsigned long long e_word = ~0ull;
-  uint64_t body_bytes = 0;
-  HIP_TRY(hipMemcpyAsync(&e_word, P.err, 8, hipMemcpyDeviceToHost, s));
-  if (nr > 0) HIP_TRY(hipMemcpyAsync(&body_bytes, off + nr, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (e_word != ~0ull) {
-    const uint32_t code = (uint32_t)(e_word & 0xFF);
-    char buf[160];
-    snprintf(buf, sizeof buf, "BAM record %lld: %s", (long long)(e_word >> 8),
-             code == bamk::kBamTag ? "malformed optional field" : "malformed record");
-    return fail(BQSR_ERR_SAM_PARSE, buf);
+  const int64_t nr = dev ? nr_dev : (int64_t)scan.rec.size();
+  if (!dev) {
+    scan.rec.push_back((uint64_t)(m - BH.body));
+    if ((st = sam_upload(tmp, &d_rec, scan.rec, s)) != BQSR_OK) return st;
   }
-  const int64_t n_text = H.body + (int64_t)body_bytes;
   uint8_t* d_text = nullptr;
-  HIP_TRY(hipMalloc(&d_text, (size_t)n_text + 64));
-  hipError_t e = hipMemsetAsync(d_text + n_text, 0, 64, s);
-  if (e == hipSuccess && H.body > 0) e = hipMemcpyAsync(d_text, hdr.data(), hdr.size(), hipMemcpyHostToDevice, s);
-  P.out = d_text;
-  if (e == hipSuccess && nr > 0) e = launch_err(bamk::bam_lines_write, g, 256, s, P);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the header copy reads `hdr`)
-  if (e != hipSuccess) {
-    (void)hipFree(d_text);
-    return fail(BQSR_ERR_DEVICE, std::string("bqsr_bam_parse: ") + hipGetErrorString(e));
-  }
+  int64_t n_text = 0;
+  if ((st = bam_lines_text(ctx, d_raw + BH.body, d_rec, nr, BH, H, hdr, s, tmp, &d_text, &n_text)) != BQSR_OK) return st;
   const double t_lines = now_s();
   st = sam_parse_device(ctx, H, hdr.data(), d_text, n_text, s, true, out);  // (owns d_text from here)
   if (st == BQSR_OK) (*out)->bam_form = dev ? 2 : 1;

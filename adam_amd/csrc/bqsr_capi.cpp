@@ -2467,6 +2467,7 @@ bqsr_status bqsr_job_tail_async(bqsr_context* ctx, bqsr_batch* b, const bqsr_sit
 #include "adam_out.hip"
 #include "bam_out.hip"
 #include "bam_index.hip"
+#include "bam_windows.hip"
 #include "bgzf_deflate.hip"
 #include "sam_sort.hip"
 #include "flagstat.hip"

@@ -30,7 +30,7 @@ from typing import Dict, Optional, Tuple
 
 from . import _capi, bqsr
 from ._capi import check, i32, vp
-from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
+from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, add_region_arguments, is_parquet, rebased, region_plan, report
 
 # the command's projection (cli/FlagStat.scala:50-57), booleans in bqsr_flagstat_chunk's order
 BOOL_COLUMNS = ("readPaired", "properPair", "readMapped", "mateMapped", "firstOfPair", "secondOfPair",
@@ -157,7 +157,8 @@ def table_chunks(table):
     return chunks, keep
 
 
-def _flagstat(path: str, device: int, partition_bytes: int):
+def _flagstat(path: str, device: int, partition_bytes: int, region=None, bai=None):
+    region = region_plan(path, region, bai)  # (refused before anything is read)
     ctx = bqsr.Context.get(device)
     ph = Phases()
     failed, passed = FlagStatMetrics(), FlagStatMetrics()
@@ -172,10 +173,11 @@ def _flagstat(path: str, device: int, partition_bytes: int):
         del keep
         stats["reads"] = table.num_rows
     else:
-        with SamInput(path, ctx, ph, partition_bytes) as src:
+        with SamInput(path, ctx, ph, partition_bytes, region=region, bai=bai) as src:
             if not src.bam and len(src.data):
                 stats["partitions"] = src.n_partitions
             for sam, base in src:
+                stats.update(src.region_stats or {})
                 with ph("flagstat"):
                     try:
                         f, p = sam_flagstat(sam)
@@ -187,13 +189,14 @@ def _flagstat(path: str, device: int, partition_bytes: int):
     return failed, passed, stats
 
 
-def flagstat(path: str, device: int = 0, partition_bytes: Optional[int] = None
-             ) -> Tuple[FlagStatMetrics, FlagStatMetrics]:
+def flagstat(path: str, device: int = 0, partition_bytes: Optional[int] = None, region: Optional[str] = None,
+             bai: Optional[str] = None) -> Tuple[FlagStatMetrics, FlagStatMetrics]:
     """adamFlagStat of a SAM, BAM or ADAMRecord Parquet input: (failed,
     passed), the reference's order (rdd/FlagStat.scala:102-114).
     partition_bytes: SAM text per streamed partition (default:
-    inputs.DEFAULT_PARTITION_BYTES)."""
-    f, p, _ = _flagstat(path, device, DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes)
+    inputs.DEFAULT_PARTITION_BYTES).  region (BAM input): only the reads that
+    overlap it, read through the .bai index (inputs.SamInput)."""
+    f, p, _ = _flagstat(path, device, DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes, region, bai)
     return f, p
 
 
@@ -254,9 +257,14 @@ def main(argv=None) -> int:
     ap.add_argument("input")
     ap.add_argument("-partition_bytes", type=int, default=DEFAULT_PARTITION_BYTES,
                     help="SAM text per streamed partition, in bytes")
+    add_region_arguments(ap)
     a = ap.parse_args(argv)
+    try:
+        a.region = region_plan(a.input, a.region, a.bai)
+    except (ValueError, OSError) as e:
+        ap.error(str(e))
     t0 = time.perf_counter()
-    failed, passed, st = _flagstat(a.input, 0, a.partition_bytes)
+    failed, passed, st = _flagstat(a.input, 0, a.partition_bytes, a.region, a.bai)
     print(format_flagstat(failed, passed))
     report(st, t0)
     return 0

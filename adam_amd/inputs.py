@@ -104,22 +104,36 @@ class SamInput:
     ``.bam``, ``.n_partitions``, and ``.data`` / ``.header`` / ``.ranges``
     (the map and its cut; ranges is None for one partition) are set on entry.
     parse(data, ctx, bam=...) replaces sam.SamText; its result needs only
-    ``.close()`` and ``.counts().n_reads``."""
+    ``.close()`` and ``.counts().n_reads``.
 
-    def __init__(self, path: str, ctx, phases, partition_bytes=None, parse=None):
+    region (``NAME``, ``NAME:BEG`` or ``NAME:BEG-END``, bam_index.parse_region)
+    (or a :class:`RegionPlan` made before) reads a BAM through its .bai index
+    (`bai`, else IN.bam.bai, else IN.bai):
+    one partition, partition_bytes ignored, whose parse is the header plus the
+    records that overlap the region, in file order; only the BGZF members the
+    index names are read (bam_index.region_text; its counts are in
+    ``.region_stats`` after the iteration).  :func:`region_plan` refuses on
+    entry, before anything is parsed: SAM or Parquet input, a missing index, a
+    reference the header does not have (ValueError)."""
+
+    def __init__(self, path: str, ctx, phases, partition_bytes=None, parse=None, *, region=None, bai=None):
         if parse is None:
             from .sam import SamText as parse
         self.path, self.ctx, self.phases, self.partition_bytes, self.parse = path, ctx, phases, partition_bytes, parse
+        self.region, self.bai = region, bai
+        self.plan = None
+        self.region_stats = None
         self.data = None
         self._sam = None
 
     def __enter__(self):
+        self.plan = region_plan(self.path, self.region, self.bai)
         with open(self.path, "rb") as fh:
             self.data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if os.path.getsize(self.path) else b""
         try:
             self.bam = is_bam(self.data)
             self.header = self.ranges = None
-            if self.partition_bytes is not None and not self.bam and len(self.data):
+            if self.partition_bytes is not None and not self.bam and len(self.data) and self.plan is None:
                 header, ranges = sam_partitions(self.data, self.partition_bytes)
                 if len(ranges) > 1:
                     self.header, self.ranges = header, ranges
@@ -149,7 +163,10 @@ class SamInput:
             self._close_parse()
             with self.phases("parse"):
                 # (the view of the map is made inside the call, so that it does not outlive it)
-                if self.ranges is None:
+                if self.plan is not None:
+                    from .bam_index import region_text
+                    self._sam, self.region_stats = region_text(self.data, self.ctx, *self.plan)
+                elif self.ranges is None:
                     self._sam = self.parse(host_bytes(self.data), self.ctx, bam=self.bam)
                 else:
                     a, b = self.ranges[k]
@@ -157,6 +174,55 @@ class SamInput:
             yield self._sam, base
             base += self._sam.counts().n_reads
         self._close_parse()
+
+
+class RegionPlan(tuple):
+    """(index, refID, beg, end): what :func:`region_plan` made of ``-region R [-bai F]``, for bam_index.region_text"""
+
+
+def region_plan(path: str, region, bai=None):
+    """What ``-region R [-bai F]`` on the input at `path` reads: None without
+    a region, else a :class:`RegionPlan`.  A plan given as `region` is returned
+    as it is, so a command makes it once (its ``main``, or its library
+    function) and hands it down as ``region=``: the header is inflated and the
+    .bai read and checked one time.
+    ValueError, with no device touched and nothing created, for SAM or Parquet
+    input, a missing index file, a reference the BAM header does not have, a
+    region that does not parse, an index that is not this file's, a BAM whose
+    header does not inflate."""
+    if isinstance(region, RegionPlan):
+        return region
+    if region is None:
+        if bai is not None:
+            raise ValueError("-bai goes with -region")
+        return None
+    from . import bam_index as BI
+    if is_parquet(path):
+        raise ValueError("-region reads a BAM through its .bai index: %s is Parquet input" % path)
+    with open(path, "rb") as fh:
+        if not is_bam(fh.read(4)):
+            raise ValueError("-region reads a BAM through its .bai index: %s is not a BAM" % path)
+        bai_path = BI.find_index(path, bai)
+        data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+    try:
+        _text, names, _lens = BI.bam_header(data)
+        size = len(data)
+    finally:
+        data.close()
+    rid, beg, end = BI.parse_region(region, names)
+    index = BI.BaiIndex.read(bai_path)
+    index.validate(len(names), size)
+    return RegionPlan((index, rid, beg, end))
+
+
+def add_region_arguments(ap) -> None:
+    """``-region R [-bai F]`` on a command that opens its input through SamInput"""
+    ap.add_argument("-region", default=None, metavar="NAME[:BEG[-END]]",
+                    help="BAM input only: read the reads that overlap the region (1-based, inclusive) through the "
+                         "file's .bai index (python -m adam_amd.bam_index IN.bam writes one); the command sees "
+                         "exactly those reads, as if the input were the filtered file: MarkDuplicates and BQSR "
+                         "(transform) work on what the region holds, and a mate outside the region is absent")
+    ap.add_argument("-bai", default=None, metavar="FILE", help="the index file (default: IN.bam.bai, else IN.bai)")
 
 
 def rebased(e: _capi.BQSRError, base: int) -> _capi.BQSRError:

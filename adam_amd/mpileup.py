@@ -59,7 +59,7 @@ import numpy as np
 
 from . import _capi, bqsr
 from ._capi import check, dblp, i32, i64, i64p, vp
-from .inputs import Phases, SamInput, is_parquet, report, text_output
+from .inputs import Phases, SamInput, add_region_arguments, is_parquet, region_plan, report, text_output
 
 # Text per window.  A window's bytes exist once on the device and once in
 # pinned host memory; 64 MiB keeps both small beside either memory and is far
@@ -196,15 +196,16 @@ def _input_row(e: _capi.BQSRError, rows) -> _capi.BQSRError:
 
 
 def mpileup(inp: str, out: Optional[str] = None, window_bytes: int = DEFAULT_WINDOW_BYTES, device: int = 0,
-            stdout=None) -> Dict[str, object]:
+            stdout=None, region: Optional[str] = None, bai: Optional[str] = None) -> Dict[str, object]:
     """`adam mpileup`: the pileup text of a SAM, BAM or ADAMRecord Parquet
     input, to `out` or, without it, to stdout (inputs.text_output: the job's
     checks have passed before the first byte is written).  Returns the job's
     statistics; raises :class:`_capi.BQSRError` as the module doc says
     (``.read``: the read's index in the input; for REFERENCE_CONFLICT the
-    position)."""
+    position).  region, bai: BAM input read through its .bai index, only the reads that overlap the region (inputs.SamInput)."""
     if int(window_bytes) < 1:
         raise ValueError("window_bytes must be at least 1")
+    region = region_plan(inp, region, bai)  # (refused before anything is read or created)
     ph = Phases()
     stats: Dict[str, object] = {}
     with text_output(out, stdout) as sink:
@@ -242,8 +243,9 @@ def mpileup(inp: str, out: Optional[str] = None, window_bytes: int = DEFAULT_WIN
             finally:
                 A.close()
         else:
-            with SamInput(inp, ctx, ph) as src:
+            with SamInput(inp, ctx, ph, region=region, bai=bai) as src:
                 for sam, _ in src:
+                    stats.update(src.region_stats or {})
                     run(lambda: sam_prepare(sam), lambda sz: sam_mpileup(sam, window_bytes, sizes=sz),
                         sam.counts().n_reads)
     stats["phases"] = ph.t
@@ -256,13 +258,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("-output", default=None, help="write the text here (default: stdout)")
     ap.add_argument("-window_bytes", type=int, default=DEFAULT_WINDOW_BYTES,
                     help="text per window, in bytes; a line must fit")
+    add_region_arguments(ap)
     a = ap.parse_args(argv)
     if a.window_bytes < 1:
         ap.error("-window_bytes must be at least 1")
     if not os.path.exists(a.input):
         ap.error("no such input: %s" % a.input)
+    try:
+        a.region = region_plan(a.input, a.region, a.bai)
+    except (ValueError, OSError) as e:
+        ap.error(str(e))
     t0 = time.perf_counter()
-    st = mpileup(a.input, a.output, a.window_bytes)
+    st = mpileup(a.input, a.output, a.window_bytes, region=a.region, bai=a.bai)
     report(st, t0)
     return 0
 

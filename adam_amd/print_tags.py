@@ -41,7 +41,7 @@ import numpy as np
 
 from . import _capi, bqsr
 from ._capi import check, dblp, i32, vp
-from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
+from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, add_region_arguments, is_parquet, rebased, region_plan, report
 
 # the command's projection (cli/PrintTags.scala:68)
 PROJECTION = ("attributes", "primaryAlignment", "readMapped", "readPaired", "failedVendorQualityChecks")
@@ -242,8 +242,9 @@ def _sam_list(sam, hdr, want: int, out: List[str]) -> None:
 
 
 def _run(path: str, list_n: Optional[int], count: Iterable[str], device: int, partition_bytes: int,
-         hash_bits: int = HASH_BITS):
-    """(list lines, {tag: count}, {tag: {(type, text): count}}, total, stats)"""
+         hash_bits: int = HASH_BITS, region: Optional[str] = None, bai: Optional[str] = None):
+    """(list lines, {tag: count}, {tag: {(type, text): count}}, total, stats); region, bai: BAM input read through its .bai index, only the reads that overlap the region (inputs.SamInput)"""
+    region = region_plan(path, region, bai)  # (refused before anything is read)
     ctx = bqsr.Context.get(device)
     ph = Phases()
     tags: Dict[str, int] = {}
@@ -277,13 +278,14 @@ def _run(path: str, list_n: Optional[int], count: Iterable[str], device: int, pa
         stats["reads"] = table.num_rows
     else:
         from .adam_save import header_info
-        with SamInput(path, ctx, ph, partition_bytes) as src:
+        with SamInput(path, ctx, ph, partition_bytes, region=region, bai=bai) as src:
             if not src.bam and len(src.data):
                 stats["partitions"] = src.n_partitions
 
             def passes(work):
                 n_reads = 0
                 for sam, base in src:
+                    stats.update(src.region_stats or {})
                     try:
                         work(sam)
                     except _capi.BQSRError as e:
@@ -356,12 +358,12 @@ def format_tags(lines: Sequence[str], tags: Dict[str, int], values: Dict[str, Di
 
 
 def print_tags(path: str, list_n: Optional[int] = None, count: Iterable[str] = (), device: int = 0,
-               partition_bytes: Optional[int] = None) -> str:
+               partition_bytes: Optional[int] = None, region: Optional[str] = None, bai: Optional[str] = None) -> str:
     """The text `adam print_tags INPUT [-list list_n] [-count ...]` prints.  A
     `count` name that is not a two-char tag of the input is ignored, as in the
     reference."""
     pb = DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes
-    lines, tags, values, total, _ = _run(path, list_n, tuple(count), device, pb)
+    lines, tags, values, total, _ = _run(path, list_n, tuple(count), device, pb, region=region, bai=bai)
     return format_tags(lines, tags, values, total)
 
 
@@ -374,10 +376,15 @@ def main(argv=None) -> int:
                     help="comma-separated tag names whose distinct values are printed with their counts")
     ap.add_argument("-partition_bytes", type=int, default=DEFAULT_PARTITION_BYTES,
                     help="SAM text per streamed partition, in bytes")
+    add_region_arguments(ap)
     a = ap.parse_args(argv)
+    try:
+        a.region = region_plan(a.input, a.region, a.bai)
+    except (ValueError, OSError) as e:
+        ap.error(str(e))
     t0 = time.perf_counter()
     count = tuple(a.count.split(",")) if a.count is not None else ()
-    lines, tags, values, total, st = _run(a.input, a.list, count, 0, a.partition_bytes)
+    lines, tags, values, total, st = _run(a.input, a.list, count, 0, a.partition_bytes, region=a.region, bai=a.bai)
     print(format_tags(lines, tags, values, total))
     report(st, t0)
     return 0

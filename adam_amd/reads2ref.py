@@ -58,7 +58,7 @@ from . import _capi, adam_save, bqsr
 from ._capi import check, dblp, i32, i64, vp
 from .adam_save import (BASES, PILEUP_DICT_COLS, PILEUP_FIELDS, PILEUP_STATS_COLS, RG_TAGS, AdamHost, AdamSizes,
                         AdamWriter, HeaderInfo, _pinned, check_out, header_info, pileup_schema)
-from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, is_parquet, rebased, report
+from .inputs import DEFAULT_PARTITION_BYTES, Phases, SamInput, add_region_arguments, is_parquet, rebased, region_plan, report
 from .parquet_pages import COMPRESSORS, compressor_refusal
 
 # Reads per part file.  A read gives about as many rows as it has bases and a
@@ -482,12 +482,14 @@ def locus_filter(table):
 
 def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_bytes: int, overwrite: bool,
                device: int, writer_args: Optional[dict] = None, parquet_encoder: str = "host",
-               page_rows: Optional[int] = None, parquet_compressor: str = "host") -> Dict[str, object]:
+               page_rows: Optional[int] = None, parquet_compressor: str = "host", region: Optional[str] = None,
+               bai: Optional[str] = None) -> Dict[str, object]:
     if parquet_encoder not in ("host", "device"):
         raise ValueError("parquet_encoder is 'host' or 'device'")
     why = compressor_refusal(parquet_compressor, parquet_encoder, compression)  # before anything is read or created
     if why:
         raise ValueError(why)
+    region = region_plan(inp, region, bai)  # (refused before anything is read or created)
     on_device = parquet_encoder == "device"
     check_out(out, overwrite, True)
     ctx = bqsr.Context.get(device)
@@ -542,9 +544,10 @@ def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_
                 A.close()
             stats["reads"] = table.num_rows
         else:
-            with SamInput(inp, ctx, ph, partition_bytes) as src:
+            with SamInput(inp, ctx, ph, partition_bytes, region=region, bai=bai) as src:
                 stats["partitions"] = src.n_partitions
                 for sam, base in src:
+                    stats.update(src.region_stats or {})
                     hdr = header_info(sam)
                     n = sam.counts().n_reads
                     emit(lambda r0, m: sam_pileups(sam, r0, m, hdr),
@@ -574,7 +577,8 @@ def _reads2ref(inp: str, out: str, compression: str, part_reads: int, partition_
 def reads2ref(inp: str, out: str, aggregate: bool = False, min_mapq: int = 30, compression: str = "gzip",
               part_reads: int = DEFAULT_PART_READS, partition_bytes: Optional[int] = None, overwrite: bool = False,
               device: int = 0, parquet_encoder: str = "host", page_rows: Optional[int] = None,
-              parquet_compressor: str = "host") -> Dict[str, object]:
+              parquet_compressor: str = "host", region: Optional[str] = None, bai: Optional[str] = None
+              ) -> Dict[str, object]:
     """`adam reads2ref`: the reads of a SAM, BAM or ADAMRecord Parquet input
     as ADAMPileup Parquet part files under `out` (which appears only when the
     job succeeds; an existing one is refused unless overwrite, and then only
@@ -588,14 +592,15 @@ def reads2ref(inp: str, out: str, aggregate: bool = False, min_mapq: int = 30, c
     table.  parquet_compressor "device": the data pages are snappy-compressed
     on the GPU before they come down (only with parquet_encoder "device" and
     compression "snappy"; a ValueError otherwise, before anything is read or
-    created).  Returns the job's statistics."""
+    created).  region, bai: BAM input read through its .bai index, only the reads that overlap the region (inputs.SamInput).  Returns the job's statistics."""
     if aggregate:
         raise ValueError("-aggregate is outside this build: PileupAggregator joins read names in Spark's shuffle "
                          "order, so the reference itself does not define its result")
     int(min_mapq)  # (checked to be a number, then unused: Reads2Ref.scala parses -mapq and never reads it)
     return _reads2ref(inp, out, compression, part_reads,
                       DEFAULT_PARTITION_BYTES if partition_bytes is None else partition_bytes, overwrite, device,
-                      parquet_encoder=parquet_encoder, page_rows=page_rows, parquet_compressor=parquet_compressor)
+                      parquet_encoder=parquet_encoder, page_rows=page_rows, parquet_compressor=parquet_compressor,
+                      region=region, bai=bai)
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -614,15 +619,21 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     help="where the part files' data pages are encoded (device: adam_amd/parquet_pages.py)")
     ap.add_argument("-parquet_compressor", default="host", choices=COMPRESSORS,
                     help="where the data pages are compressed (device: snappy only, with -parquet_encoder device)")
+    add_region_arguments(ap)
     a = ap.parse_args(argv)
     if a.aggregate:
         ap.error("-aggregate is outside this build (PileupAggregator's result depends on Spark's shuffle order)")
     why = compressor_refusal(a.parquet_compressor, a.parquet_encoder, a.parquet_compression)
     if why:
         ap.error(why)
+    try:
+        a.region = region_plan(a.input, a.region, a.bai)
+    except (ValueError, OSError) as e:
+        ap.error(str(e))
     t0 = time.perf_counter()
     st = reads2ref(a.input, a.output, False, a.mapq, a.parquet_compression, a.part_reads, a.partition_bytes,
-                   a.overwrite, parquet_encoder=a.parquet_encoder, parquet_compressor=a.parquet_compressor)
+                   a.overwrite, parquet_encoder=a.parquet_encoder, parquet_compressor=a.parquet_compressor,
+                   region=a.region, bai=a.bai)
     report(st, t0)
     return 0
 

@@ -54,7 +54,7 @@ import numpy as np
 
 from . import _capi, bqsr
 from ._capi import check, dblp, vp
-from .inputs import Phases, SamInput, is_parquet, report, text_output
+from .inputs import Phases, SamInput, add_region_arguments, is_parquet, region_plan, report, text_output
 
 # the ADAMRecord columns read from Parquet: reads2ref's without the read-level
 # ones it only copies and without LocusPredicate's, except readMapped, which
@@ -145,14 +145,16 @@ def arrow_targets(reads, stream=None, sizes: Optional[RealignTargetsSizes] = Non
                 sizes)
 
 
-def realignment_targets(path: str, device: int = 0, stats: Optional[dict] = None) -> Dict[str, np.ndarray]:
+def realignment_targets(path: str, device: int = 0, stats: Optional[dict] = None, region: Optional[str] = None,
+                        bai: Optional[str] = None) -> Dict[str, np.ndarray]:
     """RealignmentTargetFinder over a SAM, BAM or ADAMRecord Parquet input (a
     file or a directory of part files): the targets as a dict of int64 numpy
     arrays -- ``target_start`` / ``target_end`` per target, ``indel_offset``
     / ``snp_offset`` (n_targets + 1 entries) into the ``indel_*`` and
     ``snp_*`` arrays.  Raises :class:`_capi.BQSRError` (``.read``: the read's
     index in the input) where the reference throws.  `stats`, when given,
-    receives the job's sizes, phase and kernel times."""
+    receives the job's sizes, phase and kernel times.  region, bai: BAM input read through its .bai index, only the reads that overlap the region (inputs.SamInput)."""
+    region = region_plan(path, region, bai)  # (refused before anything is read)
     ctx = bqsr.Context.get(device)
     ph = Phases()
 
@@ -178,7 +180,7 @@ def realignment_targets(path: str, device: int = 0, stats: Optional[dict] = None
         finally:
             A.close()
     else:
-        with SamInput(path, ctx, ph) as src:
+        with SamInput(path, ctx, ph, region=region, bai=bai) as src:
             for sam, _ in src:
                 out = job(lambda: sam_prepare(sam), lambda sz: sam_targets(sam, sizes=sz), sam.counts().n_reads)
     if stats is not None:
@@ -203,12 +205,13 @@ def format_targets(t: Dict[str, np.ndarray], targets_only: bool = False) -> str:
 
 
 def write_targets(inp: str, out: Optional[str] = None, targets_only: bool = False, device: int = 0,
-                  stdout=None) -> Dict[str, object]:
+                  stdout=None, region: Optional[str] = None, bai: Optional[str] = None) -> Dict[str, object]:
     """The command: the targets of `inp` as text to `out` or, without it, to
     stdout (inputs.text_output).  Returns the job's statistics."""
     stats: Dict[str, object] = {}
+    region = region_plan(inp, region, bai)  # (refused before anything is read or created)
     with text_output(out, stdout) as sink:
-        text = format_targets(realignment_targets(inp, device, stats), targets_only).encode()
+        text = format_targets(realignment_targets(inp, device, stats, region, bai), targets_only).encode()
         sink.write(text)
     stats["bytes"] = len(text)
     return stats
@@ -219,11 +222,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("input")
     ap.add_argument("-output", default=None, help="write the text here (default: stdout)")
     ap.add_argument("-targets_only", action="store_true", help="print only the T lines")
+    add_region_arguments(ap)
     a = ap.parse_args(argv)
     if not os.path.exists(a.input):
         ap.error("no such input: %s" % a.input)
+    try:
+        a.region = region_plan(a.input, a.region, a.bai)
+    except (ValueError, OSError) as e:
+        ap.error(str(e))
     t0 = time.perf_counter()
-    st = write_targets(a.input, a.output, a.targets_only)
+    st = write_targets(a.input, a.output, a.targets_only, region=a.region, bai=a.bai)
     report(st, t0)
     return 0
 

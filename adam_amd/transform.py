@@ -96,7 +96,7 @@ from . import _capi, bqsr
 from . import distributed as D
 from ._capi import check
 from .adam_save import check_out as _check_out
-from .inputs import DEFAULT_PARTITION_BYTES, SamInput, is_bam, is_parquet, report, sam_partitions  # noqa: F401
+from .inputs import DEFAULT_PARTITION_BYTES, SamInput, add_region_arguments, is_bam, is_parquet, region_plan, report, sam_partitions  # noqa: F401
 from .inputs import Phases as _Phases, host_bytes as _host_bytes  # noqa: F401
 from .parquet_pages import COMPRESSORS as PARQUET_COMPRESSORS, compressor_refusal
 from .sam import SamText
@@ -701,7 +701,8 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
               sort_reads: bool = False, bam_level: Optional[int] = None,
               bam_piece_reads: int = BAM_PIECE_READS, bam_compressor: Optional[str] = None,
               bam_index: bool = False, parquet_encoder: str = "host",
-              page_rows: Optional[int] = None, parquet_compressor: str = "host") -> Dict[str, float]:
+              page_rows: Optional[int] = None, parquet_compressor: str = "host", region: Optional[str] = None,
+              bai: Optional[str] = None) -> Dict[str, float]:
     """Transform.run (cli/Transform.scala:62-97) over SAM or BAM input: the
     records parsed on the device (a BAM's records become SAM lines there),
     MarkDuplicates, BQSR, then adamSave (OUT.adam / .parquet / a directory:
@@ -716,7 +717,12 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
     "device" and compression "snappy").
     ADAM Parquet input goes through transform_parquet (Arrow reads it on the
     host).  sort_reads: the records sorted on the device before the save (see
-    the module doc); the input must be one partition."""
+    the module doc); the input must be one partition.  region, bai: BAM
+    input read through its .bai index (inputs.SamInput): the job sees only the
+    reads that overlap the region, in one partition; MarkDuplicates and BQSR
+    work on what the region holds, so a mate outside it is absent, as if the
+    input were the filtered file."""
+    region = region_plan(inp, region, bai)  # before anything is read or created
     from .adam_save import is_adam_output
     bam_out = out.endswith(".bam")
     # ADAM output by name, or over an earlier adamSave directory (never just
@@ -763,13 +769,15 @@ def transform(inp: str, out: str, mark_duplicates: bool = False, recalibrate: bo
     try:
         ph = _Phases()
         # (without a step that works across the whole input the records go through in one parse)
-        with SamInput(inp, ctx, ph, partition_bytes if recalibrate or mark_duplicates or sort_reads else None) as src:
+        with SamInput(inp, ctx, ph, partition_bytes if recalibrate or mark_duplicates or sort_reads else None,
+                      region=region, bai=bai) as src:
             if src.n_partitions > 1:
                 stats = _partitions(src.data, src.header, src.ranges, mark_duplicates, recalibrate, dbsnp, ctx, device,
                                     sink.emit)
             else:
                 for sam, _ in src:
                     stats["reads"] = sam.counts().n_reads
+                    stats.update(src.region_stats or {})
                     if mark_duplicates:
                         with ph("markdup"):
                             stats["duplicates"] = sam.mark_duplicates()
@@ -848,6 +856,7 @@ def main(argv=None) -> int:
                          "coordinate order)")
     ap.add_argument("-overwrite", action="store_true",
                     help="replace an existing output (a file, or a directory of ADAM part files only)")
+    add_region_arguments(ap)
     a = ap.parse_args(argv)
     if a.realignIndels or a.coalesce != -1:
         ap.error("-coalesce / -realignIndels are outside this build")
@@ -860,12 +869,16 @@ def main(argv=None) -> int:
     why = compressor_refusal(a.parquet_compressor, a.parquet_encoder, a.parquet_compression)
     if why:
         ap.error(why)
+    try:
+        a.region = region_plan(a.input, a.region, a.bai)
+    except (ValueError, OSError) as e:
+        ap.error(str(e))
     t0 = time.perf_counter()
     st = transform(a.input, a.output, a.mark_duplicate_reads, a.recalibrate_base_qualities, a.dbsnp_sites,
                    partition_bytes=a.partition_bytes, compression=a.parquet_compression, part_reads=a.part_reads,
                    overwrite=a.overwrite, sort_reads=a.sort_reads, bam_level=a.bam_compression_level,
                    bam_compressor=a.bam_compressor, bam_index=a.bam_index, parquet_encoder=a.parquet_encoder,
-                   parquet_compressor=a.parquet_compressor)
+                   parquet_compressor=a.parquet_compressor, region=a.region, bai=a.bai)
     report(st, t0)
     return 0
 

@@ -452,6 +452,90 @@ bqsr_status bqsr_bam_index_bytes(const bqsr_bam_index* x, uint8_t* dst, int64_t 
  * events, the serialisation by the host clock. */
 bqsr_status bqsr_bam_index_kernel_times(const bqsr_bam_index* x, double* ms6);
 
+/* A BAM read in windows (bam_windows.hip): what `python -m adam_amd.bam_index`
+ * (the index of a BAM some other tool wrote) and `-region` (a read through a
+ * .bai index) share.  `bam` is the whole file in host memory (a read-only map);
+ * it must outlive the reader.  Device memory is bounded by the window.
+ *
+ * Members.  open walks the file's BSIZE / ISIZE fields (every member, empty
+ *   ones and the EOF marker included): bqsr_bam_reader_members hands out the
+ *   table bqsr_bam_index_set_members takes, [2 (n_members + 1)] uint64 of
+ *   (stream start, file offset) and the terminal (stream length, file size).
+ * Window.  A run of whole members, inflated on the device with the kernels of
+ *   bqsr_bgzf_inflate; a member those decline is inflated by the host, and one
+ *   the host declines too is BQSR_ERR_SAM_PARSE.  A window starts at the member
+ *   that holds the next record's first byte and takes members while it stays
+ *   within piece_bytes of inflated stream (1 .. 2^31) and before end_member
+ *   (at least one member); when it holds no whole record from its start it is
+ *   extended, member by member, to what that record's block_size asks for,
+ *   whatever piece_bytes and end_member say; a block_size that points past
+ *   the stream's end is the "truncated record" refusal at once, with nothing
+ *   more inflated.  The members the host inflated are counted (members_host),
+ *   and a parse that holds one reports bqsr_sam_bam_form 1, else 2.
+ * Walk.  The offsets of the window's complete records are found from the
+ *   known offset of the first: the header's end for the first window, where the
+ *   window before stopped for a later one, what bqsr_bam_reader_seek named for
+ *   a region read.  The device chain is bqsr_bam_parse's (a guess per member,
+ *   a check that every walk lands on the next guess, the offsets written at
+ *   scanned counts) with two changes: the first member's start is the given
+ *   one, and the last walk may leave the window: the record it cannot finish
+ *   is not taken, and the next window starts at the member that holds its
+ *   first byte.  Where the check declines, the window's bytes are walked by the
+ *   host (bqsr_bam_window.device = 0; the stats count both forms).
+ * Header.  Magic, text and reference list are read by open from windows of the
+ *   file's first members (they are not counted as members read).
+ * Refusals, BQSR_ERR_SAM_PARSE: not BGZF, a member cut by the file's end, no
+ *   BAM magic, a member that does not inflate, a block_size below 32, a record
+ *   whose name and CIGAR do not fit its block_size, a record the file's end
+ *   cuts ("truncated record").  Those about a record name it by its ordinal
+ *   among the records seen (bqsr_last_error_read): the ordinal in the file for
+ *   a read from the header's end on.
+ *
+ * open; then next until .done (n_records may be 0 only with .done); after each
+ * next, the window's records go to an index (bqsr_bam_index_add_window: a row
+ * each, with the interval rule stated at bqsr_bam_index_create, from refID, pos,
+ * FLAG and the CIGAR words of the raw record) or through the region filter:
+ * bqsr_bam_reader_filter keeps, a lane per record, those with refID == ref, beg
+ * < end and end > beg in that interval (so a placed read with FLAG 0x4 is
+ * kept) that start before stream position `limit` (a chunk's v; a malformed
+ * record at or past it is not this read's to refuse); the kept
+ * records are compacted by a scan and a copy (a wavefront stores its 64
+ * records' bytes contiguously) into one device buffer that lives across
+ * windows.  *done: 1 when a record at or past `limit` was seen (the chunk is
+ * over), 2 when a record of a later reference, without one, or with beg >= end
+ * was seen: in a sorted file nothing after it overlaps, and nothing after it is
+ * kept.  bqsr_bam_reader_seek (member index, offset inside its inflated bytes)
+ * sets where the next window's first record starts.  bqsr_bam_reader_parse
+ * turns the kept records into a bqsr_sam as bqsr_bam_parse does for a whole
+ * file (the same lines kernels and parse): header plus kept records in the
+ * order they were kept. */
+typedef struct bqsr_bam_reader bqsr_bam_reader;
+typedef struct bqsr_bam_window {
+  int64_t n_records;     /* complete records found in this window */
+  int64_t member_begin;  /* the window's members [member_begin, member_end) */
+  int64_t member_end;
+  int64_t next_pos;      /* stream position of the next record */
+  int32_t device;        /* 1: the device chain; 0: the host's walk */
+  int32_t done;          /* the stream's end is reached */
+} bqsr_bam_window;
+typedef struct bqsr_bam_reader_stats {
+  int64_t members_total, stream_bytes, n_ref, body;
+  int64_t members_read, windows_device, windows_host, records_seen, records_kept;
+  int64_t members_host;  /* members the kernels declined and the host inflated (the header's windows included) */
+  double filter_ms;      /* region filter, scan and copy, by device events */
+} bqsr_bam_reader_stats;
+bqsr_status bqsr_bam_reader_open(bqsr_context* ctx, const uint8_t* bam, int64_t n_bytes, int64_t piece_bytes,
+                                 void* stream, bqsr_bam_reader** out);
+void bqsr_bam_reader_destroy(bqsr_bam_reader* r);
+bqsr_status bqsr_bam_reader_members(const bqsr_bam_reader* r, uint64_t* members, int64_t cap);
+bqsr_status bqsr_bam_reader_seek(bqsr_bam_reader* r, int64_t member, int64_t offset);
+bqsr_status bqsr_bam_reader_next(bqsr_bam_reader* r, int64_t end_member, void* stream, bqsr_bam_window* out);
+bqsr_status bqsr_bam_index_add_window(bqsr_bam_index* x, bqsr_bam_reader* r, void* stream);
+bqsr_status bqsr_bam_reader_filter(bqsr_bam_reader* r, int32_t ref, int64_t beg, int64_t end, int64_t limit,
+                                   void* stream, int64_t* kept, int32_t* done);
+bqsr_status bqsr_bam_reader_parse(bqsr_bam_reader* r, void* stream, bqsr_sam** out);
+bqsr_status bqsr_bam_reader_get_stats(const bqsr_bam_reader* r, bqsr_bam_reader_stats* out);
+
 /* MarkDuplicates (§8 f3): adam-core/.../rdd/MarkDuplicates.scala:24-111 over
  * SingleReadBucket (models/SingleReadBucket.scala:27-37: reads grouped by
  * (recordGroupId, readName)) and ReferencePositionPair

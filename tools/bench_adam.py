@@ -66,6 +66,14 @@ spread.  One JSON line.
 
     python tools/bench_adam.py --bam-out --bam-index [--reads 2000000] [--bam-level 6]
 
+--bam-region measures `python -m adam_amd.bam_index OUT.bam` (the index of an
+existing BAM, built from windows of the file: bam_windows.hip) next to the
+index stages of `transform -bam_index` on the same reads and next to
+tests/_bai_ref.bai_of_bam on the same file, and `flagstat OUT.bam -region R`
+(R holds about 1 % of the reads, read through the index) next to `flagstat
+OUT.bam`: the 2M reads sorted by position, all legs in one process, warmed,
+three timed runs each, alternating; medians and spreads.
+
 --bam-out --bam-index measures `transform IN.sam OUT.bam -bam_index`
 (transform._BamOut, bam_index.hip) over the same synthetic reads sorted by
 position on the host, MarkDuplicates, no BQSR: with the host compressor at
@@ -1320,6 +1328,110 @@ def bench_bam_index(a):
         "not_measured": "real coverage (the synthetic reads spread evenly), inputs above one partition"}))
 
 
+def bench_bam_region(a):
+    """--bam-region: see the module doc"""
+    import statistics
+    t0 = time.perf_counter()
+    data = sorted_by_position(synthetic_sam(a.reads, a.len, p_q2tail=0.0))
+    log("generated and sorted %d bytes in %.1f s" % (len(data), time.perf_counter() - t0))
+    # a region holding about 1 % of the reads: around the middle of the reference with the most reads
+    recs = [l.split(b"\t", 4) for l in data.split(b"\n") if l and not l.startswith(b"@")]
+    placed = [(f[2], int(f[3])) for f in recs if f[2] != b"*"]
+    name = placed[len(placed) // 2][0]
+    pos = [q for n, q in placed if n == name]
+    k = max(1, a.reads // 200)
+    mid = len(pos) // 2
+    region = "%s:%d-%d" % (name.decode(), pos[max(0, mid - k)], pos[min(len(pos) - 1, mid + k)])
+    del recs, placed, pos
+    import torch
+    from adam_amd import bam_index as BI
+    from adam_amd import flagstat as F
+    from adam_amd import transform as T
+    torch.zeros(1, device="cuda")
+    work = a.dir or tempfile.mkdtemp(prefix="bench_adam_")
+    os.makedirs(work, exist_ok=True)
+    src, bam = os.path.join(work, "in.sam"), os.path.join(work, "out.bam")
+    with open(src, "wb") as fh:
+        fh.write(data)
+    n_bytes = len(data)
+    del data
+    reps = max(3, a.reps)
+    pb = a.partition_bytes
+
+    def summary(times):
+        return {"seconds_median": statistics.median(times), "seconds_all": times,
+                "seconds_spread": max(times) - min(times)}
+
+    try:
+        # the BAM and, beside it, the index transform builds while it writes: its stages, for the same reads
+        written = []
+        for i in range(1 + reps):
+            log("%s transform -> out.bam -bam_index" % ("warm-up" if i == 0 else "timed"))
+            t = time.perf_counter()
+            st = T.transform(src, bam, mark_duplicates=False, partition_bytes=pb, overwrite=True, bam_index=True)
+            written.append((time.perf_counter() - t, st))
+        with open(bam + ".bai", "rb") as fh:
+            theirs = fh.read()
+        legs = {"bam_index": [], "flagstat_whole": [], "flagstat_region": []}
+        last = {}
+        for i in range(1 + reps):  # the first round warms; the legs alternate
+            for leg in legs:
+                log("%s %s" % ("warm-up" if i == 0 else "timed", leg))
+                t = time.perf_counter()
+                if leg == "bam_index":
+                    st = BI.bam_index(bam, out=os.path.join(work, "again.bai"), overwrite=True)
+                elif leg == "flagstat_whole":
+                    st = F._flagstat(bam, 0, pb)[2]
+                else:
+                    st = F._flagstat(bam, 0, pb, region)[2]
+                if i:
+                    legs[leg].append(time.perf_counter() - t)
+                last[leg] = st
+        with open(os.path.join(work, "again.bai"), "rb") as fh:
+            equal = fh.read() == theirs
+        if not equal:
+            raise SystemExit("bam_index on the finished file differs from the index transform wrote")
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import _bai_ref
+        with open(bam, "rb") as fh:
+            raw = fh.read()
+        t = time.perf_counter()
+        restated = _bai_ref.bai_of_bam(raw) == theirs
+        t_restated = time.perf_counter() - t
+        del raw
+        if not restated:
+            raise SystemExit("the index differs from the restatement's")
+        bi, fr, fw = last["bam_index"], last["flagstat_region"], last["flagstat_whole"]
+        region_s, whole_s = summary(legs["flagstat_region"]), summary(legs["flagstat_whole"])
+        gain = whole_s["seconds_median"] - region_s["seconds_median"]
+        spread = max(region_s["seconds_spread"], whole_s["seconds_spread"])
+        print(json.dumps({
+            "metric": "bam_index on an existing BAM, and flagstat -region through the index, against the whole file; "
+                      "reads sorted by position, all legs in one process, warmed, %d timed runs each, alternating" % reps,
+            "reads": a.reads, "read_len": a.len, "input_bytes": n_bytes, "bam_bytes": os.path.getsize(bam),
+            "reps": reps, "region": region,
+            "bam_index": dict(summary(legs["bam_index"]), stage_ms=bi["index_ms"],
+                              device_ms=sum(v for k, v in bi["index_ms"].items() if not k.endswith("_host")),
+                              windows_device=bi["windows_device"], windows_host=bi["windows_host"],
+                              members=bi["members_total"], index_bytes=bi["index_bytes"], equal_to_transform_s=equal),
+            "transform_bam_index": dict(summary([dt for dt, _ in written[1:]]),
+                                        stage_ms=written[-1][1]["bam"]["index_ms"],
+                                        member_walk_host_s=written[-1][1]["bam"]["index_walk_s"]),
+            "restatement": {"seconds": t_restated, "equal": restated,
+                            "what": "tests/_bai_ref.bai_of_bam on the same file (single-threaded Python)"},
+            "flagstat_whole": dict(whole_s, reads=fw["reads"], phases=fw["phases"]),
+            "flagstat_region": dict(region_s, reads=fr["reads"], phases=fr["phases"],
+                                    members_read=fr.get("members_read"), members_total=fr.get("members_total"),
+                                    records_seen=fr.get("records_seen"), records_kept=fr.get("records_kept"),
+                                    filter_ms=fr.get("filter_ms"), share_of_reads=fr["reads"] / a.reads),
+            "region_faster_by_s": gain, "region_faster_than_spread": gain > spread,
+            "not_measured": "BAMs written by other tools, real coverage (the synthetic reads spread evenly), files "
+                            "above one window"}))
+    finally:
+        if not a.dir:
+            shutil.rmtree(work, ignore_errors=True)
+
+
 def bench_adam2sam(a):
     """--adam2sam: the synthetic reads written once as .adam, then in one
     process, after a warm-up each, max(3, --reps) timed runs of ADAM -> SAM and
@@ -1420,6 +1532,8 @@ def main():
                     help="measure adam2sam (ADAM -> SAM / BAM) next to transform SAM -> SAM / BAM instead")
     ap.add_argument("--bam-index", action="store_true",
                     help="--bam-out: measure -bam_index instead (legs with and without the index, both compressors)")
+    ap.add_argument("--bam-region", action="store_true",
+                    help="measure bam_index on an existing BAM and flagstat -region through its index")
     ap.add_argument("--bam-out", action="store_true",
                     help="measure transform SAM -> BAM next to SAM -> SAM text instead of the ADAM transform")
     ap.add_argument("--bam-level", type=int, default=6, help="--bam-out: the BGZF members' DEFLATE level")
@@ -1471,6 +1585,8 @@ def main():
         return bench_reads2ref_pages(a) if a.parquet_encoder else bench_reads2ref(a)
     if a.aggregate:
         return bench_aggregate(a)
+    if a.bam_region:
+        return bench_bam_region(a)
     if a.bam_out:
         return bench_bam_index(a) if a.bam_index else bench_bam_out(a)
     if a.parquet_encoder:
