@@ -257,12 +257,116 @@ extern "C" __global__ void __launch_bounds__(kScanThreads) scan_apply(const uint
 }
 
 // ---- Java float text (tag values of type 'f') ----
-// java.lang.Float.toString: the fewest significant digits (at most 9) that
-// read back as the same float; plain notation for 1e-3 <= |f| < 1e7
-// ("100.0", "0.00125"), else "d.dddE[-]n" ("1.0E7", "1.5E-4"); "NaN",
-// "Infinity", "0.0" / "-0.0".  Powers of ten and the read-back are double
-// arithmetic: exact for the float's digits except at decimal ties (parity
-// unpinned).  out == nullptr: the length only.
+// Both directions are exact: 256-bit integers (four 64-bit limbs at fixed
+// indices, so they stay in registers) wherever a double could round.
+struct U256 {
+  uint64_t w[4];
+};
+// x = x * c + add
+__device__ __forceinline__ void u256_muladd(U256& x, uint64_t c, uint64_t add) {
+  unsigned __int128 t = add;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    t += (unsigned __int128)x.w[i] * c;
+    x.w[i] = (uint64_t)t;
+    t >>= 64;
+  }
+}
+// x <<= n, 0 <= n < 256
+__device__ __forceinline__ void u256_shl(U256& x, int n) {
+  if (n & 128) {
+    x.w[3] = x.w[1], x.w[2] = x.w[0], x.w[1] = 0, x.w[0] = 0;
+  }
+  if (n & 64) {
+    x.w[3] = x.w[2], x.w[2] = x.w[1], x.w[1] = x.w[0], x.w[0] = 0;
+  }
+  const int b = n & 63;
+  if (b) {
+    x.w[3] = (x.w[3] << b) | (x.w[2] >> (64 - b));
+    x.w[2] = (x.w[2] << b) | (x.w[1] >> (64 - b));
+    x.w[1] = (x.w[1] << b) | (x.w[0] >> (64 - b));
+    x.w[0] <<= b;
+  }
+}
+// x >>= n, 0 <= n < 256; true when a set bit fell off
+__device__ __forceinline__ bool u256_shr(U256& x, int n) {
+  uint64_t lost = 0;
+  if (n & 128) {
+    lost |= x.w[0] | x.w[1];
+    x.w[0] = x.w[2], x.w[1] = x.w[3], x.w[2] = 0, x.w[3] = 0;
+  }
+  if (n & 64) {
+    lost |= x.w[0];
+    x.w[0] = x.w[1], x.w[1] = x.w[2], x.w[2] = x.w[3], x.w[3] = 0;
+  }
+  const int b = n & 63;
+  if (b) {
+    lost |= x.w[0] << (64 - b);
+    x.w[0] = (x.w[0] >> b) | (x.w[1] << (64 - b));
+    x.w[1] = (x.w[1] >> b) | (x.w[2] << (64 - b));
+    x.w[2] = (x.w[2] >> b) | (x.w[3] << (64 - b));
+    x.w[3] >>= b;
+  }
+  return lost != 0;
+}
+// x /= c; true when a remainder was left
+__device__ __forceinline__ bool u256_div(U256& x, uint32_t c) {
+  uint64_t r = 0;
+#pragma unroll
+  for (int i = 3; i >= 0; --i) {
+    const uint64_t hi = (r << 32) | (x.w[i] >> 32);
+    const uint64_t qh = hi / c;
+    const uint64_t lo = ((hi - qh * c) << 32) | (x.w[i] & 0xffffffffull);
+    const uint64_t ql = lo / c;
+    r = lo - ql * c;
+    x.w[i] = (qh << 32) | ql;
+  }
+  return r != 0;
+}
+__device__ __forceinline__ uint64_t pow5_u64(int k) {  // 5^k, 0 <= k <= 27
+  const uint64_t kP[28] = {
+      1ull, 5ull, 25ull, 125ull, 625ull, 3125ull, 15625ull, 78125ull, 390625ull, 1953125ull, 9765625ull, 48828125ull,
+      244140625ull, 1220703125ull, 6103515625ull, 30517578125ull, 152587890625ull, 762939453125ull, 3814697265625ull,
+      19073486328125ull, 95367431640625ull, 476837158203125ull, 2384185791015625ull, 11920928955078125ull,
+      59604644775390625ull, 298023223876953125ull, 1490116119384765625ull, 7450580596923828125ull};
+  return kP[k];
+}
+// floor(x * 2^a / 10^s) for x < 2^27, a result below 2^64 and |a|, |s| within
+// a binary32's range; *exact: nothing was cut off.  10^s = 5^s * 2^s: the
+// fives multiply or divide, the twos shift.
+__device__ uint64_t scaled_floor(uint64_t x, int a, int s, bool* exact) {
+  U256 n = {{x, 0, 0, 0}};
+  bool cut = false;
+  const int b = a - s;
+  if (s <= 0) {
+    int q = -s;
+    for (; q > 27; q -= 27) u256_muladd(n, pow5_u64(27), 0);
+    u256_muladd(n, pow5_u64(q), 0);
+    if (b >= 0)
+      u256_shl(n, b);
+    else
+      cut = u256_shr(n, -b);
+  } else {
+    if (b >= 0)
+      u256_shl(n, b);
+    else
+      cut = u256_shr(n, -b);
+    int q = s;
+    for (; q > 13; q -= 13) cut |= u256_div(n, (uint32_t)pow5_u64(13));
+    cut |= u256_div(n, (uint32_t)pow5_u64(q));
+  }
+  *exact = !cut;
+  return n.w[0];
+}
+// java.lang.Float.toString, made exact: the smallest digit count p (from 2,
+// the two digits of "d.d", to 9) for which a p-digit decimal lies inside the
+// float's rounding interval --
+// the reals that read back as it: ends included when the mantissa is even, the
+// lower half narrower at a power of two -- and of the decimal below and the
+// one above the value the nearer one inside.  Plain notation for 1e-3 <= |f|
+// < 1e7 ("100.0", "0.00125"), else "d.dddE[-]n" ("1.0E7", "1.5E-4"); "NaN",
+// "Infinity", "0.0" / "-0.0".  (JDKs before 19 print some floats a digit
+// longer; that is not reproduced, DESIGN.md.)  out == nullptr: the length only.
 __device__ double pow10_d(int k) {
   const double kP[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
                          1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
@@ -283,30 +387,52 @@ __device__ int put_text(uint8_t* out, int n, const char* t) {
 }
 __device__ int java_float_text(float f, uint8_t* out) {
   int n = 0;
-  if (f != f) return put_text(out, 0, "NaN");
-  if (__builtin_signbit(f)) n = put_text(out, n, "-");
-  const double x = fabs((double)f);
-  if (isinf(x)) return put_text(out, n, "Infinity");
-  if (x == 0.0) return put_text(out, n, "0.0");
-  int k = (int)floor(log10(x));
-  while (k > -60 && pow10_d(k) > x) --k;
-  while (k < 60 && pow10_d(k + 1) <= x) ++k;
-  uint32_t dig = 0;
-  int e = k, p = 1;
-  for (; p <= 9; ++p) {
-    const int sh = p - 1 - k;
-    const double y = sh >= 0 ? x * pow10_d(sh) : x / pow10_d(-sh);
-    const double d = rint(y);
-    const double v = sh >= 0 ? d / pow10_d(sh) : d * pow10_d(-sh);
-    if ((float)v == fabsf(f) || p == 9) {
-      dig = (uint32_t)d;
-      e = k;
-      if (d >= pow10_d(p)) {  // rounded up to 10^p: one more decade
-        dig /= 10u;
-        e = k + 1;
-      }
+  const uint32_t u = __builtin_bit_cast(uint32_t, f);
+  const uint32_t ef = (u >> 23) & 0xffu, mf = u & 0x7fffffu;
+  if (ef == 0xffu && mf) return put_text(out, 0, "NaN");
+  if (u >> 31) n = put_text(out, n, "-");
+  if (ef == 0xffu) return put_text(out, n, "Infinity");
+  if (!(ef | mf)) return put_text(out, n, "0.0");
+  // |f| = m * 2^(a + 2); in units of 2^a the value is 4m, the interval [4m - (1 or 2), 4m + 2]
+  const uint32_t m = ef ? mf | 0x800000u : mf;
+  const int a = (int)(ef ? ef : 1u) - 152;
+  // 10^k <= |f| < 10^(k+1): floor(log10 2^x) from x * 78913 >> 18, then set right by the nine-digit quotient
+  int k = ((32 - __builtin_clz(m) + a + 1) * 78913) >> 18;
+  uint64_t d2;  // floor(2 |f| / 10^(k-8)): the nine digits and the half bit
+  bool ex;
+  for (;;) {
+    d2 = scaled_floor(8ull * m, a, k - 8, &ex);
+    if (d2 >= 2000000000ull)
+      ++k;
+    else if (d2 < 200000000ull)
+      --k;
+    else
+      break;
+  }
+  const uint32_t d9 = (uint32_t)(d2 >> 1), half = (uint32_t)(d2 & 1);
+  // the integers c with c * 10^(k-8) inside the interval: lo <= c <= hi
+  const bool even = !(m & 1u);
+  bool exl, exh;
+  const uint64_t fl = scaled_floor(4ull * m - ((mf == 0 && ef > 1) ? 1 : 2), a, k - 8, &exl);
+  const uint64_t fh = scaled_floor(4ull * m + 2, a, k - 8, &exh);
+  const uint64_t lo = (even && exl) ? fl : fl + 1, hi = (even || !exh) ? fh : fh - 1;
+  uint32_t dig = d9 + half;  // (nine digits always hold one: the loop finds it)
+  uint32_t step = 10000000u;
+  for (int p = 2; p <= 9; ++p, step /= 10u) {  // (the text shows two digits at least: "d.d")
+    const uint32_t below = d9 - d9 % step, above = below + step;
+    // 2 (|f| - below) against step, in units of 10^(k-8): 2 (d9 - below) + half (+ a fraction unless ex)
+    const uint32_t t = 2u * (d9 - below) + half;
+    const bool first_below = t < step || (t == step && ex && !((below / step) & 1u));  // (a tie: the even digit)
+    const bool in_b = below >= lo && below <= hi, in_a = above >= lo && above <= hi;
+    if (in_b || in_a) {
+      dig = (in_b && (first_below || !in_a)) ? below : above;
       break;
     }
+  }
+  int e = k;
+  if (dig >= 1000000000u) {  // rounded up to 10^9: one more decade
+    dig = 1u;
+    e = k + 1;
   }
   uint8_t D[10];
   int nd = 0;
@@ -362,7 +488,56 @@ __device__ int java_float_text(float f, uint8_t* out) {
   }
   return n;
 }
-// java.lang.Float.parseFloat of t[a, b) (decimal forms, NaN / Infinity);
+// The sign of D - odd * 2^j, D the decimal 0.s0 s1 s2 ... * 10^top whose
+// digits stand in t[first, dend) (s0 not '0', a '.' among them skipped):
+// exact for any number of digits.  odd < 2^26, -150 <= j <= 105, top <= 39.
+// odd * 2^j = I + R / 2^252; the integer parts compare as integers, then the
+// fraction's digits come off R one by one (it is spent after -j of them)
+// against the rest of the text.
+__device__ int decimal_cmp_dyadic(const uint8_t* t, int64_t first, int64_t dend, int top, uint32_t odd, int j) {
+  U256 I = {{0, 0, 0, 0}}, R = {{0, 0, 0, 0}};
+  if (j >= 0) {
+    I.w[0] = odd;
+    u256_shl(I, j);
+  } else {
+    const int sh = -j;
+    I.w[0] = sh < 32 ? odd >> sh : 0u;
+    R.w[0] = sh < 32 ? odd & ((1u << sh) - 1u) : odd;
+    u256_shl(R, 252 - sh);
+  }
+  int64_t p = first;
+  auto next = [&]() -> int {  // the next digit, -1 behind the last
+    if (p < dend && t[p] == '.') ++p;
+    return p < dend ? (int)t[p++] - '0' : -1;
+  };
+  U256 A = {{0, 0, 0, 0}};  // the text's integer part: its first `top` digits, zeros where it ends sooner
+  for (int q = 0; q < top; ++q) {
+    const int c = next();
+    u256_muladd(A, 10, c < 0 ? 0 : (uint64_t)c);
+  }
+#pragma unroll
+  for (int i = 3; i >= 0; --i)
+    if (A.w[i] != I.w[i]) return A.w[i] < I.w[i] ? -1 : 1;
+  int zeros = top < 0 ? -top : 0;  // the digits begin that far behind the point
+  for (;;) {
+    if (!(R.w[0] | R.w[1] | R.w[2] | R.w[3])) {  // the fraction is spent: any digit left but '0' is more
+      for (int c; (c = next()) >= 0;)
+        if (c) return 1;
+      return 0;
+    }
+    int c = 0;
+    if (zeros > 0)
+      --zeros;
+    else if ((c = next()) < 0)
+      return -1;
+    u256_muladd(R, 10, 0);
+    const int g = (int)(R.w[3] >> 60);
+    R.w[3] &= (1ull << 60) - 1;
+    if (c != g) return c < g ? -1 : 1;
+  }
+}
+// java.lang.Float.parseFloat of t[a, b) (decimal forms, NaN / Infinity),
+// correctly rounded (nearest, ties to even) whatever the number of digits;
 // false when it would throw NumberFormatException
 __device__ bool java_parse_float(const uint8_t* t, int64_t a, int64_t b, float* v) {
   while (a < b && t[a] <= ' ') ++a;  // String.trim
@@ -386,16 +561,18 @@ __device__ bool java_parse_float(const uint8_t* t, int64_t a, int64_t b, float* 
     *v = neg ? -__builtin_inff() : __builtin_inff();
     return true;
   }
-  uint64_t m = 0;
-  int nd = 0, dexp = 0;
+  uint64_t m = 0;  // the first 19 significant digits
+  int nd = 0;
+  int64_t dexp = 0;  // the digits' value is about m * 10^dexp, and below 10^(nd + dexp)
   bool any = false, dot = false;
-  int64_t i = a;
+  int64_t i = a, first = -1;  // first: the first significant digit
   for (; i < b; ++i) {
     const uint8_t c = t[i];
     if (c >= '0' && c <= '9') {
       any = true;
       if (nd < 19) {
         if (m || c != '0') {
+          if (!m) first = i;
           m = m * 10 + (c - '0');
           ++nd;
         }
@@ -410,22 +587,49 @@ __device__ bool java_parse_float(const uint8_t* t, int64_t a, int64_t b, float* 
     }
   }
   if (!any) return false;
+  const int64_t dend = i;  // the end of the digits
   if (i < b && (t[i] == 'e' || t[i] == 'E')) {
     ++i;
     bool en = false;
     if (i < b && (t[i] == '+' || t[i] == '-')) en = t[i++] == '-';
     if (i >= b) return false;
-    int x = 0;
-    for (; i < b && t[i] >= '0' && t[i] <= '9'; ++i) x = x < 100000 ? x * 10 + (t[i] - '0') : x;
+    int64_t x = 0;
+    for (; i < b && t[i] >= '0' && t[i] <= '9'; ++i) x = x < (1ll << 56) ? x * 10 + (t[i] - '0') : x;
     dexp += en ? -x : x;
   }
   if (i < b && (t[i] == 'f' || t[i] == 'F' || t[i] == 'd' || t[i] == 'D')) ++i;  // Java's type suffixes
   if (i != b) return false;
-  double d = (double)m;
-  if (dexp < -340) d = 0.0;
-  else if (dexp > 0) d *= pow10_d(dexp > 320 ? 320 : dexp);
-  else if (dexp < 0) d /= pow10_d(-dexp > 320 ? 320 : -dexp);
-  *v = neg ? -(float)d : (float)d;
+  const uint32_t sign = neg ? 0x80000000u : 0u;
+  uint32_t bits;
+  const int64_t top = nd + dexp;  // 10^(top-1) <= value < 10^top
+  if (!m || top < -45) {          // below 1e-46 < 2^-150, half the smallest subnormal
+    bits = 0;
+  } else if (top > 39) {  // 1e39 and more
+    bits = 0x7f800000u;
+  } else {
+    // a double within 2^-49 of the value (relative): the 19 digits cut off at most 1e-18; the conversion, the two
+    // roundings inside pow10_d (|dexp| <= 64: three factors) and the multiply or divide 2^-53 each
+    double d = (double)m;
+    if (dexp > 0) d *= pow10_d((int)dexp);
+    else if (dexp < 0) d /= pow10_d((int)-dexp);
+    const uint64_t db = __builtin_bit_cast(uint64_t, d);
+    const int E = (int)((db >> 52) & 0x7ffu) - 1023;  // (1e-65 <= d <= 1e39: normal)
+    const int Eb = E < -126 ? -126 : E;                // the float grid there: steps of 2^(Eb - 23)
+    const int sh = 29 + (Eb - E);                      // (2^-156 < 1e-46 <= d: sh < 60)
+    const uint64_t m53 = (db & ((1ull << 52) - 1)) | (1ull << 52);
+    const uint32_t n = (uint32_t)(m53 >> sh);
+    const uint64_t rem = m53 & ((1ull << sh) - 1), mid = 1ull << (sh - 1);
+    bool up = rem > mid;
+    // d is 2^28 ulps or more wide of a grid point's neighbours' midpoints unless it is near this one; 64 ulps
+    // clear of it the value is on d's side.  Else the digits themselves against the midpoint (2n + 1) 2^(Eb - 24).
+    if ((up ? rem - mid : mid - rem) <= 64) {
+      const int c = decimal_cmp_dyadic(t, first, dend, top, 2u * n + 1u, Eb - 24);
+      up = c > 0 || (c == 0 && (n & 1u));  // a tie: to the even one
+    }
+    bits = ((uint32_t)(Eb + 126) << 23) + n + (up ? 1u : 0u);  // (a carry out of n lands in the exponent)
+    if (bits > 0x7f800000u) bits = 0x7f800000u;
+  }
+  *v = __builtin_bit_cast(float, sign | bits);
   return true;
 }
 

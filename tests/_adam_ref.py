@@ -18,6 +18,8 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
+from _float_ref import f32_bits_of_decimal, shortest_text
+
 OPS = "MIDNSHP=X"
 
 
@@ -33,6 +35,8 @@ def java_float_str(v) -> str:
     if f == 0:
         return sign + "0.0"
     s = np.format_float_scientific(abs(f), unique=True, trim="-")  # e.g. 1.5e+00, 1e-05
+    if "." not in s:  # one digit would do: Java takes the nearest of two digits (Float.MIN_VALUE is 1.4E-45)
+        s = np.format_float_scientific(abs(f), precision=1, unique=False)
     mant, exp = s.split("e")
     digits = mant.replace(".", "").rstrip("0") or "0"
     e = int(exp)
@@ -152,7 +156,7 @@ def convert_sam(text: bytes, run_date=None) -> List[dict]:
                 assert -2 ** 31 <= v < 2 ** 31
                 val = str(v)
             elif typ == "f":
-                val = java_float_str(float(val))
+                val = shortest_text(f32_bits_of_decimal(val.encode("latin-1")))  # Float.parseFloat, Float.toString
             else:
                 assert typ in "AZ", typ
             parts.append("%s:%s:%s" % (name, typ, val))

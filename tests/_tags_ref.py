@@ -33,6 +33,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from _adam_ref import java_float_str
+from _float_ref import f32_bits_of_decimal
 
 Record = Tuple[Optional[bytes], Optional[bool]]
 TYPE_ORDER = "AifZH"
@@ -66,16 +67,14 @@ def java_int(s: bytes) -> int:
 
 def java_float(s: bytes) -> np.float32:
     """Float.valueOf: String.trim (chars <= ' '), decimal forms with an
-    optional type suffix, NaN, Infinity"""
+    optional type suffix, NaN, Infinity; the nearest binary32 of the decimal
+    itself (tests/_float_ref.py)"""
     s = s.strip(bytes(range(0x21)))
     if re.match(rb"[+-]?0[xX]", s):
         raise TagRefError("UNSUPPORTED", "a hexadecimal float: %r" % s)
     if not _FLOAT.match(s):
         raise TagRefError("ATTRIBUTE", "NumberFormatException: %r" % s)
-    if s[-1:] in b"fFdD" and not s.endswith(b"Infinity"):
-        s = s[:-1]
-    with np.errstate(over="ignore"):
-        return np.float32(float(s.decode("ascii").replace("Infinity", "inf").replace("NaN", "nan")))
+    return np.uint32(f32_bits_of_decimal(s)).view(np.float32)  # correctly rounded: no detour over a double
 
 
 class Attribute:
